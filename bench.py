@@ -36,6 +36,10 @@ The JSON line also carries
   other_workloads : one chain each of configs[1] (C-alpha x 32), configs[4] on one GPU (joint
                     RePaint x 64) and the heterogeneous-pocket batch, so that the driver's
                     record holds them
+
+--dump-outputs DIR writes what the last timed chain returned (ligand, ligand_mask, pocket,
+pocket_mask) as DIR/<name>.npy; the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import json
@@ -408,6 +412,18 @@ def training_leg(device, n_lig_atoms, steps=10, warmup=3, workload="crossdock_fu
                          "recompute_flops_per_step_not_counted_only_with_DSBDD_TRAIN_STORE_Z2_0": recompute}}
 
 
+def dump_outputs(outdir, arrays, budget=64 << 20):
+    """--dump-outputs: every array as outdir/<name>.npy.  Over `budget` bytes in all, every array keeps the same fixed,
+    seeded sample of its rows (arrays of equal length keep the same rows, so a ligand and its mask stay paired)."""
+    os.makedirs(outdir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget:
+            n = max(1, int(a.shape[0] * budget / total))
+            a = a[np.sort(np.random.RandomState(0).choice(a.shape[0], n, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def self_launch(n, attempts=3):
     """Re-exec this script under torch.distributed.run with n ranks on this node
     (rendezvous on 127.0.0.1 and a free port); returns the job's exit code.  The port is probed and released before
@@ -491,6 +507,10 @@ def main():
     ap.add_argument("--dump-ligands", default=None,
                     help="rank 0 writes the gathered ligands of the LAST timed chain (all_lig [rows, 3 + atom_nf], all_mask = "
                          "global sample ids) to this .npz (tests: the gathered result of W ranks == W sequential world-1 runs)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the LAST timed chain returned to its caller as DIR/<name>.npy (float32 / float64): "
+                         "ligand (gathered over the ranks), ligand_mask (global sample ids), pocket, pocket_mask; at most "
+                         "64 MB in all (beyond that a fixed, seeded sample of the rows)")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="testing only: all ranks use cuda:0 (needs --backend gloo)")
@@ -535,6 +555,8 @@ def main():
                                                     n_same=((args.n_same or 5 * B // 8) if args.pockets == "grouped" else 0))
         anchor = None if joint else anchor_m
 
+    last = {}                                       # the latest chain's return values, for --dump-outputs
+
     def chain(seed, states=None):
         states = states or args.states
         model.seed(seed, sample_offset=lo)
@@ -553,6 +575,7 @@ def main():
                                                  resamplings=2, jump_length=1, timesteps=T)
         else:
             out_l, out_p, lm, pm = model.sample_given_pocket(pocket, n_lig, timesteps=T)
+        last.update(pocket=out_p, pocket_mask=pm)
         return sharding.gather_ligands(out_l, lm, lo)
 
     def barrier():
@@ -583,6 +606,12 @@ def main():
         all_lig, all_mask = chain(200 + k)
     sync()
     elapsed = time.perf_counter() - t0
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        # copied to the host now: the legs below run more chains on the same model
+        outputs = {"ligand": all_lig.float(), "ligand_mask": all_mask.double(),
+                   "pocket": last["pocket"].float(), "pocket_mask": last["pocket_mask"].double()}
+        outputs = {k: v.cpu().numpy() for k, v in outputs.items()}
     kern_ms, kern_n = (eng.profile_read() if not args.no_kernel_timing else (0.0, 0))
     eng.profile(False, 0)
     lv_main = eng.level_stats(since=lv0)
@@ -669,6 +698,8 @@ def main():
         offsets = [int(b.item()) for b in buf]
     if rank == 0 and args.dump_ligands:
         np.savez(args.dump_ligands, all_lig=all_lig.cpu().numpy(), all_mask=all_mask.cpu().numpy())
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
 
     if rank == 0:
         N = B * args.n_lig + pocket0["x"].shape[0]

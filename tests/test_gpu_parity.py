@@ -579,51 +579,54 @@ def test_bench_two_ranks_sharing_the_gpu():
     assert d["value"] > 0 and d["unit"] == "ligands/s" and d["cpu_baseline"] is None
 
 
-def test_bench_eight_ranks_config3_shape_equals_sequential_runs(tmp_path):
-    """BASELINE configs[3] as the driver launches it -- `python -m torch.distributed.run --nproc-per-node 8 bench.py --gpus 8`:
-    64 pockets per rank = 512 -- with the eight ranks sharing the one GPU of this box over gloo (RCCL refuses several
-    ranks per device; the one-rank RCCL path is tests/test_gpu_rccl.py).  The JSON line reports 8 ranks and the sample
-    offsets 0, 64, ..., 448; the gathered 512 x 23 rows are BITWISE those of eight sequential world-1 chains (one per
-    shard, same seed, offset = the shard's first global sample id)."""
+def test_bench_four_ranks_config3_per_rank_shape_equals_sequential_runs(tmp_path):
+    """The multi-rank path of bench.py as the driver launches it -- `python -m torch.distributed.run --nproc-per-node W
+    bench.py --gpus W` -- with BASELINE configs[3]'s 64 pockets per rank, W = 4 ranks sharing the one GPU of this box over
+    gloo (RCCL refuses several ranks per device; the one-rank RCCL path is tests/test_gpu_rccl.py).  Four ranks, not
+    configs[3]'s eight: this process, the launcher and the ranks all hold the device, and a shared GPU host admits at
+    most six such processes at once.  The JSON line reports 4 ranks and the sample offsets 0, 64, 128, 192; the gathered
+    256 x 23 rows are BITWISE those of four sequential world-1 chains (one per shard, same seed, offset = the shard's
+    first global sample id)."""
     import json
     import os
     import socket
     import subprocess
     import sys
     import bench
+    W, B = 4, 64
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
-    dump = str(tmp_path / "lig8.npz")
+    dump = str(tmp_path / "lig4.npz")
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     T = 2
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0",
-           "--timesteps", str(T), "--backend", "gloo", "--share-gpu", "--no-cpu-baseline", "--no-kernel-timing",
-           "--dump-ligands", dump]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(W), "--master-addr",
+           "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(W), "--steps", "1",
+           "--warmup", "0", "--timesteps", str(T), "--backend", "gloo", "--share-gpu", "--no-cpu-baseline",
+           "--no-kernel-timing", "--dump-ligands", dump]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 8 and d["rccl_ranks"] == 8 and d["scaling"] == "weak"
-    assert d["config"]["global_batch"] == 512 and d["config"]["batch_per_gpu"] == 64
-    assert d["rank_sample_offsets"] == [0, 64, 128, 192, 256, 320, 384, 448]
+    assert d["n_gpus"] == W and d["rccl_ranks"] == W and d["scaling"] == "weak"
+    assert d["config"]["global_batch"] == W * B and d["config"]["batch_per_gpu"] == B
+    assert d["rank_sample_offsets"] == [B * r for r in range(W)]
     z = np.load(dump)
-    assert z["all_lig"].shape == (512 * 23, 13) and z["all_mask"].shape == (512 * 23,)
-    assert np.array_equal(z["all_mask"], np.repeat(np.arange(512), 23))
-    # eight sequential world-1 chains in this process: bench.py's own protocol (chain(200): seed 200, anchored states)
+    assert z["all_lig"].shape == (W * B * 23, 13) and z["all_mask"].shape == (W * B * 23,)
+    assert np.array_equal(z["all_mask"], np.repeat(np.arange(W * B), 23))
+    # W sequential world-1 chains in this process: bench.py's own protocol (chain(200): seed 200, anchored states)
     d0 = dev()
     cfg, dd, model = bench.build_model("crossdock_fullatom_cond", d0)
     rows = []
-    for r in range(8):
-        model.seed(200, sample_offset=64 * r)
-        pocket = bench.load_pocket("fa", 64, d0)
-        ligand = bench.anchor_ligand(64, 23, cfg["atom_nf"], d0)
-        o_l, _, lmask, _ = model.inpaint(ligand, pocket, torch.ones(64 * 23, device=d0), resamplings=1, timesteps=T)
+    for r in range(W):
+        model.seed(200, sample_offset=B * r)
+        pocket = bench.load_pocket("fa", B, d0)
+        ligand = bench.anchor_ligand(B, 23, cfg["atom_nf"], d0)
+        o_l, _, lmask, _ = model.inpaint(ligand, pocket, torch.ones(B * 23, device=d0), resamplings=1, timesteps=T)
         rows.append(o_l.cpu())
     seq = torch.cat(rows).numpy()
     assert np.array_equal(seq, z["all_lig"])                                         # bitwise
@@ -656,12 +659,10 @@ def test_rows_spanning_many_tiles(arch, max_wg, granule, monkeypatch):
     row's edge segment spans 5+ wave tiles / 2+ workgroup tiles.  granule "16": every stage on the 16-edge-granule
     kernels (csrc/edge_wave16.h: a row then spans 10+ wave tiles; head slots per 16-edge tile).  granule "sk": every
     stage on the split-K kernels (csrc/edge_splitk.h, H = 256: a workgroup per 32-edge tile; with the grid capped at 8 / 16
-    workgroups every workgroup walks many items, both MLPs of the coordinate stage as separate populations)."""
+    workgroups every workgroup walks many items, both MLPs of the coordinate stage as separate populations).  The split-K
+    kernels serve hidden_nf 256 only: for the other architectures the engine ignores the mask, and the result must be
+    bitwise that of the same call without it."""
     import os
-    if granule == "sk" and not arch.startswith("crossdock"):
-        pytest.skip("split-K kernels: hidden_nf 256 only")
-    if granule != "sk" and arch.startswith("crossdock") and max_wg != 8:
-        pytest.skip("the H = 256 cases of the other variants: one is enough")
     if granule == "16":
         monkeypatch.setenv("DSBDD_GRANULE16", "0xFFFFFFFF")
     if granule == "sk":
@@ -678,6 +679,10 @@ def test_rows_spanning_many_tiles(arch, max_wg, granule, monkeypatch):
         e_l2, e_p2, _ = m.forward_async(xl, xp, t, ml, mp, edges=edges)
         assert torch.equal(e_l, e_l2) and torch.equal(e_p, e_p2)                            # each variant bitwise reproducible
         f_l, f_p = m(xl.to(dev()), xp.to(dev()), t.to(dev()), ml.to(dev()), mp.to(dev()))   # device-built edges
+        if granule == "sk" and cfg["hidden_nf"] != 256:
+            monkeypatch.delenv("DSBDD_SPLITK")
+            n_l, n_p, _ = make_dynamics(cfg, sd).forward_async(xl, xp, t, ml, mp, edges=edges)
+            assert torch.equal(e_l, n_l) and torch.equal(e_p, n_p)                          # the mask is ignored
     finally:
         del os.environ["DSBDD_EDGE_MAX_WG"]
     assert int(st.item()) == 0

@@ -723,3 +723,26 @@ def test_sum_except_batch_with_a_known_batch_size():
     assert torch.equal(D.sum_except_batch(x, idx), D.sum_except_batch(x, idx, 4))
     assert D.sum_except_batch(x, idx, 6).shape == (6,)       # trailing samples without nodes: zeros
     assert torch.equal(D.remove_mean_batch(x, idx), D.remove_mean_batch(x, idx, 4))
+
+
+def test_bench_dump_outputs_writes_every_array_and_caps_the_total_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: small outputs are written whole; over the budget every array keeps the same seeded rows
+    (a ligand row stays paired with its mask entry), the total stays within the budget and a second run writes the
+    same files."""
+    import bench
+    small = {"ligand": np.arange(12, dtype=np.float32).reshape(4, 3), "ligand_mask": np.arange(4, dtype=np.float64)}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    for k, v in small.items():
+        got = np.load(tmp_path / "small" / f"{k}.npy")
+        assert got.dtype == v.dtype and np.array_equal(got, v)
+    rows = 1000
+    big = {"ligand": np.random.RandomState(1).randn(rows, 13).astype(np.float32),
+           "ligand_mask": np.arange(rows, dtype=np.float64)}
+    budget = 16000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big, budget=budget)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in big}
+    assert 0 < sum(v.nbytes for v in got.values()) <= budget
+    assert np.array_equal(got["ligand"], big["ligand"][got["ligand_mask"].astype(np.int64)])
+    for k in big:
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy"))
