@@ -2,7 +2,7 @@
 """Benchmark of the DDPM sampling hot path on MI355X (contract: see the task
 description / DESIGN.md 6 Measurement).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" = one complete sampling chain over one batch of synthetic pockets on
 BASELINE.json configs[2] (crossdock_fullatom_cond, 64 pockets per GPU, 23 ligand
@@ -15,7 +15,7 @@ known ("anchored" states, `--states anchored`, the default): the same 501 EGNN c
 and fused updates as sampling, on the state distribution a TRAINED model's chain
 has (ligand inside the pocket) -- a free-running chain on random weights drifts out
 of the pocket and its calls get cheaper.  The metric's literal call,
-`ConditionalDDPM.sample_given_pocket` free-running, is timed in the same run as
+`ConditionalDDPM.sample_given_pocket` free-running, is timed by a --full run as
 `other_states`, with its own kernel timing and roofline block.
 
 For N > 1 either the driver launches one process per GPU with torch.distributed.run,
@@ -24,18 +24,28 @@ every rank runs its own 64 pockets (weak scaling, no data-path collective) and
 the finished ligands are gathered once per chain over RCCL.  value = ligands of
 all ranks / max-over-ranks wall time.
 
-The JSON line also carries
+A plain run does only what the headline needs: it sets up, runs the warm-up chains, times the
+--steps chains, writes --dump-outputs and prints the JSON line.  Its `roofline` block comes
+from those timed chains:
   roofline        : the dominant kernel (fused GCL edge stage, edge_wave_kernel<H, MODE_GCL>,
                     csrc/edge_wave.h) timed live with HIP events on its own stream;
                     algorithmic FLOPs (E_r (H^2 + (A+2) H) MAC per launch, E_r =
                     edges of the rows the launch evaluates) / duration vs the 157.3 TFLOP/s
                     fp32 matrix peak; the same over the whole call
+
+--full adds the legs that take runs of their own (each one's --no-* option skips it there);
+without it their keys are null:
+  other_states    : the other state model of the chain (with the default --states anchored:
+                    sample_given_pocket free-running), its own roofline block, and the same leg
+                    with every edge stage on the split-K kernels (`splitk_all`)
+  emulated        : the headline chain with the edge kernels' H x H layer emulated on the bf16
+                    matrix cores, its own roofline block
+  other_workloads : chains of configs[1] (C-alpha x 32), configs[4] on one GPU (joint RePaint
+                    x 64) and the heterogeneous-pocket batch (each with an emulated variant),
+                    and the training step at full-atom x 16 and C-alpha x 96
   cpu_baseline    : the reference's own modules (kind "reference", oracle/_ref, when the build
                     shipped them) or the CPU oracle (kind "port") timed on this host's cores on
-                    a bounded sample of the same workload
-  other_workloads : one chain each of configs[1] (C-alpha x 32), configs[4] on one GPU (joint
-                    RePaint x 64) and the heterogeneous-pocket batch, so that the driver's
-                    record holds them
+                    a bounded sample of the same workload, plus BASELINE configs[0] end to end
 
 --dump-outputs DIR writes what the last timed chain returned (ligand, ligand_mask, pocket,
 pocket_mask) as DIR/<name>.npy; the inputs are seeded, so two builds run with the same
@@ -461,7 +471,11 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="pockets per GPU")
     ap.add_argument("--timesteps", type=int, default=None, help="DDPM steps (default: the config's 500)")
     ap.add_argument("--n-lig", type=int, default=23)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline (other_states, emulated, other_workloads incl. the "
+                         "training steps, cpu_baseline incl. configs[0]); a plain run does only the warm-up and timed "
+                         "chains, --dump-outputs and the JSON line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=None, help="batch of the CPU baseline (default: the benchmark batch)")
     ap.add_argument("--cpu-steps", type=int, default=5, help="timed reverse steps of the CPU baseline (SURVEY.md 8d: k = 5)")
     ap.add_argument("--cpu-threads", type=int, default=32)
@@ -485,14 +499,14 @@ def main():
                          "'free' is sample_given_pocket free-running on the random weights, whose ligand drifts out "
                          "of the pocket (fewer ligand-pocket contacts, cheaper calls).  The other one is reported "
                          "as a secondary figure.")
-    ap.add_argument("--no-other-leg", action="store_true", help="skip the secondary figure (the other state model)")
+    ap.add_argument("--no-other-leg", action="store_true", help="--full: skip the secondary figure (the other state model)")
     ap.add_argument("--other-steps", type=int, default=5, help="timed chains of the secondary figure")
     ap.add_argument("--secondary-steps", type=int, default=3, help="timed chains of every `other_workloads` leg")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip the one-chain legs of the other single-GPU configurations (configs[1], configs[4] on one "
-                         "GPU, heterogeneous pockets) that ride along with the default run")
+                    help="--full: skip the legs of the other single-GPU configurations (configs[1], configs[4] on one "
+                         "GPU, heterogeneous pockets) and the training steps")
     ap.add_argument("--no-config0", action="store_true",
-                    help="skip the end-to-end CPU run of BASELINE configs[0] (C-alpha, 4 samples, 50 steps)")
+                    help="--full: skip the end-to-end CPU run of BASELINE configs[0] (C-alpha, 4 samples, 50 steps)")
     ap.add_argument("--granule16", default=None,
                     help="16-edge-granule edge kernels: 'auto' or a stage bit mask (DSBDD_OPT_GRANULE16); default: off")
     ap.add_argument("--splitk", default=None,
@@ -502,7 +516,7 @@ def main():
                     help="arithmetic of the main legs' H x H edge layers: 0 (default) exact fp32 MFMA; 6 / 9: fp32 emulated on "
                          "the bf16 matrix cores (DSBDD_OPT_EMU); `dtype` of the line then says so")
     ap.add_argument("--no-emulated-leg", action="store_true",
-                    help="skip the separate leg that runs the headline chain with the emulated-fp32 edge kernels")
+                    help="--full: skip the separate leg that runs the headline chain with the emulated-fp32 edge kernels")
     ap.add_argument("--emulated-steps", type=int, default=3, help="timed chains of the emulated leg")
     ap.add_argument("--dump-ligands", default=None,
                     help="rank 0 writes the gathered ligands of the LAST timed chain (all_lig [rows, 3 + atom_nf], all_mask = "
@@ -622,7 +636,7 @@ def main():
     # the metric's LITERAL call, sample_given_pocket free-running -- one warm-up, --other-steps timed chains, its own
     # kernel timing, level statistics and roofline block
     other = None
-    if not joint and world == 1 and not args.no_other_leg:
+    if args.full and not joint and world == 1 and not args.no_other_leg:
         o_states = "free" if args.states == "anchored" else "anchored"
         chain(300, o_states)
         sync()
@@ -662,7 +676,7 @@ def main():
     # separate leg: the headline chain with the edge kernels' H x H layer EMULATED on the bf16 matrix cores
     # (csrc/edge_wave.h "emulated path"; same inputs, same states, same seeds as the main leg's protocol)
     emulated = None
-    if world == 1 and not args.no_emulated_leg and not args.emulation and args.workload == "crossdock_fullatom_cond":
+    if args.full and world == 1 and not args.no_emulated_leg and not args.emulation and args.workload == "crossdock_fullatom_cond":
         model.edge_emulation = 6
         chain(400)
         sync()
@@ -790,7 +804,7 @@ def main():
             emulated["gate"] = ("opt-in (ddpm.edge_emulation = 6 / DSBDD_OPT_EMU); every -m gpu parity test holds at 1e-4 with it on, "
                                 "error vs float64 <= 2 x the exact path's: tests/test_gpu_emu.py, profiles/r5_emu_*")
         other_workloads = None
-        if world == 1 and not args.no_other_workloads and args.workload == "crossdock_fullatom_cond" and \
+        if args.full and world == 1 and not args.no_other_workloads and args.workload == "crossdock_fullatom_cond" and \
                 args.pockets == "same" and args.timesteps is None and args.batch is None:
             other_workloads = secondary_workloads(device, args.n_lig, steps=args.secondary_steps, emulated_legs=not args.no_emulated_leg)
             for wl_, b_ in (("crossdock_fullatom_cond", 16), ("crossdock_ca_cond", 96)):
@@ -800,7 +814,7 @@ def main():
                     other_workloads.append({"workload": "training step: " + wl_, "pockets": "same", "value": None,
                                             "error": repr(exc)[:300]})
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and not joint:
+        if args.full and world == 1 and not args.no_cpu_baseline and not joint:
             cpu = cpu_baseline(arch, key, args.cpu_batch or B, args.n_lig, n_calls, steps=args.cpu_steps,
                                max_threads=args.cpu_threads)
             if not args.no_config0:

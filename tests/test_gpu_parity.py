@@ -579,6 +579,33 @@ def test_bench_two_ranks_sharing_the_gpu():
     assert d["value"] > 0 and d["unit"] == "ligands/s" and d["cpu_baseline"] is None
 
 
+def test_bench_plain_run_times_the_headline_only_full_adds_the_legs():
+    """A plain `bench.py` run times the warm-up and --steps chains and nothing else: every leg that takes runs of its own
+    (other_states, emulated, cpu_baseline, other_workloads) is null.  `--full` runs them."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
+            "--timesteps", "3", "--batch", "4"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--other-steps", "1",
+                                                 "--emulated-steps", "1"])):
+        out = subprocess.run(base + extra, capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        js = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1, out.stdout
+        lines[name] = json.loads(js[0])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["value"] > 0 and d["steps"] == 1 and d["warmup"] == 1 and d["dtype"] == "f32"
+        assert d["roofline"]["timed_launches"] > 0
+    assert plain["other_states"] is None and plain["emulated"] is None
+    assert plain["cpu_baseline"] is None and plain["other_workloads"] is None
+    assert full["other_states"]["value"] > 0 and full["emulated"]["value"] > 0
+
+
 def test_bench_four_ranks_config3_per_rank_shape_equals_sequential_runs(tmp_path):
     """The multi-rank path of bench.py as the driver launches it -- `python -m torch.distributed.run --nproc-per-node W
     bench.py --gpus W` -- with BASELINE configs[3]'s 64 pockets per rank, W = 4 ranks sharing the one GPU of this box over
