@@ -120,6 +120,7 @@ SIGNATURES = {
                                     _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "dsbdd_bond_orders": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _P, C.c_float, C.c_float,
                                     C.c_float, _I32, _P]),
+    "dsbdd_pack_ligands": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _P, _P, _P, _I64, _I64, _I32, _P, _P, _P, _P, _P]),
     # training-step building blocks (struct arguments are passed by pointer: ctypes.byref / arrays)
     "dsbdd_train_scratch_bytes": (C.c_size_t, [_I32, _I64, _I64]),
     "dsbdd_train_wgrad_scratch_bytes": (C.c_size_t, [_I64, _I64, _I64]),

@@ -18,6 +18,7 @@
 #include "edge_splitk.h"
 #include "graph.h"
 #include "lig_head.h"
+#include "ligand_pack.h"
 #include "molecule.h"
 #include "node_chain.h"
 #include "node_linear.h"
@@ -1637,6 +1638,26 @@ int dsbdd_bond_orders(void* stream, const float* x, const int32_t* atom_type, co
   BondArgs a{x, atom_type, mol_off, bonds1, bonds2, bonds3, margin1, margin2, margin3, n_types, n_max,
              reinterpret_cast<signed char*>(order)};
   hipLaunchKernelGGL(bond_orders_kernel, dim3((unsigned)batch), dim3(64), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_pack_ligands(void* stream, const float* tmpl_x, const int32_t* tmpl_type, const int32_t* tmpl_ptr,
+                       int32_t n_tmpl, int64_t tmpl_rows, const int32_t* slot_tmpl, const int32_t* slot_size,
+                       const int32_t* slot_off, int64_t batch, int64_t n_rows, int32_t atom_nf, float* x,
+                       float* one_hot, int64_t* lig_fixed, int64_t* mask, int64_t* size) {
+  StreamDevice stream_device_(stream);
+  if (!tmpl_ptr || !slot_tmpl || !slot_size || !slot_off || !x || !one_hot || !lig_fixed || !mask || !size)
+    return fail(DSBDD_ERR_ARG, "null argument");
+  if ((tmpl_rows > 0 && (!tmpl_x || !tmpl_type)) || tmpl_rows < 0 || n_tmpl < 0 || atom_nf < 1)
+    return fail(DSBDD_ERR_ARG, "bad template set");
+  if (batch < 1 || n_rows < batch || n_rows > 0x7fffffff / 4)
+    return fail(DSBDD_ERR_ARG, "every slot needs at least one row (n_rows >= batch)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  PackArgs a{tmpl_x, tmpl_type, tmpl_ptr, slot_tmpl, slot_size, slot_off, n_tmpl, (int)tmpl_rows, (int)batch,
+             (int)n_rows, atom_nf, x, one_hot, reinterpret_cast<long long*>(lig_fixed),
+             reinterpret_cast<long long*>(mask), reinterpret_cast<long long*>(size)};
+  hipLaunchKernelGGL(pack_ligands_kernel, dim3((unsigned)((n_rows + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);
   HIP_TRY(hipGetLastError());
   return DSBDD_OK;
 }

@@ -13,6 +13,11 @@ or OpenBabel:
     pocket selection, size sampling, conditional sampling or joint inpainting,
     moving the result back to the pocket frame, molecule building.
 
+Ligands as input (`ligand_io.py`) carry the reference's two other workflows: `inpaint_ligands` /
+`inpaint_for_pockets` (inpaint.py: a fixed substructure, the rest designed) and `diversify_ligands` /
+`optimize_ligands` (optimize.py: partial noising + denoising of a population, selection by a caller-supplied
+objective).  Their packed batches are written by one HIP launch (`ligand_io.pack_ligands`).
+
 Molecules are built with the distance-table bonds of `molecules.py` (the
 reference's `use_openbabel=False` path); `sanitize` / `relax_iter` need RDKit and
 are refused here (convert with `Molecule.to_rdkit()` where RDKit exists).
@@ -26,12 +31,13 @@ import sys
 import numpy as np
 import torch
 
+from . import ligand_io
 from . import pocket as pocket_io
 from .chem_tables import dataset_info
 from .conditional_model import ConditionalDDPM, SimpleConditionalDDPM
 from .dynamics import EGNNDynamics
 from .en_diffusion import EnVariationalDiffusion, num_nodes_to_batch_mask, seg_mean
-from .molecules import build_molecules
+from .molecules import Molecule, build_molecules
 
 _DDPM_BY_MODE = {"joint": EnVariationalDiffusion,
                  "pocket_conditioning": ConditionalDDPM,
@@ -71,6 +77,9 @@ def load_checkpoint(path, trusted=False):
 
 class LigandGenerator:
     """Sampling-only counterpart of the reference's LightningModule."""
+
+    _RDKIT_REFUSAL = ("sanitize / relax_iter are RDKit operations; take the returned molecules' "
+                      ".to_rdkit() and apply the reference's process_molecule where RDKit is installed")
 
     def __init__(self, dataset, egnn_params, diffusion_params, mode, node_histogram,
                  pocket_representation="CA", virtual_nodes=False, device="cuda"):
@@ -188,9 +197,7 @@ class LigandGenerator:
                          sanitize=False, largest_frag=False, relax_iter=0, timesteps=None,
                          n_nodes_bias=0, n_nodes_min=0, **kwargs):
         if sanitize or relax_iter:
-            raise NotImplementedError(
-                "sanitize / relax_iter are RDKit operations; take the returned molecules' "
-                ".to_rdkit() and apply the reference's process_molecule where RDKit is installed")
+            raise NotImplementedError(self._RDKIT_REFUSAL)
         residues = self.select_pocket_residues(pdb_file, pocket_ids, ref_ligand)
         pocket = self.prepare_pocket(residues, repeats=n_samples)
         xh_lig, lig_mask = self.sample_for_pocket(pocket, n_samples, num_nodes_lig, timesteps,
@@ -290,6 +297,302 @@ class LigandGenerator:
             out.append(mols[o:o + n])
             o += n
         return out
+
+
+    # -- substructure inpainting (the reference's inpaint.py:63-189) ------------------------------------------
+    def _check_inpaint_model(self, center):
+        """ConditionalDDPM: both centring options.  Joint model: `inpaint` with every pocket node fixed, which has no
+        centring argument (the reference's script cannot run it at all: it passes `center=`).  The simple conditional
+        model has no pinned chain, as in `sample_for_pocket`."""
+        if center not in ("ligand", "pocket"):
+            raise ValueError("center must be 'ligand' or 'pocket'")
+        if type(self.ddpm) == EnVariationalDiffusion:
+            if center != "ligand":
+                raise ValueError("the joint model centres on the known nodes; only the default center='ligand' is accepted")
+        elif type(self.ddpm) != ConditionalDDPM:
+            raise NotImplementedError(f"inpainting front end: {type(self.ddpm).__name__} is not supported")
+
+    def prepare_substructure(self, pdb_file, ref_ligand, fix_atoms):
+        """The atoms to keep (inpaint.py:47-60) -> (xyz float32 [n,3], int32 class ids): the first molecule of every
+        SDF file of `fix_atoms`, concatenated, or the atoms of the PDB ligand `<chain>:<resi>` whose names are in
+        `fix_atoms`, in file order."""
+        fix_atoms = [fix_atoms] if isinstance(fix_atoms, str) else list(fix_atoms)
+        if not fix_atoms:
+            raise ValueError("fix_atoms is empty")
+        if str(fix_atoms[0]).endswith(".sdf"):
+            mols = [ligand_io.read_sdf_molecules(f)[0] for f in fix_atoms]
+            xyz = np.concatenate([m[0] for m in mols])
+            elements = sum((m[1] for m in mols), [])
+        else:
+            if str(ref_ligand).endswith(".sdf"):
+                raise ValueError("atom names need the ligand inside the PDB file (ref_ligand = <chain>:<resi>)")
+            residues = pocket_io.read_pdb_residues(pdb_file, hetero=True)
+            xyz, elements = ligand_io.ligand_atoms_from_pdb(residues, ref_ligand, fix_atoms)
+        return xyz, ligand_io.encode_elements(elements, self.lig_type_encoder)
+
+    def _inpaint_chain(self, pocket, ligand, lig_fixed, n, center, resamplings, timesteps, frames, jump_length):
+        """ddpm.inpaint on a packed batch + the move back into the pocket's frame (inpaint.py:143-170).
+        -> (xh_lig [rows, 3 + atom_nf], lig_mask); with frames > 1 the rows are the frames one after the other,
+        noisiest first, and the mask numbers the frames (utils.reverse_tensor, inpaint.py:152-162)."""
+        nd = self.x_dims
+        pocket_com_before = self.ddpm._seg_mean3(pocket["x"].float(), pocket["mask"], n)
+        if type(self.ddpm) == EnVariationalDiffusion:
+            pocket_fixed = torch.ones(len(pocket["mask"]), device=self.device)
+            xh_lig, xh_pocket, lig_mask, pocket_mask = self.ddpm.inpaint(
+                ligand, pocket, lig_fixed, pocket_fixed, resamplings=resamplings, jump_length=jump_length,
+                return_frames=frames, timesteps=timesteps)
+        else:
+            xh_lig, xh_pocket, lig_mask, pocket_mask = self.ddpm.inpaint(
+                ligand, pocket, lig_fixed, center=center, resamplings=resamplings, timesteps=timesteps,
+                return_frames=frames)
+        if frames > 1:
+            n = xh_lig.size(0)
+            xh_lig, xh_pocket = xh_lig.flip(0), xh_pocket.flip(0)
+            lig_mask = torch.arange(n, device=self.device).repeat_interleave(len(lig_mask))
+            pocket_mask = torch.arange(n, device=self.device).repeat_interleave(len(pocket_mask))
+            xh_lig = xh_lig.reshape(-1, xh_lig.size(2))
+            xh_pocket = xh_pocket.reshape(-1, xh_pocket.size(2))
+        pocket_com_after = self.ddpm._seg_mean3(xh_pocket[:, :nd], pocket_mask, n)
+        shift = pocket_com_before - pocket_com_after          # ([1,3] - [frames,3] for a trajectory)
+        xh_lig = xh_lig.clone()
+        xh_lig[:, :nd] += shift[lig_mask]
+        return xh_lig, lig_mask
+
+    @torch.no_grad()
+    def inpaint_ligands(self, pdb_file, n_samples, ref_ligand, fix_atoms, add_n_nodes=None, center="ligand",
+                        sanitize=False, largest_frag=False, relax_iter=0, timesteps=None, resamplings=1,
+                        save_traj=False, seed=None, jump_length=1):
+        """Design the rest of a ligand around a fixed substructure: the reference's `inpaint_ligand`
+        (inpaint.py:63-189) with its keywords.  `ref_ligand` (SDF path or `<chain>:<resi>`) defines the pocket;
+        `fix_atoms` is a list of SDF files or of atom names of the PDB ligand.  Sizes: drawn from p(n | pocket size) and
+        raised to the number of fixed atoms, or `n_fixed + add_n_nodes`.  `save_traj` (n_samples = 1) returns the
+        `timesteps` frames as molecules, noisiest first, without fragment selection.  `seed` keys the noise (and the
+        size draw); `jump_length` reaches the joint model only."""
+        if sanitize or relax_iter:
+            raise NotImplementedError(self._RDKIT_REFUSAL)
+        if save_traj and n_samples > 1:
+            raise NotImplementedError("Can only visualize trajectory with n_samples=1.")
+        self._check_inpaint_model(center)
+        timesteps = self.T if timesteps is None else timesteps
+        frames = timesteps if save_traj else 1
+        largest_frag = False if save_traj else largest_frag
+        residues = self.select_pocket_residues(pdb_file, ref_ligand=ref_ligand)
+        pocket = self.prepare_pocket(residues, repeats=n_samples)
+        x_fixed, t_fixed = self.prepare_substructure(pdb_file, ref_ligand, fix_atoms)
+        with torch.random.fork_rng(devices=[], enabled=seed is not None):
+            if seed is not None:
+                torch.manual_seed(int(seed))
+            sizes = ligand_io.inpaint_sizes(self.ddpm.size_distribution, pocket["size"].cpu(), len(x_fixed), add_n_nodes)
+        tmpl_x, tmpl_t, tmpl_sizes = ligand_io.upload_templates([(x_fixed, t_fixed)], self.device)
+        ligand, lig_fixed = ligand_io.pack_ligands(tmpl_x, tmpl_t, tmpl_sizes, [0] * n_samples, sizes.tolist(),
+                                                   self.atom_nf)
+        if seed is not None:
+            self.ddpm.seed(seed)
+        xh_lig, lig_mask = self._inpaint_chain(pocket, ligand, lig_fixed, n_samples, center, resamplings, timesteps,
+                                               frames, jump_length)
+        x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
+        return build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag,
+                               batch=frames if save_traj else n_samples)
+
+    @torch.no_grad()
+    def inpaint_for_pockets(self, jobs, timesteps=None, resamplings=1, center="ligand", largest_frag=False,
+                            seed=None, sample_ids=None, jump_length=1, cone_mode=2):
+        """Several design jobs in one batch: the packed-batch twin of `generate_for_pockets`.  `jobs`: list of
+        (residues, n_samples, substructure, add_n_nodes or sizes) -- `substructure` a `Molecule` or an (xyz, elements)
+        pair, the last entry None (sizes drawn), an int (atoms to add) or one ligand size per sample.  Returns one list
+        of molecules per job.  With keyed noise (`seed`, and `sample_ids` = one global id per slot of the packed
+        batch, default 0, 1, ...) a sample is the same molecule, bit for bit, in any packing that gives it the same
+        id.  For that the engine's per-batch choices must not follow the packing either: the forward cone, which the
+        model otherwise switches by the number of distinct pockets in the batch (en_diffusion.cone_mode; on and off
+        differ in rounding), is pinned to `cone_mode` (2 = on, 0 = off; None = the model's own per-batch rule) and the
+        automatic 16-row granule is switched off for the call, as the test-set driver does (testset.make_hip_sampler)."""
+        self._check_inpaint_model(center)
+        if cone_mode not in (None, 0, 2):
+            raise ValueError("cone_mode must be 2, 0 or None")
+        parts, templates, slot_tmpl, sizes, counts = [], [], [], [], []
+        base = 0
+        for residues, n, sub, extra in jobs:
+            pk = self.prepare_pocket(residues, repeats=n)
+            pk["mask"] = pk["mask"] + base
+            parts.append(pk)
+            (xyz, types), = ligand_io.as_templates([sub], self.lig_type_encoder)
+            if extra is None or isinstance(extra, (int, np.integer)):
+                n_lig = ligand_io.inpaint_sizes(self.ddpm.size_distribution, pk["size"].cpu(), len(xyz), extra)
+            else:
+                n_lig = torch.as_tensor(extra, dtype=torch.int64).cpu().reshape(-1)
+            assert n_lig.numel() == n
+            slot_tmpl += [len(templates)] * n
+            templates.append((xyz, types))
+            sizes.append(n_lig)
+            counts.append(n)
+            base += n
+        pocket = {k: torch.cat([p[k] for p in parts]) for k in ("x", "one_hot", "size", "mask")}
+        tmpl_x, tmpl_t, tmpl_sizes = ligand_io.upload_templates(templates, self.device)
+        ligand, lig_fixed = ligand_io.pack_ligands(tmpl_x, tmpl_t, tmpl_sizes, slot_tmpl, torch.cat(sizes).tolist(),
+                                                   self.atom_nf)
+        if seed is not None:
+            self.ddpm.seed(seed, sample_ids=sample_ids)
+        saved = self.ddpm.cone_mode, self.ddpm.edge_granule16
+        if cone_mode is not None:
+            self.ddpm.cone_mode = cone_mode
+            if saved[1] == "auto":
+                self.ddpm.edge_granule16 = 0
+        try:
+            xh_lig, lig_mask = self._inpaint_chain(pocket, ligand, lig_fixed, base, center, resamplings,
+                                                   self.T if timesteps is None else timesteps, 1, jump_length)
+        finally:
+            self.ddpm.cone_mode, self.ddpm.edge_granule16 = saved
+        x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
+        mols = build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=base)
+        out, o = [], 0
+        for n in counts:
+            out.append(mols[o:o + n])
+            o += n
+        return out
+
+    # -- diversification and the evolutionary loop (the reference's optimize.py) ------------------------------
+    def _diversify_chain(self, pocket, ligand, noising_steps):
+        """ddpm.diversify on a packed batch + the move back into the pocket's frame (optimize.py:116-128)."""
+        if not hasattr(self.ddpm, "diversify"):
+            raise NotImplementedError(f"{type(self.ddpm).__name__} has no diversify (pocket-conditioned models only)")
+        n = len(pocket["size"])
+        pocket_com_before = self.ddpm._seg_mean3(pocket["x"].float(), pocket["mask"], n)
+        out_lig, out_pocket, lig_mask, pocket_mask = self.ddpm.diversify(ligand, pocket, noising_steps=noising_steps)
+        pocket_com_after = self.ddpm._seg_mean3(out_pocket[:, :self.x_dims], pocket_mask, n)
+        out_lig = out_lig.clone()
+        out_lig[:, :self.x_dims] += (pocket_com_before - pocket_com_after)[lig_mask]
+        return out_lig, lig_mask
+
+    @torch.no_grad()
+    def diversify_ligands(self, pocket, molecules, noising_steps, largest_frag=False, seed=None):
+        """Partially noise and denoise ligands in their pocket: the reference's `diversify_ligands`
+        (optimize.py:92-147).  `pocket`: the dict of `prepare_pocket(residues, repeats=len(molecules))`; `molecules`:
+        a list of `Molecule` objects or (xyz, elements) pairs, or an SDF path -- one ligand per pocket replica.
+        Returns one molecule per input, in order."""
+        if not hasattr(self.ddpm, "diversify"):
+            raise NotImplementedError(f"{type(self.ddpm).__name__} has no diversify (pocket-conditioned models only)")
+        templates = ligand_io.as_templates(molecules, self.lig_type_encoder)
+        n = len(pocket["size"])
+        if len(templates) != n:
+            raise ValueError(f"{len(templates)} ligands for {n} pocket replicas (one ligand per replica)")
+        tmpl_x, tmpl_t, tmpl_sizes = ligand_io.upload_templates(templates, self.device)
+        ligand, _ = ligand_io.pack_ligands(tmpl_x, tmpl_t, tmpl_sizes, list(range(n)), tmpl_sizes, self.atom_nf)
+        if seed is not None:
+            self.ddpm.seed(seed)
+        xh_lig, lig_mask = self._diversify_chain(pocket, ligand, noising_steps)
+        x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
+        return build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=n)
+
+    def reference_ligand(self, pdb_file, ref_ligand):
+        """(xyz, element symbols) of the ligand that defines the pocket: first record of an SDF file, or the group
+        `<chain>:<resi>` of the PDB file."""
+        if str(ref_ligand).endswith(".sdf"):
+            return ligand_io.read_sdf_molecules(ref_ligand)[0]
+        return ligand_io.ligand_atoms_from_pdb(pocket_io.read_pdb_residues(pdb_file, hetero=True), ref_ligand)
+
+    def _population_step(self, pocket, reference, noising_steps, largest_frag, seed):
+        """`diversify(parent_ids, generation)` of `evolve_population` on the HIP path.  The previous generation stays
+        on the device as it came out of the chain: its coordinates, its atom classes (argmax on the device) and the
+        slot sizes the host already knows ARE the template set of the next `pack_ligands` call, and a slot's template
+        id is its parent's slot -- no coordinate crosses the host between generations.  That holds while every selected
+        parent is its whole slot.  With `largest_frag=True`, or when virtual atoms were dropped, a parent can have
+        fewer atoms than its slot: such a generation takes its parents from the host copies (the `Molecule` objects
+        that went to the objective) and uploads them; `self.optimize_stats['host_template_generations']` lists the
+        generations that did (generation 0, the reference ligand, always does)."""
+        n = len(pocket["size"])
+        (x0, t0), = ligand_io.as_templates([reference], self.lig_type_encoder)
+        state = {"mols": [Molecule(x0, list(reference[1]))], "sizes": [len(t0)], "dev": None}
+        self.optimize_stats = {"host_template_generations": []}
+
+        def diversify(parent_ids, generation):
+            assert len(parent_ids) == n
+            used = sorted(set(parent_ids))
+            whole = state["dev"] is not None and all(state["mols"][i].num_atoms == state["sizes"][i] for i in used)
+            if whole:
+                tmpl_x, tmpl_t = state["dev"]
+                tmpl_sizes, slot_tmpl = state["sizes"], list(parent_ids)
+            else:
+                tmpl_x, tmpl_t, tmpl_sizes = ligand_io.upload_templates(
+                    ligand_io.as_templates([state["mols"][i] for i in used], self.lig_type_encoder), self.device)
+                new_id = {i: k for k, i in enumerate(used)}
+                slot_tmpl = [new_id[i] for i in parent_ids]
+                self.optimize_stats["host_template_generations"].append(generation)
+            slot_sizes = [tmpl_sizes[t] for t in slot_tmpl]
+            ligand, _ = ligand_io.pack_ligands(tmpl_x, tmpl_t, tmpl_sizes, slot_tmpl, slot_sizes, self.atom_nf)
+            self.ddpm.seed((int(seed) << 20) + generation)
+            xh_lig, lig_mask = self._diversify_chain(pocket, ligand, noising_steps)
+            x, atom_type, kept_mask = self._drop_virtual(xh_lig, lig_mask)
+            mols = build_molecules(x, atom_type, kept_mask, self.dataset_info, largest_frag=largest_frag, batch=n)
+            state.update(mols=mols, sizes=slot_sizes,
+                         dev=(xh_lig[:, :self.x_dims].contiguous(), xh_lig[:, self.x_dims:].argmax(1).to(torch.int32)))
+            return [m if m.num_atoms > 0 else None for m in mols]
+
+        return diversify
+
+    @torch.no_grad()
+    def optimize_ligands(self, pdb_file, ref_ligand, objective, population_size=100, evolution_steps=10, top_k=7,
+                         noising_steps=100, largest_frag=False, seed=0, diversify=None):
+        """The evolutionary loop of the reference's optimize.py (:198-246) around `diversify`: generation 0 is the
+        reference ligand repeated `population_size` times; every later generation takes the `top_k` molecules of the
+        previous one by `objective`, each `population_size // top_k` times, and fills the remainder by a SEEDED draw
+        among them (the reference draws unseeded).  `objective` is any callable on a `Molecule`, larger = better; QED
+        and SA need RDKit and are not provided -- where it is installed pass e.g. `lambda m: qed(m.to_rdkit())`.
+        Molecules that come back empty do not enter the next generation.  Returns (molecules of the last generation,
+        history): history is a list of {'generation', 'index', 'score', 'fate'} records, fate 'initial' (the
+        reference), 'survived' (selected as a parent), 'purged', 'rejected' (no molecule) or 'final' (last generation).
+
+        Parents stay on the device between generations when each is its whole batch slot; otherwise
+        (`largest_frag=True`, dropped virtual atoms) that generation's parents are taken from their host copies --
+        see `_population_step`.  `diversify(parent_ids, generation) -> list of Molecule | None`, one per slot, replaces
+        the sampling step (tests, other samplers)."""
+        xyz, elements = self.reference_ligand(pdb_file, ref_ligand)
+        if diversify is None:
+            residues = self.select_pocket_residues(pdb_file, ref_ligand=ref_ligand)
+            pocket = self.prepare_pocket(residues, repeats=population_size)
+            diversify = self._population_step(pocket, (xyz, elements), noising_steps, largest_frag, seed)
+        return evolve_population(Molecule(np.asarray(xyz, np.float32), list(elements)), objective, diversify,
+                                 population_size, evolution_steps, top_k, seed)
+
+
+def evolve_population(initial, objective, diversify, population_size, evolution_steps, top_k, seed=0):
+    """Selection loop of optimize.py:198-246 on the host; `diversify(parent_ids, generation)` produces generation
+    `generation + 1` from the molecules of the previous one addressed by index (generation 0: index 0 = `initial`).
+    -> (molecules of the last generation, history records)."""
+    import random
+    if not 1 <= top_k <= population_size:
+        raise ValueError(f"top_k = {top_k} must lie in [1, population_size = {population_size}]")
+    if evolution_steps < 1:
+        raise ValueError("evolution_steps must be at least 1")
+    rng = random.Random(seed)
+    records = [dict(generation=0, index=0, score=objective(initial), fate="initial")]
+    history = list(records)
+    prev = [initial]
+    for generation in range(evolution_steps):
+        if generation == 0:
+            parent_ids = [0] * population_size
+        else:
+            alive = [i for i, m in enumerate(prev) if m is not None]
+            if not alive:
+                raise RuntimeError(f"generation {generation} has no surviving molecule: every sample came back empty "
+                                   "or was rejected, nothing to select parents from")
+            top = sorted(alive, key=lambda i: -records[i]["score"])[:top_k]        # stable: ties keep slot order
+            for i in top:
+                records[i]["fate"] = "survived"
+            parent_ids = top * (population_size // top_k)
+            pool = list(parent_ids) or list(top)
+            parent_ids += [rng.choice(pool) for _ in range(population_size - len(parent_ids))]
+        prev = list(diversify(parent_ids, generation))
+        if len(prev) != population_size:
+            raise RuntimeError(f"diversify returned {len(prev)} molecules for a population of {population_size}")
+        records = [dict(generation=generation + 1, index=i, score=None if m is None else objective(m),
+                        fate="rejected" if m is None else "purged") for i, m in enumerate(prev)]
+        history += records
+    final = []
+    for r, m in zip(records, prev):
+        if m is not None:
+            r["fate"] = "final"
+            final.append(m)
+    return final, history
 
 
 def main(argv=None):

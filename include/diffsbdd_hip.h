@@ -555,6 +555,27 @@ int dsbdd_bond_orders(void* stream, const float* x, const int32_t* atom_type,
                       float margin1, float margin2, float margin3, int32_t n_max,
                       int8_t* order);
 
+/* ---- ligands as input: the packed batch of the design front ends -------------*/
+/* One launch that writes the ligand batch of substructure inpainting and of
+ * diversification (inpaint.py:114-141, optimize.py:39-62 of the reference build
+ * it on the host).  Templates: tmpl_x [tmpl_rows][3], tmpl_type [tmpl_rows]
+ * class ids, tmpl_ptr [n_tmpl+1] first row of every template -- device memory,
+ * e.g. the output of an earlier chain.  Slots: slot_tmpl [batch] template id,
+ * slot_size [batch] rows of the slot (>= rows of its template, >= 1), slot_off
+ * [batch+1] first output row (exclusive scan of slot_size; n_rows = the total) --
+ * device memory as well, known to the host, which uploads them as one buffer.
+ * Outputs: x [n_rows][3] and one_hot [n_rows][atom_nf] hold the template in the
+ * first rows of every slot and zeros after, lig_fixed [n_rows] is 1 on the
+ * template rows, mask [n_rows] the slot id, size [batch] = slot_size (int64).
+ * Launch geometry depends on n_rows only; no host synchronisation.  Indices read
+ * from device memory are range-checked: a row without a valid source is empty. */
+int dsbdd_pack_ligands(void* stream, const float* tmpl_x, const int32_t* tmpl_type,
+                       const int32_t* tmpl_ptr, int32_t n_tmpl, int64_t tmpl_rows,
+                       const int32_t* slot_tmpl, const int32_t* slot_size,
+                       const int32_t* slot_off, int64_t batch, int64_t n_rows,
+                       int32_t atom_nf, float* x, float* one_hot, int64_t* lig_fixed,
+                       int64_t* mask, int64_t* size);
+
 #ifdef __cplusplus
 }
 #endif
