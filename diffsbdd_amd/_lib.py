@@ -71,6 +71,11 @@ class TrainMlpGrad(C.Structure):
                 ("gd0", C.c_void_p)]
 
 
+class OptimCfg(C.Structure):
+    """struct dsbdd_optim_cfg"""
+    _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")] + [("clip_grad", C.c_int32)]
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 _I32 = C.c_int32
@@ -152,6 +157,18 @@ SIGNATURES = {
     "dsbdd_loss_cond_pre": (C.c_int, [_P, C.POINTER(LossCfg)] + [_P] * 17),
     "dsbdd_loss_cond_post": (C.c_int, [_P, C.POINTER(LossCfg)] + [_P] * 8),
     "dsbdd_loss_cond_post_backward": (C.c_int, [_P, C.POINTER(LossCfg)] + [_P] * 9),
+    # the optimiser step and the auxiliary loss of the native training loop (csrc/optim.h, csrc/lj_loss.h)
+    "dsbdd_optim_create": (C.c_int, [C.POINTER(OptimCfg), _I32, C.POINTER(_I64), C.POINTER(_P)]),
+    "dsbdd_optim_destroy": (None, [_P]),
+    "dsbdd_optim_state_elems": (_I64, [_P]),
+    "dsbdd_optim_state_offset": (_I64, [_P, _I32]),
+    "dsbdd_optim_workspace_bytes": (C.c_size_t, [_P]),
+    "dsbdd_optim_bind": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t]),
+    "dsbdd_optim_set_params": (C.c_int, [_P, _P, C.POINTER(_P)]),
+    "dsbdd_optim_step": (C.c_int, [_P, _P, C.POINTER(_P), C.POINTER(_I32), C.c_double]),
+    "dsbdd_optim_state_read": (C.c_int, [_P, _P, C.POINTER(C.c_double), _I32]),
+    "dsbdd_optim_state_write": (C.c_int, [_P, _P, C.POINTER(C.c_double), _I32, C.c_double, C.c_double]),
+    "dsbdd_lj_potential": (C.c_int, [_P, _P, _I32, _I32, _P, _I64, _I64, _P, C.c_double, _I32, _P, _P, _P]),
 }
 
 _lib = None

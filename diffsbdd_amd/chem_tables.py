@@ -29,7 +29,21 @@ P P 221 0 0     | P F 156 0 0
 I I 266 0 0     | I F 187 0 0
 F F 142 0 0
 """
-MARGINS_PM = (3.0, 2.0, 1.0)   # margin1, margin2, margin3 (constants.py:17)
+# Lennard-Jones radius r_m in pm per unordered pair (the reference's `lennard_jones_rm`, constants.py:135-145 and its
+# per-dataset copies); a pair that is not listed (the rest class 'others') is 0
+_LJ_RM_PM = """
+C C 120 | C N 116 | C O 113 | C S 160 | C B 133 | C Br 194 | C Cl 177 | C P 184 | C I 214 | C F 135
+N N 110 | N O 121 | N S 168 | N B 127 | N Br 214 | N Cl 175 | N P 177 | N I 222 | N F 136
+O O 121 | O S 151 | O B 126 | O Br 172 | O Cl 164 | O P 150 | O I 194 | O F 142
+S S 204 | S B 167 | S Br 225 | S Cl 207 | S P 186 | S I 234 | S F 158
+B B 146 | B Br 182 | B Cl 175 | B P 167 | B I 198 | B F 126
+Br Br 228 | Br Cl 214 | Br P 222 | Br I 234 | Br F 178
+Cl Cl 199 | Cl P 203 | Cl I 218 | Cl F 166
+P P 221 | P I 219 | P F 156
+I I 266 | I F 187
+F F 142
+"""
+MARGINS_PM = (3.0, 2.0, 1.0)  # margin1, margin2, margin3 (constants.py:17)
 
 # highest number of covalent bonds (sum of bond orders) an element takes: the reference's `allowed_bonds`
 # (constants.py:19-22; where it lists alternatives -- P, Hg, Bi -- the largest one)
@@ -47,9 +61,9 @@ _DATASETS = {
 }
 
 
-def _pair_table():
+def _pair_table(text=_PAIR_PM):
     out = {}
-    for item in _PAIR_PM.replace("\n", "|").split("|"):
+    for item in text.replace("\n", "|").split("|"):
         tok = item.split()
         if not tok:
             continue
@@ -59,6 +73,21 @@ def _pair_table():
 
 
 _PAIRS = _pair_table()
+_LJ_PAIRS = _pair_table(_LJ_RM_PM)
+
+
+def lennard_jones_rm(decoder):
+    """Dense [A][A] float64 matrix of Lennard-Jones radii (pm) for an atom decoder (or a dataset name)."""
+    if isinstance(decoder, str):
+        decoder = _DATASETS[decoder][0]
+    n = len(decoder)
+    m = np.zeros((n, n), dtype=np.float64)
+    for i, a in enumerate(decoder):
+        for j, b in enumerate(decoder):
+            v = _LJ_PAIRS.get(frozenset((a, b)))
+            if v is not None:
+                m[i, j] = v[0]
+    return m
 
 
 def bond_matrices(decoder):

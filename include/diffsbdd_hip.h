@@ -540,6 +540,46 @@ int dsbdd_loss_cond_post_backward(void* stream, const dsbdd_loss_cfg* cfg, const
                                   const int64_t* lig_mask, const float* per_sample, const float* g_err, const float* g_l0x,
                                   const float* g_hat, float* d_net);
 
+/* ---- the optimiser step of the native training loop (csrc/optim.h) --------------------------------------------------------
+ * One step = configure_gradient_clipping (lightning_modules.py:874-899) + torch.optim.AdamW(amsgrad=True).step() of the
+ * reference in two launches and without a device-to-host copy: per-chunk sums of g^2 in a fixed order; then every
+ * workgroup derives the same global norm, threshold 1.5 mean + 2 std (population) of the last 50 norms and
+ * clip_coef = min(1, max_norm / (norm + 1e-6)), and updates p, exp_avg, exp_avg_sq, max_exp_avg_sq with the gradient scaled
+ * as it is read (the caller's gradient tensors are NOT scaled).  The queue lives on the device, double-buffered by step
+ * parity, and starts with the single entry 3000.
+ *   _create: host only; numel [n_tensors].  The optimiser state is three flat float buffers of _state_elems() elements in
+ *     which tensor i starts at _state_offset(i) (a multiple of 4); the caller owns them (zero-initialised) and a workspace
+ *     of _workspace_bytes(); _bind uploads the tables and resets the queue; _set_params uploads the parameter pointers
+ *     (again whenever one changes).  _bind, _set_params, _state_read and _state_write synchronise the stream; _step does not.
+ *   _step: grads [n_tensors] device pointers, NULL = no gradient at this step: that tensor is skipped entirely (no decay,
+ *     no state update); steps [n_tensors] = the tensor's own step count INCLUDING this step (>= 1; ignored where grads is NULL).
+ *   _state_read: out [64] doubles: [0] entries in the queue, [1 .. 50] the entries newest first, [51] clipped steps,
+ *     [52] last norm, [53] last threshold, [54] steps, [55] last clip coefficient.  _state_write sets the queue (newest
+ *     first) and the two counters. */
+typedef struct {
+  double lr, beta1, beta2, eps, weight_decay;
+  int32_t clip_grad;      /* 0: plain AdamW, one launch */
+} dsbdd_optim_cfg;
+typedef struct dsbdd_optim dsbdd_optim;
+int dsbdd_optim_create(const dsbdd_optim_cfg* cfg, int32_t n_tensors, const int64_t* numel, dsbdd_optim** out);
+void dsbdd_optim_destroy(dsbdd_optim* o);
+int64_t dsbdd_optim_state_elems(const dsbdd_optim* o);
+int64_t dsbdd_optim_state_offset(const dsbdd_optim* o, int32_t tensor);
+size_t dsbdd_optim_workspace_bytes(const dsbdd_optim* o);
+int dsbdd_optim_bind(dsbdd_optim* o, void* stream, float* m, float* v, float* vmax, void* ws, size_t ws_bytes);
+int dsbdd_optim_set_params(dsbdd_optim* o, void* stream, float* const* params);
+int dsbdd_optim_step(dsbdd_optim* o, void* stream, const float* const* grads, const int32_t* steps, double lr);
+int dsbdd_optim_state_read(dsbdd_optim* o, void* stream, double* out, int32_t capacity);
+int dsbdd_optim_state_write(dsbdd_optim* o, void* stream, const double* items, int32_t n_items, double clips, double steps);
+
+/* ---- the auxiliary Lennard-Jones term of the training loss (csrc/lj_loss.h; lightning_modules.py:304-331) ----------------
+ * xh [n][ld]: coordinates in columns 0-2, n_types feature columns from column 3 (type = argmax); mask [n] int64 sorted
+ * ascending in [0, batch); sigma [n_types][n_types] doubles = 2^(-1/6) rm / 100 / norm_values[0].  One launch, one workgroup per
+ * sample: u [batch] = sum over ordered pairs of min(4 ((sigma/r)^12 - (sigma/r)^6), clamp), dx [n][3] = d u[sample] / d x
+ * (a clamped pair contributes none).  type_scratch [n] int32.  Rows whose mask is outside [0, batch) are not written. */
+int dsbdd_lj_potential(void* stream, const float* xh, int32_t ld, int32_t n_types, const int64_t* mask, int64_t n, int64_t batch,
+                       const double* sigma, double clamp, int32_t has_clamp, int32_t* type_scratch, float* u, float* dx);
+
 /* ---- post-processing of a finished batch ------------------*/
 /* Distance-based bond orders of a batch of molecules: replaces
  * get_bond_order_batch + the (X, A, E) step of make_mol_edm

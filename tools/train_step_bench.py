@@ -57,7 +57,17 @@ def main():
     ap.add_argument("--bare", action="store_true",
                     help="free-running loop only: dynamics forward + a one-kernel loss + backward + optimiser, inputs prepared "
                          "beforehand -- the step without the reference's loss glue (what the ~340 small torch launches cost)")
+    ap.add_argument("--clip", choices=("none", "reference", "hip"), default="none",
+                    help="gradient clipping as every shipped config sets it (clip_grad: True): reference = the host-side queue with "
+                         "its read-backs (lightning_modules.py:874-899), hip = inside ClippedAdamW (needs --optimizer hip)")
+    ap.add_argument("--optimizer", choices=("torch", "hip"), default="torch",
+                    help="torch.optim.AdamW(amsgrad=True), or diffsbdd_amd.optim.ClippedAdamW (csrc/optim.h)")
     a = ap.parse_args()
+    if a.clip == "hip" and a.optimizer != "hip":
+        ap.error("--clip hip is part of --optimizer hip")
+    if a.optimizer == "hip" and (a.clip == "reference" or a.fused_adam):
+        ap.error("--optimizer hip takes --clip none or --clip hip")
+    from diffsbdd_amd.optim import ClippedAdamW, ReferenceClipper
     dev = torch.device("cuda:0")
     key = "ca" if "ca_" in a.workload else "fa"
     B = a.batch or (96 if key == "ca" else 16)
@@ -67,8 +77,13 @@ def main():
         os.environ["DSBDD_TRAIN"] = path
         model, cfg, dd = build(a.workload, dev)
         model.train(True)
-        opt = torch.optim.AdamW(model.parameters(), lr=1e-4, amsgrad=True, weight_decay=1e-12,
-                                **({"fused": True} if a.fused_adam else {}))
+        params = list(model.parameters())
+        if a.optimizer == "hip":
+            opt = ClippedAdamW(params, lr=1e-4, weight_decay=1e-12, clip_grad=a.clip == "hip")
+        else:
+            opt = torch.optim.AdamW(params, lr=1e-4, amsgrad=True, weight_decay=1e-12,
+                                    **({"fused": True} if a.fused_adam else {}))
+        clipper = ReferenceClipper() if a.clip == "reference" else None
         tf = tb = to = 0.0
         n_nodes = n_edges = 0
         for it in range(a.warmup + a.steps):
@@ -83,6 +98,8 @@ def main():
             loss.backward()
             torch.cuda.synchronize()
             t2 = time.perf_counter()
+            if clipper is not None:
+                clipper.clip(params)
             opt.step()
             torch.cuda.synchronize()
             t3 = time.perf_counter()
@@ -96,6 +113,8 @@ def main():
         for pocket, ligand in batches:
             opt.zero_grad(set_to_none=True)
             loss_of(model(ligand, pocket)).backward()
+            if clipper is not None:
+                clipper.clip(params)
             opt.step()
         torch.cuda.synchronize()
         t_free = (time.perf_counter() - t0) / a.steps
@@ -113,6 +132,8 @@ def main():
                     opt.zero_grad(set_to_none=True)
                     eps, _ = model.dynamics(zl, zp, tt, lm, pm)
                     (eps ** 2).mean().backward()
+                    if clipper is not None:
+                        clipper.clip(params)
                     opt.step()
                 torch.cuda.synchronize()
             print(f"bare step ({path}): {(time.perf_counter() - t0) / a.steps * 1e3:.2f} ms", flush=True)
@@ -121,7 +142,8 @@ def main():
             e = model.dynamics.get_edges(ligand["mask"], pocket["mask"], ligand["x"], pocket["x"])
         n_edges = int(e.shape[1])
         k = 1e3 / a.steps
-        print(f"| {a.workload} | {B} | {path} | {(tf + tb + to) * k:.2f} | {tf * k:.2f} | {tb * k:.2f} | {to * k:.2f} | "
+        label = path if (a.clip, a.optimizer) == ("none", "torch") else f"{path}, clip {a.clip}, optimizer {a.optimizer}"
+        print(f"| {a.workload} | {B} | {label} | {(tf + tb + to) * k:.2f} | {tf * k:.2f} | {tb * k:.2f} | {to * k:.2f} | "
               f"{n_nodes} | {n_edges} | {t_free * 1e3:.2f} |", flush=True)
         del model, opt
         torch.cuda.empty_cache()
