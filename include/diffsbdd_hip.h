@@ -356,7 +356,19 @@ int dsbdd_joint_repaint_update(void* stream, float* z_lig, float* z_pocket, floa
  * that a chain's noise does not depend on how samples are sharded over GPUs or packed
  * into batches.  out [n_rows][n_cols]; global sample id of row i =
  * sample_ids[mask[i]] when sample_ids != NULL (int64 [batch], device), else
- * mask[i] + sample_offset. */
+ * mask[i] + sample_offset.
+ *
+ * Key domain.  With gs the global sample id and e = row_in_sample * n_cols + col (32 bit), a value is Box-Muller
+ * (u1 = ((w0 >> 8) + 1) / 2^24 in (0, 1], u2 = (w1 >> 8) / 2^24 in [0, 1), |z| <= sqrt(48 ln 2)) on words 0 and 1 of
+ *   Philox4x32-10(counter = { gs_lo, e, draw_lo, draw_hi ^ stream_id * 0x9E3779B1 ^ gs_hi }, key = { seed_lo, seed_hi }).
+ * Distinct (seed, draw_index, stream_id, sample id, element) give distinct (counter, key) pairs, hence unrelated
+ * streams, as long as draw_index < 2^32 and the sample id < 2^32: there the last counter word is stream_id * 0x9E3779B1
+ * alone (an odd multiplier: a bijection of the stream ids) and the other words are the inputs verbatim.  Outside that
+ * domain the three terms of the last word alias: (draw_index + 2^32, gs) and (draw_index, gs + 2^32) are the SAME
+ * stream, and a stream_id can cancel a high half likewise.  Every caller in this project stays inside the domain (draw
+ * indices count the draws of one chain, sample ids the molecules of one run); a caller that does not must not rely
+ * on independence.  oracle/keyed_noise.py restates the generator on the host; tests/test_keyed_noise.py pins both
+ * statements. */
 int dsbdd_randn_keyed(void* stream, float* out, const int64_t* mask, int64_t n_rows,
                       int32_t n_cols, int64_t batch, int64_t sample_offset,
                       const int64_t* sample_ids, uint64_t seed, uint64_t draw_index,
