@@ -1,0 +1,221 @@
+// Thin C-ABI wrappers of the stand-alone kernels (included by engine.hip): DDPM steps (ddpm.h), keyed noise, node GEMM,
+// bond orders (molecule.h), ligand packing (ligand_pack.h), the radius graph (graph.h).
+#pragma once
+
+extern "C" {
+
+int dsbdd_cond_reverse_update(void* stream, float* z_lig, float* xh_pocket, const float* eps_lig,
+                              const float* noise, const int64_t* mask_lig, const int64_t* mask_pocket,
+                              int64_t n_lig, int64_t n_pocket, int64_t batch, int32_t atom_nf,
+                              int32_t residue_nf, float alpha_ts, float c_eps, float sigma, int32_t remove_com) {
+  StreamDevice stream_device_(stream);
+  if (!z_lig || !xh_pocket || !eps_lig || !noise || !mask_lig || !mask_pocket || batch < 1)
+    return fail(DSBDD_ERR_ARG, "bad argument");
+  hipLaunchKernelGGL(cond_update_kernel, dim3((int)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                     z_lig, xh_pocket, eps_lig, noise, mask_lig, (int)n_lig, mask_pocket, (int)n_pocket,
+                     3 + atom_nf, 3 + residue_nf, alpha_ts, c_eps, sigma, remove_com);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_joint_reverse_update(void* stream, float* z_lig, float* z_pocket, const float* eps_lig,
+                               const float* eps_pocket, const float* noise_lig, const float* noise_pocket,
+                               const int64_t* mask_lig, const int64_t* mask_pocket, int64_t n_lig,
+                               int64_t n_pocket, int64_t batch, int32_t atom_nf, int32_t residue_nf,
+                               float alpha_ts, float c_eps, float sigma, int32_t center_noise) {
+  StreamDevice stream_device_(stream);
+  if (!z_lig || !z_pocket || !eps_lig || !eps_pocket || !noise_lig || !noise_pocket || !mask_lig ||
+      !mask_pocket || batch < 1)
+    return fail(DSBDD_ERR_ARG, "bad argument");
+  hipLaunchKernelGGL(joint_update_kernel, dim3((int)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                     z_lig, z_pocket, eps_lig, eps_pocket, noise_lig, noise_pocket, mask_lig, (int)n_lig,
+                     mask_pocket, (int)n_pocket, 3 + atom_nf, 3 + residue_nf, alpha_ts, c_eps, sigma, center_noise);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_segment_mean3(void* stream, const float* x, int32_t ld, const int64_t* mask, int64_t n_rows,
+                        int64_t batch, float* out) {
+  StreamDevice stream_device_(stream);
+  if (!x || !mask || !out || batch < 1 || ld < 3 || n_rows < 0) return fail(DSBDD_ERR_ARG, "bad argument");
+  hipLaunchKernelGGL(segment_mean3_kernel, dim3((int)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                     x, ld, mask, (int)n_rows, out);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_cond_affine_noise(void* stream, float* z_lig, float* xh_pocket, const float* noise,
+                            const int64_t* mask_lig, const int64_t* mask_pocket, int64_t n_lig,
+                            int64_t n_pocket, int64_t batch, int32_t atom_nf, int32_t residue_nf, float a,
+                            float sigma, int32_t remove_com) {
+  StreamDevice stream_device_(stream);
+  if (!z_lig || !xh_pocket || !noise || !mask_lig || !mask_pocket || batch < 1)
+    return fail(DSBDD_ERR_ARG, "bad argument");
+  hipLaunchKernelGGL(cond_affine_noise_kernel, dim3((int)batch), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), z_lig, xh_pocket, noise, mask_lig, (int)n_lig, mask_pocket,
+                     (int)n_pocket, 3 + atom_nf, 3 + residue_nf, a, sigma, remove_com);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_joint_affine_noise(void* stream, float* z_lig, float* z_pocket, const float* noise_lig,
+                             const float* noise_pocket, const int64_t* mask_lig, const int64_t* mask_pocket,
+                             int64_t n_lig, int64_t n_pocket, int64_t batch, int32_t atom_nf,
+                             int32_t residue_nf, float a, float sigma, int32_t center_noise,
+                             int32_t remove_com) {
+  StreamDevice stream_device_(stream);
+  if (!z_lig || !z_pocket || !noise_lig || !noise_pocket || !mask_lig || !mask_pocket || batch < 1)
+    return fail(DSBDD_ERR_ARG, "bad argument");
+  hipLaunchKernelGGL(joint_affine_noise_kernel, dim3((int)batch), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), z_lig, z_pocket, noise_lig, noise_pocket, mask_lig,
+                     (int)n_lig, mask_pocket, (int)n_pocket, 3 + atom_nf, 3 + residue_nf, a, sigma, center_noise,
+                     remove_com);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_cond_repaint_update(void* stream, float* z_lig, float* xh_pocket, float* scratch_lig,
+                              const float* xh0_lig, const float* com_pocket0, const float* fixed,
+                              const float* noise_known, const float* noise_resample, const int64_t* mask_lig,
+                              const int64_t* mask_pocket, int64_t n_lig, int64_t n_pocket, int64_t batch,
+                              int32_t atom_nf, int32_t residue_nf, float alpha_s, float sigma_s,
+                              float alpha_ts, float sigma_ts, int32_t resample, int32_t remove_com) {
+  StreamDevice stream_device_(stream);
+  if (!z_lig || !xh_pocket || !scratch_lig || !xh0_lig || !com_pocket0 || !fixed || !noise_known ||
+      (resample && !noise_resample) || !mask_lig || !mask_pocket || batch < 1)
+    return fail(DSBDD_ERR_ARG, "bad argument");
+  CondRepaintArgs a{z_lig, xh_pocket, scratch_lig, xh0_lig, com_pocket0, fixed, noise_known, noise_resample,
+                    mask_lig, mask_pocket, (int)n_lig, (int)n_pocket, 3 + atom_nf, 3 + residue_nf, alpha_s,
+                    sigma_s, alpha_ts, sigma_ts, resample, remove_com};
+  hipLaunchKernelGGL(cond_repaint_kernel, dim3((int)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_cond_step_keyed(void* stream, float* z_lig, float* xh_pocket, const float* eps_lig, float* scratch_lig,
+                          const float* xh0_lig, const float* com_pocket0, const float* fixed, const int64_t* mask_lig,
+                          const int64_t* mask_pocket, int64_t n_lig, int64_t n_pocket, int64_t batch, int32_t atom_nf,
+                          int32_t residue_nf, float alpha_ts, float c_eps, float sigma, int32_t repaint, float alpha_s,
+                          float sigma_s, float sigma_ts, int32_t remove_com, uint64_t seed, uint64_t draw_index,
+                          int64_t sample_offset, const int64_t* sample_ids, float* t_word, float t_next) {
+  StreamDevice stream_device_(stream);
+  if (!z_lig || !xh_pocket || !eps_lig || !mask_lig || !mask_pocket || batch < 1 || repaint < 0 || repaint > 2 ||
+      (repaint && (!scratch_lig || !xh0_lig || !com_pocket0 || !fixed)))
+    return fail(DSBDD_ERR_ARG, "bad argument");
+  CondStepArgs a{};
+  a.rp = CondRepaintArgs{z_lig, xh_pocket, scratch_lig, xh0_lig, com_pocket0, fixed, nullptr, nullptr, mask_lig, mask_pocket,
+                         (int)n_lig, (int)n_pocket, 3 + atom_nf, 3 + residue_nf, alpha_s, sigma_s, alpha_ts, sigma_ts,
+                         repaint == 2, remove_com};
+  a.eps = eps_lig; a.u_alpha_ts = alpha_ts; a.u_c_eps = c_eps; a.u_sigma = sigma; a.repaint = repaint;
+  a.seed = seed; a.draw = draw_index; a.sample_offset = sample_offset; a.sample_ids = sample_ids;
+  a.t_word = t_word; a.t_next = t_next;
+  hipLaunchKernelGGL(cond_step_keyed_kernel, dim3((int)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_joint_repaint_update(void* stream, float* z_lig, float* z_pocket, float* scratch_lig,
+                               float* scratch_pocket, const float* xh0_lig, const float* xh0_pocket,
+                               const float* fixed_lig, const float* fixed_pocket, const float* noise_known_lig,
+                               const float* noise_known_pocket, const float* noise_jump_lig,
+                               const float* noise_jump_pocket, const int64_t* mask_lig,
+                               const int64_t* mask_pocket, int64_t n_lig, int64_t n_pocket, int64_t batch,
+                               int32_t atom_nf, int32_t residue_nf, float alpha_s, float sigma_s,
+                               float alpha_ts, float sigma_ts, int32_t jump) {
+  StreamDevice stream_device_(stream);
+  if (!z_lig || !z_pocket || !scratch_lig || !scratch_pocket || !xh0_lig || !xh0_pocket || !fixed_lig ||
+      !fixed_pocket || !noise_known_lig || !noise_known_pocket || (jump && (!noise_jump_lig || !noise_jump_pocket)) ||
+      !mask_lig || !mask_pocket || batch < 1)
+    return fail(DSBDD_ERR_ARG, "bad argument");
+  JointRepaintArgs a{z_lig, z_pocket, scratch_lig, scratch_pocket, xh0_lig, xh0_pocket, fixed_lig, fixed_pocket,
+                     noise_known_lig, noise_known_pocket, noise_jump_lig, noise_jump_pocket, mask_lig, mask_pocket,
+                     (int)n_lig, (int)n_pocket, 3 + atom_nf, 3 + residue_nf, alpha_s, sigma_s, alpha_ts, sigma_ts,
+                     jump};
+  hipLaunchKernelGGL(joint_repaint_kernel, dim3((int)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_randn_keyed(void* stream, float* out, const int64_t* mask, int64_t n_rows, int32_t n_cols,
+                      int64_t batch, int64_t sample_offset, const int64_t* sample_ids, uint64_t seed,
+                      uint64_t draw_index, uint32_t stream_id) {
+  StreamDevice stream_device_(stream);
+  (void)batch;
+  if (!out || !mask || n_rows < 0 || n_cols < 1) return fail(DSBDD_ERR_ARG, "bad argument");
+  const int64_t n = n_rows * n_cols;
+  if (n == 0) return DSBDD_OK;
+  hipLaunchKernelGGL(randn_keyed_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), out, mask, (int)n_rows, (int)n_cols, sample_offset,
+                     sample_ids, seed, draw_index, stream_id);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_node_linear(void* stream, const float* A1, int32_t lda1, int32_t K1, const float* A2, int32_t lda2,
+                      int32_t K2, const float* WT, int32_t ldw, const float* bias, const float* R, int32_t ldr,
+                      float* C, int32_t ldc, int64_t M, int32_t N, int32_t act) {
+  StreamDevice stream_device_(stream);
+  if (!A1 || !WT || !C || K1 < 1 || K2 < 0 || (K2 > 0 && !A2) || (ldw & 3) || N > ldw ||
+      (reinterpret_cast<uintptr_t>(WT) & 15))
+    return fail(DSBDD_ERR_ARG, "bad argument (WT must be 16-byte aligned with ldw % 4 == 0)");
+  HIP_TRY(nl(static_cast<hipStream_t>(stream), A1, lda1, K1, A2, lda2, K2, WT, ldw, bias, R, ldr, C, ldc, M, N, act));
+  return DSBDD_OK;
+}
+
+int dsbdd_bond_orders(void* stream, const float* x, const int32_t* atom_type, const int32_t* mol_off,
+                      int64_t batch, int32_t n_types, const float* bonds1, const float* bonds2,
+                      const float* bonds3, float margin1, float margin2, float margin3, int32_t n_max,
+                      int8_t* order) {
+  StreamDevice stream_device_(stream);
+  if (!x || !atom_type || !mol_off || !bonds1 || !bonds2 || !bonds3 || !order || batch < 1 || n_types < 1 ||
+      n_max < 1)
+    return fail(DSBDD_ERR_ARG, "bad argument");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipMemsetAsync(order, 0, (size_t)batch * n_max * n_max, s));
+  BondArgs a{x, atom_type, mol_off, bonds1, bonds2, bonds3, margin1, margin2, margin3, n_types, n_max,
+             reinterpret_cast<signed char*>(order)};
+  hipLaunchKernelGGL(bond_orders_kernel, dim3((unsigned)batch), dim3(64), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_pack_ligands(void* stream, const float* tmpl_x, const int32_t* tmpl_type, const int32_t* tmpl_ptr,
+                       int32_t n_tmpl, int64_t tmpl_rows, const int32_t* slot_tmpl, const int32_t* slot_size,
+                       const int32_t* slot_off, int64_t batch, int64_t n_rows, int32_t atom_nf, float* x,
+                       float* one_hot, int64_t* lig_fixed, int64_t* mask, int64_t* size) {
+  StreamDevice stream_device_(stream);
+  if (!tmpl_ptr || !slot_tmpl || !slot_size || !slot_off || !x || !one_hot || !lig_fixed || !mask || !size)
+    return fail(DSBDD_ERR_ARG, "null argument");
+  if ((tmpl_rows > 0 && (!tmpl_x || !tmpl_type)) || tmpl_rows < 0 || n_tmpl < 0 || atom_nf < 1)
+    return fail(DSBDD_ERR_ARG, "bad template set");
+  if (batch < 1 || n_rows < batch || n_rows > 0x7fffffff / 4)
+    return fail(DSBDD_ERR_ARG, "every slot needs at least one row (n_rows >= batch)");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  PackArgs a{tmpl_x, tmpl_type, tmpl_ptr, slot_tmpl, slot_size, slot_off, n_tmpl, (int)tmpl_rows, (int)batch,
+             (int)n_rows, atom_nf, x, one_hot, reinterpret_cast<long long*>(lig_fixed),
+             reinterpret_cast<long long*>(mask), reinterpret_cast<long long*>(size)};
+  hipLaunchKernelGGL(pack_ligands_kernel, dim3((unsigned)((n_rows + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_build_edges(void* stream, const float* x, const int64_t* mask_lig, const int64_t* mask_pocket,
+                      int64_t n_lig, int64_t n_pocket, int64_t batch, const dsbdd_config* cfg,
+                      int32_t* node_batch, int32_t* lig_off, int32_t* poc_off, int32_t* deg, int32_t* row_ptr,
+                      int32_t* edge_row, int32_t* edge_col, float* edge_d0, int64_t edge_capacity,
+                      int32_t* status) {
+  StreamDevice stream_device_(stream);
+  if (!x || !mask_lig || !mask_pocket || !cfg || !node_batch || !lig_off || !poc_off || !deg || !row_ptr ||
+      !edge_row || !edge_col || !edge_d0 || !status || batch < 1)
+    return fail(DSBDD_ERR_ARG, "bad argument");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int N = (int)(n_lig + n_pocket), B = (int)batch;
+  const int work = N > B + 1 ? N : B + 1;
+  hipLaunchKernelGGL(prep_kernel, dim3((work + 255) / 256), dim3(256), 0, s, mask_lig, (int)n_lig, mask_pocket,
+                     (int)n_pocket, B, node_batch, lig_off, poc_off, (int*)nullptr);
+  HIP_TRY(hipGetLastError());
+  return build_edges_impl(s, x, (int)n_lig, N, B, *cfg, node_batch, lig_off, poc_off, deg, row_ptr, edge_row,
+                          edge_col, edge_d0, edge_capacity, status);
+}
+
+}  // extern "C"

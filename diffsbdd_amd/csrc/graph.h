@@ -60,7 +60,7 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 // Optional second output of the radius graph: the edges that have a LIGAND endpoint (all edges of
 // ligand rows + the ligand columns of pocket rows), in the same aligned layout with its own
 // row_ptr / deg.  Block 0 of a pocket-conditioned chain evaluates the pocket-pocket messages
-// separately (engine.hip, "pocket frame"), so its message stage runs on this list.
+// separately (forward.h, "Pocket frame"), so its message stage runs on this list.
 struct EdgeList2 {
   int* deg; int* row_ptr; int* erow; int* ecol; float* ed0; int e_cap;
   SegAlign seg;      // scan_tmp / seg_base of this list
@@ -337,7 +337,7 @@ struct LevelArgs {
   int* erow; int* ecol; float* ed0; int e_cap;
   // running sums over calls (bench / tests): [0..5) nodes with level <= r, [5..10) list slots, [10..15) edges, [15] calls
   unsigned long long* stats;
-  // "ghost" rows of the canonical pocket (engine.hip, forward cone): node_off entries at the front of lvl_list and
+  // "ghost" rows of the canonical pocket (forward.h, forward cone): node_off entries at the front of lvl_list and
   // edge_off slots (a multiple of kEdgeAlign) at the front of the edge list are theirs, written once per chain
   int node_off; int edge_off;
   int e_cap_nat;            // capacity of the natural-order list: never indexed past it, even when the radius graph
@@ -535,7 +535,7 @@ __global__ __launch_bounds__(kThreads) void gather_rows_kernel(float* dst, const
 }
 
 // h[i] <- h[ghost twin of i] for the pocket rows with lo < level <= hi: rows the next message stage reads but the
-// ligand could not have influenced yet -- their value is the canonical pocket's (engine.hip, forward cone).
+// ligand could not have influenced yet -- their value is the canonical pocket's (forward.h, forward cone).
 __global__ __launch_bounds__(kThreads) void canon_fill_kernel(float* h, const int* lvl, const int* twin_local,
                                                               int n_lig, int n_nodes, int ghost_base, int lo,
                                                               int hi, int H, float* pq = nullptr, int ldpq = 0) {

@@ -23,7 +23,7 @@
 // workspace between the two calls (per block: h, the projections, the aggregate, the node MLP's pre-activation and
 // activation, the coordinates); nothing of size [E][H] is kept (the edge activations are recomputed, train.h).
 //
-// Included by engine.hip behind the dsbdd_train_* building blocks it calls.
+// Included by engine.hip behind the dsbdd_train_* building blocks it calls (train_blocks.h).
 #pragma once
 
 namespace dsbdd {
@@ -277,7 +277,7 @@ static TnParamIndex tn_index(const dsbdd_config& c) {
   return p;
 }
 
-static const int kTnSideDefault = SIDE_CO | SIDE_NODE_WG | SIDE_COORD_WG;     // DSBDD_TRAIN_STREAMS (bit mask of SIDE_*, engine.hip) overrides
+static const int kTnSideDefault = SIDE_CO | SIDE_NODE_WG | SIDE_COORD_WG;     // DSBDD_TRAIN_STREAMS (bit mask of SIDE_*, train_blocks.h) overrides
 struct dsbdd_train_net {
   dsbdd_config cfg;
   TnParamIndex ix;
@@ -285,7 +285,7 @@ struct dsbdd_train_net {
   std::vector<const float*> last_params;
   void* last_pack = nullptr;
   int n_pack = 0, n_tab = 0;
-  // side streams of the backward (TrainSide, engine.hip), created on the first backward call; DSBDD_TRAIN_STREAMS=0: none
+  // side streams of the backward (TrainSide, train_blocks.h), created on the first backward call; DSBDD_TRAIN_STREAMS=0: none
   TrainSide side;
   bool side_ready = false;
   int side_mask = 0;
@@ -491,7 +491,7 @@ extern "C" {
 
 int dsbdd_train_net_create(const dsbdd_config* cfg, dsbdd_train_net** out) {
   if (!cfg || !out) return fail(DSBDD_ERR_ARG, "null argument");
-  if (!train_h_ok(cfg->hidden_nf) || cfg->n_layers < 1 || cfg->inv_sublayers < 1 || cfg->atom_nf < 1 || cfg->residue_nf < 1)
+  if (!hidden_nf_ok(cfg->hidden_nf) || cfg->n_layers < 1 || cfg->inv_sublayers < 1 || cfg->atom_nf < 1 || cfg->residue_nf < 1)
     return fail(DSBDD_ERR_ARG, "unsupported configuration");
   auto* n = new dsbdd_train_net();
   n->cfg = *cfg; n->ix = tn_index(*cfg);

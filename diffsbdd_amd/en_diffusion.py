@@ -618,7 +618,7 @@ class EnVariationalDiffusion(nn.Module):
             raise ValueError("NaN detected in EGNN output")
 
     share_identical_pockets = True   # evaluate block 0's pocket-pocket messages once for a batch of identical pockets
-    # forward cone of the engine (csrc/engine.hip): 2 = on, 0 = off (1 = the engine's own cost model, for direct C-API
+    # forward cone of the engine (csrc/forward.h): 2 = on, 0 = off (1 = the engine's own cost model, for direct C-API
     # callers).  Cone on / off differ in rounding (the canonical pocket is evaluated on the raw pocket coordinates), so the
     # mode is decided HERE, once per chain and from the pocket groups alone (`_cone_for_groups`: on while the distinct
     # pockets are at most 0.2 of the batch (measured break-even at B = 64: 12 groups, profiles/r4n_cone_rule.md) -- one pocket repeated, the reference's generate_ligands / test.py case: on;

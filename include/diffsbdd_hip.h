@@ -205,7 +205,7 @@ int dsbdd_engine_graph_stats(const dsbdd_engine* e, int64_t* replays, int64_t* c
 
 /* Which rows the message stages of the last forward evaluated (host-side bookkeeping, no sync): radius[g] = hop
  * level up to which stage g computed its rows (4 = every row), ghost[g] = 1 when the stage also evaluated the
- * canonical pocket (identical pockets, csrc/engine.hip "forward cone"), timed_level = radius of the launches that
+ * canonical pocket (identical pockets, csrc/forward.h "Forward cone"), timed_level = radius of the launches that
  * dsbdd_engine_profile brackets.  All 4 / 0 unless the call was a ligand-output-only call in pocket-conditioning
  * mode (eps_pocket == NULL), see csrc/graph.h "Level-ordered edge list". */
 int dsbdd_engine_last_plan(const dsbdd_engine* e, int32_t* radius, int32_t* ghost, int32_t capacity,

@@ -1,5 +1,5 @@
 """CPU emulation of what libdiffsbdd_hip.so computes, written against the PACKED
-weight slots and following diffsbdd_amd/csrc/engine.hip launch by launch.
+weight slots and following diffsbdd_amd/csrc/forward.h launch by launch.
 
 Purpose (host-logic tests, no GPU): prove that the weight packing
 (diffsbdd_amd/engine.pack_weights), the slot order, the paddings, the exact
@@ -341,7 +341,7 @@ def node_gemm_schedule(M, N, ct, balance, grid_x=None):
 
 
 def stage_plan(n_stages, cone, levels=5):
-    """Radius and ghost flag of every message stage of a ligand-output-only call (csrc/engine.hip forward_impl):
+    """Radius and ghost flag of every message stage of a ligand-output-only call (csrc/forward.h, struct Forward):
     backward cone G - g, with the forward cone min(g + 1, G - g); radii are capped at levels - 1 ("every row"); the
     canonical pocket is evaluated while a later stage still reads rows the previous one did not compute."""
     lv = levels - 1

@@ -388,7 +388,7 @@ def test_ligand_only_call_evaluates_live_rows(arch, B, frame, monkeypatch):
 def test_full_atom_chains_with_identical_pockets_vs_oracle():
     """Free-running chains on a full-atom pocket repeated over the batch -- the configuration in which the
     chain hands the engine a pocket frame and the engine runs the forward cone on a canonical pocket
-    (csrc/engine.hip): ConditionalDDPM.sample_given_pocket and .inpaint (every ligand atom known: bench.py's
+    (csrc/forward.h): ConditionalDDPM.sample_given_pocket and .inpaint (every ligand atom known: bench.py's
     anchored states) against the oracle with the same noise tape, 4 steps, 1e-3 on coordinates (the tolerance
     of the other free-running tests), identical atom types."""
     from diffsbdd_amd.pocket import prepare_pocket

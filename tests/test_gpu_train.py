@@ -420,7 +420,7 @@ def test_input_gradients_match_the_torch_path(arch):
                                               ("small_joint", [5, 7, 6], [40, 35, 38])])
 def test_side_streams_of_the_backward_keep_the_bits(arch, n_lig, n_poc):
     """Round 6: the network backward runs the weight gradients and the second coordinate MLP's chain on side streams
-    (DSBDD_TRAIN_STREAMS, a bit mask read when the per-module handle is created; csrc/engine.hip TrainSide).  Kernels and
+    (DSBDD_TRAIN_STREAMS, a bit mask read when the per-module handle is created; csrc/train_blocks.h TrainSide).  Kernels and
     reduction orders are those of the single-stream sequence, so every parameter and input gradient must be IDENTICAL --
     a missing fork / join would show up here as a difference between the masks or between repeats."""
     import copy

@@ -1,5 +1,5 @@
 """CPU tests of the host side: weight packing + launch orchestration (through
-the emulator that mirrors engine.hip), state_dict contract, schedule tables,
+the emulator that mirrors csrc/forward.h), state_dict contract, schedule tables,
 RePaint schedule, C-ABI symbol export."""
 import ctypes
 import json
@@ -416,7 +416,7 @@ def test_node_gemm_tile_schedule_covers_every_output_once():
 
 
 def test_stage_plan_model():
-    """Host model of the per-stage plan (tests/_emulate.stage_plan mirrors engine.hip; the GPU tests compare
+    """Host model of the per-stage plan (tests/_emulate.stage_plan mirrors csrc/forward.h; the GPU tests compare
     dsbdd_engine_last_plan with the same formulas): a row evaluated by stage g + 1 is either computed by stage g or
     canonical, the last stage computes hop <= 1, and without the forward cone the first stages compute everything."""
     assert em.stage_plan(6, True) == ([1, 2, 3, 3, 2, 1], [1, 1, 1, 0, 0, 0])

@@ -169,7 +169,7 @@ def test_packed_sampling_is_independent_of_the_packing():
 def test_packed_sampling_full_atom_pockets_is_independent_of_the_packing():
     """The same with FULL-ATOM pockets (3rfm 286 atoms, 5ndu 287 atoms): here the chain hands the engine a pocket frame
     with one representative per distinct pocket of the batch and the ligand-output-only calls run the forward /
-    backward cones (csrc/engine.hip).  A pocket's molecules are bit-identical whether it shares its batches with the
+    backward cones (csrc/forward.h).  A pocket's molecules are bit-identical whether it shares its batches with the
     other pocket (12 or 7 slots) or not (4 slots: mostly one pocket per batch)."""
     from oracle import weights as W
     from diffsbdd_amd import pocket as pk
