@@ -8,9 +8,14 @@
 //   forward.h       the per-call plan (pocket frame, level pruning, "forward cone") and the stages of one forward
 //   graph_cache.h   ghost-row upkeep and the hipGraph capture / replay around the forward
 //   capi_kernels.h  C-ABI wrappers of the stand-alone kernels
-//   train_blocks.h, train_net.h, train_api.h   the training step
+//   train_blocks.h  the training step's building blocks: weight gradients, scratch, side streams, one edge stage each way
+//   train_net.h     the training step of the whole network: parameter index, pack buffer, workspace, the two walks
+//   train_api.h     every dsbdd_train_* / dsbdd_loss_* / dsbdd_optim_* entry point
+// (device code: the kernel headers included first; train_kernels.h holds the network walk's own kernels)
 #include "../../include/diffsbdd_hip.h"
 
+#include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -33,6 +38,7 @@
 #include "node_chain.h"
 #include "node_linear.h"
 #include "train.h"
+#include "train_kernels.h"
 
 using namespace dsbdd;
 

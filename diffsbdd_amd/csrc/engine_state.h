@@ -11,6 +11,12 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
     if (_e != hipSuccess)                                                          \
       return fail(DSBDD_ERR_LAUNCH, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
+// the same for the int codes of the library's own helpers
+#define RC_TRY(expr)                       \
+  do {                                     \
+    const int _rc = (expr);                \
+    if (_rc != DSBDD_OK) return _rc;       \
+  } while (0)
 
 // Every entry point launches on the caller's stream: make that stream's device the current one for the duration of the
 // call (a module living on a GPU that is not torch's current device must not launch through another device's
@@ -33,6 +39,15 @@ struct StreamDevice {
 
 static inline int pad4(int v) { return (v + 3) & ~3; }
 static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+// Hands out consecutive 256-byte aligned pieces of one buffer (the training step's pack buffer, workspace and scratch).
+// base == nullptr: sizes only (`off` is the total), every pointer null.
+struct Carver {
+  char* base;
+  size_t off = 0;
+  char* bytes(size_t n) { char* q = base ? base + off : nullptr; off += al256(n); return q; }
+  float* f(size_t floats) { return reinterpret_cast<float*>(bytes(floats * 4)); }
+  float* f1(size_t floats) { return f(floats > 0 ? floats : 1); }      // an empty buffer still gets an address of its own
+};
 
 // The one list of supported hidden_nf: run-time H -> compile-time constant.  f is a generic callable taking
 // std::integral_constant<int, H> and returning hipError_t.
@@ -293,6 +308,11 @@ static bool env_int(const char* name, long long* v, bool mask = false) {
   if (!s) return false;
   *v = mask ? (long long)strtoul(s, nullptr, 0) : (long long)atoi(s);
   return true;
+}
+// NAME's value when it is set and lies in [lo, hi], otherwise dflt
+static int env_int_in(const char* name, long long lo, long long hi, int dflt) {
+  long long v;
+  return env_int(name, &v) && v >= lo && v <= hi ? (int)v : dflt;
 }
 static void read_env_switches(dsbdd_engine* e) {
   long long v;

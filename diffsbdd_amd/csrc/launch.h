@@ -9,6 +9,15 @@ static hipError_t nl(hipStream_t s, const float* A1, int lda1, int K1, const flo
   return launch_node_linear(s, a);
 }
 
+// one thread per item in workgroups of 256: the elementwise kernels.  The arguments are converted to the kernel's own
+// parameter types (float* -> const float*, nullptr -> T*).
+template <class... P, class... A>
+static int launch_1d(void (*kernel)(P...), size_t n_items, hipStream_t s, A... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, s, static_cast<P>(args)...);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
 static int device_cus() {      // CU count of the CURRENT device (cached per device id)
   static int cache[64] = {0};
   int dev = 0;

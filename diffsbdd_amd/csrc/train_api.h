@@ -1,4 +1,5 @@
-// C-ABI wrappers of the native training loop around the network call (included by engine.hip): the loss terms of the
+// C-ABI entry points of training (included by engine.hip): argument checks around the building blocks (train_blocks.h)
+// and the network walk (train_net.h), then the native training loop around the network call: the loss terms of the
 // pocket-conditioned step (loss_head.h), the fused clipping + AdamW step (optim.h), the auxiliary LJ loss (lj_loss.h).
 #pragma once
 
@@ -13,6 +14,137 @@ static bool loss_cfg_ok(const dsbdd_loss_cfg* c) {
 
 extern "C" {
 
+// ---- building blocks (train_blocks.h) -----------------------------------------------------------------------------------
+size_t dsbdd_train_scratch_bytes(int32_t H, int64_t n_nodes, int64_t n_edges) {
+  if (!hidden_nf_ok(H) || n_nodes < 1 || n_edges < 0) return 0;
+  return carve_train(nullptr, H, n_nodes, n_edges).bytes;
+}
+
+size_t dsbdd_train_wgrad_scratch_bytes(int64_t K, int64_t M, int64_t N) {
+  if (K < 1 || M < 1 || N < 1) return 0;
+  return wgrad_floats_upto(K, M, N) * 4;      // covers every K' <= K (the plan is not monotonic in K)
+}
+
+size_t dsbdd_train_wgrad_plan_bytes(int64_t K, int64_t M, int64_t N) {
+  if (K < 1 || M < 1 || N < 1) return 0;
+  return wgrad_plan(K, M, N).floats * 4;      // what a call with exactly this K writes (tests: <= the bound above)
+}
+
+int dsbdd_train_edge_rev(void* stream, const dsbdd_train_graph* g, int32_t* rev) {
+  StreamDevice stream_device_(stream);
+  if (!graph_ok(g) || !rev) return fail(DSBDD_ERR_ARG, "bad argument");
+  if (g->n_edges == 0) return DSBDD_OK;
+  return launch_1d(edge_rev_kernel, (size_t)g->n_edges, static_cast<hipStream_t>(stream), g->erow, g->ecol, g->row_ptr, g->deg,
+                   (int)g->n_edges, (int)g->n_nodes, rev);
+}
+
+int dsbdd_train_sample_mean(void* stream, const float* x, const dsbdd_train_graph* g, float* mean) {
+  StreamDevice stream_device_(stream);
+  if (!graph_ok(g) || !x || !mean) return fail(DSBDD_ERR_ARG, "bad argument");
+  return sample_mean_impl(static_cast<hipStream_t>(stream), x, g, mean);
+}
+
+int dsbdd_train_gcl_forward(void* stream, int32_t H, const dsbdd_train_graph* g, const dsbdd_train_mlp* m, const float* x,
+                            float norm_factor, float* agg, void* scratch, size_t scratch_bytes) {
+  return gcl_forward_impl(stream, H, g, m, x, norm_factor, agg, scratch, scratch_bytes, nullptr);
+}
+
+int dsbdd_train_coord_forward(void* stream, int32_t H, const dsbdd_train_graph* g, const dsbdd_train_mlp* m, int32_t n_mlp,
+                              const float* x, const float* mean, int64_t n_upd, float norm_constant, float coords_range,
+                              int32_t use_tanh, float norm_factor, float* x_out, void* scratch, size_t scratch_bytes) {
+  return coord_forward_impl(stream, H, g, m, n_mlp, x, mean, n_upd, norm_constant, coords_range, use_tanh, norm_factor, x_out,
+                            scratch, scratch_bytes, nullptr, 0);
+}
+
+int dsbdd_train_gcl_backward(void* stream, int32_t H, const dsbdd_train_graph* g, const dsbdd_train_mlp* m, const float* x,
+                             float norm_factor, const float* d_agg, const dsbdd_train_mlp_grad* out, float* d_x,
+                             void* scratch, size_t scratch_bytes) {
+  return gcl_backward_impl(stream, H, g, m, x, norm_factor, d_agg, out, d_x, scratch, scratch_bytes, nullptr);
+}
+
+int dsbdd_train_coord_backward(void* stream, int32_t H, const dsbdd_train_graph* g, const dsbdd_train_mlp* m, int32_t n_mlp,
+                               const float* x, const float* mean, int64_t n_upd, int64_t e_upd, float norm_constant,
+                               float coords_range, int32_t use_tanh, float norm_factor, const float* d_xout,
+                               const dsbdd_train_mlp_grad* out, float* d_x, float* d_mean, void* scratch,
+                               size_t scratch_bytes) {
+  return coord_backward_impl(stream, H, g, m, n_mlp, x, mean, n_upd, e_upd, norm_constant, coords_range, use_tanh, norm_factor,
+                             d_xout, out, d_x, d_mean, scratch, scratch_bytes, nullptr);
+}
+
+int dsbdd_train_radial_backward(void* stream, const dsbdd_train_graph* g, const float* x, const float* gd, float* d_x) {
+  StreamDevice stream_device_(stream);
+  if (!graph_ok(g) || !g->rev || !x || !gd || !d_x) return fail(DSBDD_ERR_ARG, "bad argument");
+  return radial_backward_impl(static_cast<hipStream_t>(stream), g, x, gd, d_x);
+}
+
+int dsbdd_train_wgrad(void* stream, const float* A, int32_t lda, const float* B, int32_t ldb, int64_t K, int32_t M,
+                      int32_t N, float* C, void* scratch, size_t scratch_bytes) {
+  StreamDevice stream_device_(stream);
+  if (!A || !B || !C || K < 1 || M < 1 || N < 1 || lda < M || ldb < N || !scratch) return fail(DSBDD_ERR_ARG, "bad argument");
+  if (wgrad_plan(K, M, N).floats * 4 > scratch_bytes) return fail(DSBDD_ERR_CAPACITY, "scratch too small");
+  return wgrad_impl(static_cast<hipStream_t>(stream), A, lda, B, ldb, K, M, N, C, static_cast<float*>(scratch), scratch_bytes / 4);
+}
+
+int dsbdd_train_colsum(void* stream, const float* A, int32_t lda, int64_t M, int32_t N, float* out, void* scratch,
+                       size_t scratch_bytes) {
+  StreamDevice stream_device_(stream);
+  if (!A || !out || M < 1 || N < 1 || lda < N || !scratch) return fail(DSBDD_ERR_ARG, "bad argument");
+  if ((size_t)((M + 31) / 32) * N * 4 > scratch_bytes) return fail(DSBDD_ERR_CAPACITY, "scratch too small");
+  HIP_TRY(reduce_parts(static_cast<hipStream_t>(stream), A, (int)M, (size_t)lda, N, out, static_cast<float*>(scratch)));
+  return DSBDD_OK;
+}
+
+// ---- the network walk (train_net.h) -------------------------------------------------------------------------------------
+int dsbdd_train_net_create(const dsbdd_config* cfg, dsbdd_train_net** out) {
+  if (!cfg || !out) return fail(DSBDD_ERR_ARG, "null argument");
+  if (!hidden_nf_ok(cfg->hidden_nf) || cfg->n_layers < 1 || cfg->inv_sublayers < 1 || cfg->atom_nf < 1 || cfg->residue_nf < 1)
+    return fail(DSBDD_ERR_ARG, "unsupported configuration");
+  *out = tn_create(*cfg);
+  return DSBDD_OK;
+}
+void dsbdd_train_net_destroy(dsbdd_train_net* n) {
+  if (n && n->side_ready) n->side.destroy();
+  delete n;
+}
+int dsbdd_train_net_param_count(const dsbdd_train_net* n) { return n ? n->ix.n : 0; }
+size_t dsbdd_train_net_pack_bytes(const dsbdd_train_net* n) { return n ? tn_carve_pack(nullptr, n->cfg).bytes : 0; }
+size_t dsbdd_train_net_workspace_bytes(const dsbdd_train_net* n, const dsbdd_train_graph* g) {
+  if (!n || !graph_ok(g)) return 0;
+  return tn_carve_ws(nullptr, tn_dims(n->cfg, g), n->store_z2).bytes;
+}
+
+int dsbdd_train_net_forward(dsbdd_train_net* net, void* stream, const dsbdd_train_graph* g, const float* const* params,
+                            void* pack, size_t pack_bytes, void* ws, size_t ws_bytes, const float* xh_lig,
+                            const float* xh_pocket, const float* t, int64_t t_count, int32_t zero_nan, float* eps_lig,
+                            float* eps_pocket, int32_t* status) {
+  StreamDevice stream_device_(stream);
+  if (!net || !graph_ok(g) || !params || !pack || !ws || !t || !status || t_count < 1 || (g->n_lig > 0 && (!xh_lig || !eps_lig)) ||
+      (g->n_nodes > g->n_lig && (!xh_pocket || !eps_pocket)))
+    return fail(DSBDD_ERR_ARG, "bad argument");
+  for (int i = 0; i < net->ix.n; ++i) if (!params[i]) return fail(DSBDD_ERR_ARG, "null parameter " + std::to_string(i));
+  TrainForward f(net, stream, g, params, pack, ws);
+  if (f.pk.bytes > pack_bytes) return fail(DSBDD_ERR_CAPACITY, "pack buffer too small (dsbdd_train_net_pack_bytes)");
+  if (f.w.bytes > ws_bytes) return fail(DSBDD_ERR_CAPACITY, "workspace too small (dsbdd_train_net_workspace_bytes)");
+  return f.run(xh_lig, xh_pocket, t, t_count, zero_nan, eps_lig, eps_pocket, status);
+}
+
+int dsbdd_train_net_backward(dsbdd_train_net* net, void* stream, const dsbdd_train_graph* g, const float* const* params,
+                             float* const* grads, void* pack, size_t pack_bytes, void* ws, size_t ws_bytes,
+                             int64_t e_upd, const float* d_eps_lig, const float* d_eps_pocket, float* d_xh_lig,
+                             float* d_xh_pocket) {
+  StreamDevice stream_device_(stream);      // (makes the stream's device current: the side streams are created on it)
+  if (!net || !graph_ok(g) || !g->rev || !params || !grads || !pack || !ws) return fail(DSBDD_ERR_ARG, "bad argument");
+  for (int i = 0; i < net->ix.n; ++i)
+    if (!params[i] || !grads[i]) return fail(DSBDD_ERR_ARG, "null parameter / gradient " + std::to_string(i));
+  if ((g->n_lig > 0 && !d_eps_lig) || (g->n_nodes > g->n_lig && !d_eps_pocket)) return fail(DSBDD_ERR_ARG, "null output gradient");
+  if (net->cfg.update_pocket_coords) e_upd = g->n_edges;      // (else: row_ptr[n_lig], the edge prefix of the ligand rows, a host value)
+  if (e_upd < 0 || e_upd > g->n_edges) return fail(DSBDD_ERR_ARG, "e_upd out of range");
+  TrainBackward f(net, stream, g, params, grads, pack, ws, e_upd, d_xh_lig || d_xh_pocket);
+  if (f.pk.bytes > pack_bytes || f.w.bytes > ws_bytes) return fail(DSBDD_ERR_CAPACITY, "buffer too small");
+  return f.run(d_eps_lig, d_eps_pocket, d_xh_lig, d_xh_pocket);
+}
+
+// ---- loss terms (loss_head.h) -------------------------------------------------------------------------------------------
 int dsbdd_edge_capacity(void* stream, const int64_t* lig_mask, int64_t n_lig, const int64_t* pocket_mask, int64_t n_pocket,
                         int64_t batch, int64_t* out) {
   StreamDevice stream_device_(stream);

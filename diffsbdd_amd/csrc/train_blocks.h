@@ -1,5 +1,6 @@
 // Training-step building blocks (host side of csrc/train.h; included by engine.hip in front of train_net.h): weight
-// gradients, the backward edge-kernel launches, side streams, and the dsbdd_train_* entry points.
+// gradients, the edge-stage scratch, side streams, and the forward / backward of one message or coordinate stage.  The
+// dsbdd_train_* entry points over them are in train_api.h.
 #pragma once
 
 // out[i] = sum_p part[p * stride + i] in a fixed order (two levels above 64 parts); tmp: ceil(n_part / 32) * width floats
@@ -26,8 +27,8 @@ static int64_t wgrad_chunk_bound(int64_t K, int64_t M, int64_t N) {
   // 256 / tiles chunks for the edge-level ones: <= 96 partial slabs reduce in ONE ordered launch (round 6: 768 -> 256,
   // 14.46 -> 14.03 ms per training step, profiles/r6_train_step.md; round 4's sweep had preferred 768 when the reduction
   // was two launches either way)
-  static const int min_kc = [] { const char* v = getenv("DSBDD_WGRAD_MINKC"); return v && atoi(v) >= 32 ? atoi(v) : 64; }();
-  static const int max_wg = [] { const char* v = getenv("DSBDD_WGRAD_MAXWG"); return v && atoi(v) >= 1 ? atoi(v) : 256; }();
+  static const int min_kc = env_int_in("DSBDD_WGRAD_MINKC", 32, INT_MAX, 64);      // (read once, on first use)
+  static const int max_wg = env_int_in("DSBDD_WGRAD_MAXWG", 1, INT_MAX, 256);
   const int64_t tiles = ((M + 127) / 128) * ((N + 127) / 128);
   const int64_t cap = max_wg / tiles > 1 ? max_wg / tiles : 1;
   int64_t chunks = (K + min_kc - 1) / min_kc;
@@ -71,25 +72,24 @@ struct TrainScratch {
 static int train_grid(int64_t E) {
   // persistent workgroups of the backward edge kernels per CU (DSBDD_TRAIN_WG_PER_CU, default 1; the kernels fit two:
   // 256 VGPRs, 74 KB of LDS)
-  static const int per_cu = [] { const char* v = getenv("DSBDD_TRAIN_WG_PER_CU"); return v && atoi(v) >= 1 && atoi(v) <= 4 ? atoi(v) : 1; }();
+  static const int per_cu = env_int_in("DSBDD_TRAIN_WG_PER_CU", 1, 4, 1);
   return persistent_grid((E + 127) / 128, device_cus(), per_cu, 0, 1);
 }
 static TrainScratch carve_train(char* base, int H, int64_t N, int64_t E) {
   TrainScratch t{};
-  size_t off = 0;
-  auto take = [&](size_t floats) { float* p = base ? reinterpret_cast<float*>(base + off) : nullptr; off += al256(floats * 4); return p; };
-  const size_t EH = (size_t)(E > 0 ? E : 1) * H;
-  const int slots = 256 * 8;
-  t.dz2 = take(EH); t.a1 = take(EH); t.dz1 = take(EH);
-  t.partA = take((size_t)slots * kPartAll * H); t.partB = t.partA;      // one [8][H] slot per workgroup for both kernels
-  t.rtmp = take((size_t)(slots / 32 + 1) * kPartAll * H);
+  Carver cv{base};
+  const size_t EH = (size_t)(E > 0 ? E : 1) * H, E3 = 3 * (size_t)E + 4, tiles = (size_t)((E + 31) / 32 + 2);
+  const size_t slots = 256 * 8, PH = (size_t)kPartAll * H;
+  t.dz2 = cv.f(EH); t.a1 = cv.f(EH); t.dz1 = cv.f(EH);
+  t.partA = cv.f(slots * PH); t.partB = t.partA;          // one [8][H] slot per workgroup for both kernels
+  t.rtmp = cv.f((slots / 32 + 1) * PH);
   t.wg_floats = wgrad_floats_upto(E > N ? E : N, H, H);   // any K <= max(E, N): the coordinate stage runs on an edge prefix
-  t.wg = take(t.wg_floats);
-  t.gd = take(E + 1); t.gxr = take(3 * (size_t)E + 4); t.gxc = take(3 * (size_t)E + 4); t.gm = take(3 * (size_t)E + 4);
-  t.agg_head = take((size_t)((E + 31) / 32 + 2) * H);
-  t.xagg = take(2 * (3 * (size_t)N + 4)); t.xagg_head = take(2 * 4 * (size_t)((E + 31) / 32 + 2));   // one sum per MLP (pass split)
-  t.vec = take(8 * (size_t)H);
-  t.bytes = off;
+  t.wg = cv.f(t.wg_floats);
+  t.gd = cv.f(E + 1); t.gxr = cv.f(E3); t.gxc = cv.f(E3); t.gm = cv.f(E3);
+  t.agg_head = cv.f(tiles * H);
+  t.xagg = cv.f(2 * (3 * (size_t)N + 4)); t.xagg_head = cv.f(2 * 4 * tiles);   // one sum per MLP (pass split)
+  t.vec = cv.f(8 * (size_t)H);
+  t.bytes = cv.off;
   return t;
 }
 
@@ -164,22 +164,31 @@ struct TrainSide {
 };
 
 // the backward of ONE edge MLP: kernel A / E -> weight gradient -> kernel B -> node gathers; returns the per-edge gradient
-// w.r.t. the current squared distance in ts.gd.  `sd` (optional) -- what waits for what:
-//   * kernel A / E overwrites ts.dz2 / ts.a1 of scratch set `set`: it waits for the last W2 weight gradient that read this
+// w.r.t. the current squared distance in ts.gd.  `o.side` (optional) -- what waits for what:
+//   * kernel A / E overwrites ts.dz2 / ts.a1 of scratch set `o.scratch_set`: it waits for the last W2 weight gradient that read this
 //     set on the side stream (its own event), NOT for the whole side stream -- the node-level weight gradients queued there
 //     keep running beside the memory-bound kernel E (waiting for them cost the main chain 60 - 70 us per stage);
 //   * the message stage's W2 gradient stays on this stream and is preceded by a FULL join of the side stream: it streams
 //     373 MB and runs 1.6 x longer with anything beside it, and the join is the one point per block that covers the
-//     caller's hazards (dsbdd_train_net_backward: dout, dz / xcat, d_pq / d_pq4 are overwritten after it only);
+//     caller's hazards: the node-level weight and bias gradients that TrainBackward (train_net.h) queued on the side
+//     streams read dout, dz / xcat and d_pq / d_pq4.  dout is overwritten by the message stage's last tn_lin, dz / xcat
+//     by the next sublayer, d_pq / d_pq4 by the node gathers below -- all of them after this join;
 //   * a coordinate stage's W2 gradient goes to the side stream and records the set's event.
+struct MlpBwdOpts {
+  TrainSide* side = nullptr;      // the side streams, or none
+  bool already_linked = false;    // the caller joined / forked the side streams itself (coordinate stage)
+  const float* z2 = nullptr;      // the second-layer pre-activations the forward pass kept, or null: recompute (kernel A)
+  int scratch_set = 0;            // which of the two scratch sets `ts` is (the W2 gradient's event)
+};
 static int mlp_backward(hipStream_t s, int H, int mode, const dsbdd_train_graph* g, const dsbdd_train_mlp* m, const float* x,
                         int64_t E, TrainEdgeArgs a, const dsbdd_train_mlp_grad* out, const TrainScratch& ts,
-                        TrainSide* sd = nullptr, bool linked = false, const float* z2 = nullptr, int set = 0) {
+                        const MlpBwdOpts& o = {}) {
+  TrainSide* const sd = o.side;
   const int grid = train_grid(E);
   const bool side_w = sd && (sd->mask & (mode == MODE_GCL ? SIDE_GCL_WG : SIDE_COORD_WG));
   const bool late_join = sd && mode == MODE_GCL && !side_w;      // the full join sits in front of the W2 gradient instead
-  if (sd && !linked && !late_join) { HIP_TRY(sd->link(sd->wg, s)); HIP_TRY(sd->link(sd->co, s)); }
-  if (sd && sd->w2_valid[set]) HIP_TRY(hipStreamWaitEvent(s, sd->w2_done[set], 0));
+  if (sd && !o.already_linked && !late_join) { HIP_TRY(sd->link(sd->wg, s)); HIP_TRY(sd->link(sd->co, s)); }
+  if (sd && sd->w2_valid[o.scratch_set]) HIP_TRY(hipStreamWaitEvent(s, sd->w2_done[o.scratch_set], 0));
   const int slots = grid;                  // one partial-vector slot per workgroup
   a.erow = g->erow; a.ecol = g->ecol; a.ed0 = g->ed0; a.E = (int)E; a.x = x; a.n_lig = (int)g->n_lig;
   a.n_nodes = (int)g->n_nodes; a.P = m->P; a.Q = m->Q; a.ldpq = m->ldpq; a.wd = m->wd; a.wd0 = m->wd0; a.table = m->tab;
@@ -187,13 +196,13 @@ static int mlp_backward(hipStream_t s, int H, int mode, const dsbdd_train_graph*
   a.a1_out = ts.a1; a.gxr = ts.gxr; a.gxc = ts.gxc; a.gd = ts.gd; a.gd0 = out->gd0;
   // A: dz2, a1, partial bias / head vectors
   a.Bmat = m->W2T; a.dz_out = ts.dz2; a.part = ts.partA;
-  if (z2) HIP_TRY(launch_bwd_e(H, s, mode, a, z2, grid));     // the forward pass kept z2: no H x H layer here
+  if (o.z2) HIP_TRY(launch_bwd_e(H, s, mode, a, o.z2, grid));     // the forward pass kept z2: no H x H layer here
   else HIP_TRY(launch_bwd_a(H, s, mode, a, grid));
   // dW2[f][i] = sum_e dz2[e][f] a1[e][i]
   if (side_w) HIP_TRY(sd->link(s, sd->wg));
   if (late_join) { HIP_TRY(sd->link(sd->wg, s)); HIP_TRY(sd->link(sd->co, s)); }
-  { const int rc = wgrad_impl(side_w ? sd->wg : s, ts.dz2, H, ts.a1, H, E, H, H, out->d_W2, ts.wg, ts.wg_floats); if (rc != DSBDD_OK) return rc; }
-  if (side_w) { HIP_TRY(hipEventRecord(sd->w2_done[set], sd->wg)); sd->w2_valid[set] = true; }
+  RC_TRY(wgrad_impl(side_w ? sd->wg : s, ts.dz2, H, ts.a1, H, E, H, H, out->d_W2, ts.wg, ts.wg_floats));
+  if (side_w) { HIP_TRY(hipEventRecord(sd->w2_done[o.scratch_set], sd->wg)); sd->w2_valid[o.scratch_set] = true; }
   // B: dz1, partial first-layer vectors, per-edge distance gradients
   a.Bmat = m->W2; a.dz_in = ts.dz2; a.dz_out = ts.dz1; a.part = ts.partB;
   HIP_TRY(launch_bwd_b(H, s, a, grid));
@@ -207,39 +216,18 @@ static int mlp_backward(hipStream_t s, int H, int mode, const dsbdd_train_graph*
   return DSBDD_OK;
 }
 
-extern "C" {
-
-size_t dsbdd_train_scratch_bytes(int32_t H, int64_t n_nodes, int64_t n_edges) {
-  if (!hidden_nf_ok(H) || n_nodes < 1 || n_edges < 0) return 0;
-  return carve_train(nullptr, H, n_nodes, n_edges).bytes;
-}
-
-size_t dsbdd_train_wgrad_scratch_bytes(int64_t K, int64_t M, int64_t N) {
-  if (K < 1 || M < 1 || N < 1) return 0;
-  return wgrad_floats_upto(K, M, N) * 4;      // covers every K' <= K (the plan is not monotonic in K)
-}
-
-size_t dsbdd_train_wgrad_plan_bytes(int64_t K, int64_t M, int64_t N) {
-  if (K < 1 || M < 1 || N < 1) return 0;
-  return wgrad_plan(K, M, N).floats * 4;      // what a call with exactly this K writes (tests: <= the bound above)
-}
-
-int dsbdd_train_edge_rev(void* stream, const dsbdd_train_graph* g, int32_t* rev) {
-  StreamDevice stream_device_(stream);
-  if (!graph_ok(g) || !rev) return fail(DSBDD_ERR_ARG, "bad argument");
-  if (g->n_edges == 0) return DSBDD_OK;
-  hipLaunchKernelGGL(edge_rev_kernel, dim3((unsigned)((g->n_edges + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), g->erow, g->ecol, g->row_ptr, g->deg, (int)g->n_edges,
-                     (int)g->n_nodes, rev);
+// per-sample mean of x over the ligand and pocket rows of every sample (fixed order) -> mean [B][3]
+static int sample_mean_impl(hipStream_t s, const float* x, const dsbdd_train_graph* g, float* mean) {
+  hipLaunchKernelGGL(sample_mean_kernel, dim3((unsigned)g->batch), dim3(kThreads), 0, s, x, g->lig_off, g->poc_off,
+                     (int)g->n_lig, mean);
   HIP_TRY(hipGetLastError());
   return DSBDD_OK;
 }
-
-int dsbdd_train_sample_mean(void* stream, const float* x, const dsbdd_train_graph* g, float* mean) {
-  StreamDevice stream_device_(stream);
-  if (!graph_ok(g) || !x || !mean) return fail(DSBDD_ERR_ARG, "bad argument");
-  hipLaunchKernelGGL(sample_mean_kernel, dim3((unsigned)g->batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), x,
-                     g->lig_off, g->poc_off, (int)g->n_lig, mean);
+// d_x[i] = sum over the edges at node i of the per-edge gradients gd w.r.t. the squared distances (ordered gather)
+static int radial_backward_impl(hipStream_t s, const dsbdd_train_graph* g, const float* x, const float* gd, float* d_x) {
+  const int N = (int)g->n_nodes;
+  hipLaunchKernelGGL(edge_to_node3_kernel, dim3((N + 3) / 4), dim3(kThreads), 0, s, gd, (const float*)nullptr,
+                     (const float*)nullptr, x, g->ecol, g->row_ptr, g->deg, g->rev, (int)g->n_edges, N, d_x, 0);
   HIP_TRY(hipGetLastError());
   return DSBDD_OK;
 }
@@ -266,11 +254,6 @@ static int gcl_forward_impl(void* stream, int32_t H, const dsbdd_train_graph* g,
   return DSBDD_OK;
 }
 
-int dsbdd_train_gcl_forward(void* stream, int32_t H, const dsbdd_train_graph* g, const dsbdd_train_mlp* m, const float* x,
-                            float norm_factor, float* agg, void* scratch, size_t scratch_bytes) {
-  return gcl_forward_impl(stream, H, g, m, x, norm_factor, agg, scratch, scratch_bytes, nullptr);
-}
-
 static int gcl_backward_impl(void* stream, int32_t H, const dsbdd_train_graph* g, const dsbdd_train_mlp* m, const float* x,
                              float norm_factor, const float* d_agg, const dsbdd_train_mlp_grad* out, float* d_x,
                              void* scratch, size_t scratch_bytes, TrainSide* sd, const float* z2 = nullptr) {
@@ -283,13 +266,10 @@ static int gcl_backward_impl(void* stream, int32_t H, const dsbdd_train_graph* g
   hipStream_t s = static_cast<hipStream_t>(stream);
   TrainEdgeArgs a{};
   a.d_agg = d_agg; a.norm_factor = norm_factor;
-  { const int rc = mlp_backward(s, H, MODE_GCL, g, m, x, g->n_edges, a, out, ts, sd, false, z2); if (rc != DSBDD_OK) return rc; }
-  const int N = (int)g->n_nodes;
-  hipLaunchKernelGGL(edge_to_node3_kernel, dim3((N + 3) / 4), dim3(kThreads), 0, s, (const float*)ts.gd,
-                     (const float*)nullptr, (const float*)nullptr, x, g->ecol, g->row_ptr, g->deg, g->rev,
-                     (int)g->n_edges, N, d_x, 0);
-  HIP_TRY(hipGetLastError());
-  return DSBDD_OK;
+  MlpBwdOpts o;
+  o.side = sd; o.z2 = z2;
+  RC_TRY(mlp_backward(s, H, MODE_GCL, g, m, x, g->n_edges, a, out, ts, o));
+  return radial_backward_impl(s, g, x, ts.gd, d_x);
 }
 
 static int coord_forward_impl(void* stream, int32_t H, const dsbdd_train_graph* g, const dsbdd_train_mlp* m, int32_t n_mlp,
@@ -321,18 +301,8 @@ static int coord_forward_impl(void* stream, int32_t H, const dsbdd_train_graph* 
   // CU: twice as many, half as long work items), one coordinate sum per MLP, added by coord_update_kernel
   ea.pass_split = n_mlp == 2 ? 1 : 0;
   HIP_TRY(launch_edge_plain(H, s, MODE_COORD, ea, g->n_edges));
-  hipLaunchKernelGGL(coord_update_kernel, dim3((unsigned)((3 * n_upd + 255) / 256)), dim3(256), 0, s, x_out,
-                     (const float*)ts.xagg, (const float*)ts.xagg_head, ea.pass_split ? 2 : 1, ea.xagg_stride, ea.xhead_stride, g->row_ptr,
-                     g->deg, (int)(3 * n_upd), (int)((g->n_edges + 31) / 32 + 1), 5);
-  HIP_TRY(hipGetLastError());
-  return DSBDD_OK;
-}
-
-int dsbdd_train_coord_forward(void* stream, int32_t H, const dsbdd_train_graph* g, const dsbdd_train_mlp* m, int32_t n_mlp,
-                              const float* x, const float* mean, int64_t n_upd, float norm_constant, float coords_range,
-                              int32_t use_tanh, float norm_factor, float* x_out, void* scratch, size_t scratch_bytes) {
-  return coord_forward_impl(stream, H, g, m, n_mlp, x, mean, n_upd, norm_constant, coords_range, use_tanh, norm_factor, x_out,
-                            scratch, scratch_bytes, nullptr, 0);
+  return launch_1d(coord_update_kernel, (size_t)(3 * n_upd), s, x_out, ts.xagg, ts.xagg_head, ea.pass_split ? 2 : 1, ea.xagg_stride,
+                   ea.xhead_stride, g->row_ptr, g->deg, (int)(3 * n_upd), (int)((g->n_edges + 31) / 32 + 1), 5);
 }
 
 static int coord_backward_impl(void* stream, int32_t H, const dsbdd_train_graph* g, const dsbdd_train_mlp* m, int32_t n_mlp,
@@ -367,9 +337,9 @@ static int coord_backward_impl(void* stream, int32_t H, const dsbdd_train_graph*
     dsbdd_train_mlp mq = m[q];
     mq.head = m[0].head;                      // the output layer is shared by both MLPs (egnn_new.py:78,85,91)
     hipStream_t sq = two && q == 1 ? sd->co : s;
-    { const int rc = mlp_backward(sq, H, MODE_COORD, g, &mq, x, e_upd, a, out + q, tq, sd, true, z2 ? z2 + (size_t)q * z2_stride : nullptr,
-                                  two && q == 1 ? 1 : 0);
-      if (rc != DSBDD_OK) return rc; }
+    MlpBwdOpts o;
+    o.side = sd; o.already_linked = true; o.z2 = z2 ? z2 + (size_t)q * z2_stride : nullptr; o.scratch_set = two && q == 1 ? 1 : 0;
+    RC_TRY(mlp_backward(sq, H, MODE_COORD, g, &mq, x, e_upd, a, out + q, tq, o));
     if (sq != s) HIP_TRY(sd->link(sq, s));
     hipLaunchKernelGGL(edge_to_node3_kernel, dim3((N + 3) / 4), dim3(kThreads), 0, s, (const float*)tq.gd,
                        (const float*)tq.gxr, (const float*)tq.gxc, x, g->ecol, g->row_ptr, g->deg, g->rev, (int)e_upd, N,
@@ -383,48 +353,3 @@ static int coord_backward_impl(void* stream, int32_t H, const dsbdd_train_graph*
   }
   return DSBDD_OK;
 }
-
-int dsbdd_train_gcl_backward(void* stream, int32_t H, const dsbdd_train_graph* g, const dsbdd_train_mlp* m, const float* x,
-                             float norm_factor, const float* d_agg, const dsbdd_train_mlp_grad* out, float* d_x,
-                             void* scratch, size_t scratch_bytes) {
-  return gcl_backward_impl(stream, H, g, m, x, norm_factor, d_agg, out, d_x, scratch, scratch_bytes, nullptr);
-}
-
-int dsbdd_train_coord_backward(void* stream, int32_t H, const dsbdd_train_graph* g, const dsbdd_train_mlp* m, int32_t n_mlp,
-                               const float* x, const float* mean, int64_t n_upd, int64_t e_upd, float norm_constant,
-                               float coords_range, int32_t use_tanh, float norm_factor, const float* d_xout,
-                               const dsbdd_train_mlp_grad* out, float* d_x, float* d_mean, void* scratch,
-                               size_t scratch_bytes) {
-  return coord_backward_impl(stream, H, g, m, n_mlp, x, mean, n_upd, e_upd, norm_constant, coords_range, use_tanh, norm_factor,
-                             d_xout, out, d_x, d_mean, scratch, scratch_bytes, nullptr);
-}
-
-int dsbdd_train_radial_backward(void* stream, const dsbdd_train_graph* g, const float* x, const float* gd, float* d_x) {
-  StreamDevice stream_device_(stream);
-  if (!graph_ok(g) || !g->rev || !x || !gd || !d_x) return fail(DSBDD_ERR_ARG, "bad argument");
-  const int N = (int)g->n_nodes;
-  hipLaunchKernelGGL(edge_to_node3_kernel, dim3((N + 3) / 4), dim3(kThreads), 0, static_cast<hipStream_t>(stream), gd,
-                     (const float*)nullptr, (const float*)nullptr, x, g->ecol, g->row_ptr, g->deg, g->rev, (int)g->n_edges,
-                     N, d_x, 0);
-  HIP_TRY(hipGetLastError());
-  return DSBDD_OK;
-}
-
-int dsbdd_train_wgrad(void* stream, const float* A, int32_t lda, const float* B, int32_t ldb, int64_t K, int32_t M,
-                      int32_t N, float* C, void* scratch, size_t scratch_bytes) {
-  StreamDevice stream_device_(stream);
-  if (!A || !B || !C || K < 1 || M < 1 || N < 1 || lda < M || ldb < N || !scratch) return fail(DSBDD_ERR_ARG, "bad argument");
-  if (wgrad_plan(K, M, N).floats * 4 > scratch_bytes) return fail(DSBDD_ERR_CAPACITY, "scratch too small");
-  return wgrad_impl(static_cast<hipStream_t>(stream), A, lda, B, ldb, K, M, N, C, static_cast<float*>(scratch), scratch_bytes / 4);
-}
-
-int dsbdd_train_colsum(void* stream, const float* A, int32_t lda, int64_t M, int32_t N, float* out, void* scratch,
-                       size_t scratch_bytes) {
-  StreamDevice stream_device_(stream);
-  if (!A || !out || M < 1 || N < 1 || lda < N || !scratch) return fail(DSBDD_ERR_ARG, "bad argument");
-  if ((size_t)((M + 31) / 32) * N * 4 > scratch_bytes) return fail(DSBDD_ERR_CAPACITY, "scratch too small");
-  HIP_TRY(reduce_parts(static_cast<hipStream_t>(stream), A, (int)M, (size_t)lda, N, out, static_cast<float*>(scratch)));
-  return DSBDD_OK;
-}
-
-}  // extern "C"
