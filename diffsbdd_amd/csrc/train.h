@@ -888,9 +888,11 @@ __global__ __launch_bounds__(kThreads) void sample_edge_sum3_kernel(const float*
   if (t < 3) out[3 * b + t] = red[t][0];
 }
 
-// out[g][i] = sum over the parts p in [g gs, min((g + 1) gs, n_part)) of part[p * stride + i], i < width; fixed order
+// out[g][i] = sum over the parts p in [g gs, min((g + 1) gs, n_part)) of part[p * stride + i], i < width; fixed order.
+// acc: out[g][i] += that sum instead -- the complete sum first, the old value added last with one rounding (the
+// accumulating store of a parameter gradient, dsbdd_train_net_backward_acc)
 __global__ void partial_reduce_kernel(const float* part, int n_part, size_t stride, int width, int gs, float* out,
-                                      size_t out_stride) {
+                                      size_t out_stride, int acc) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= width) return;
   const int g = blockIdx.y;
@@ -904,7 +906,9 @@ __global__ void partial_reduce_kernel(const float* part, int n_part, size_t stri
     a3 += part[(size_t)(pi + 3) * stride + i];
   }
   for (; pi < p1; ++pi) a0 += part[(size_t)pi * stride + i];
-  out[(size_t)g * out_stride + i] = (a0 + a1) + (a2 + a3);
+  const float v = (a0 + a1) + (a2 + a3);
+  float* o = out + (size_t)g * out_stride + i;
+  *o = acc ? __fadd_rn(*o, v) : v;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -113,10 +113,13 @@ size_t dsbdd_train_net_workspace_bytes(const dsbdd_train_net* n, const dsbdd_tra
   return tn_carve_ws(nullptr, tn_dims(n->cfg, g), n->store_z2).bytes;
 }
 
-int dsbdd_train_net_forward(dsbdd_train_net* net, void* stream, const dsbdd_train_graph* g, const float* const* params,
-                            void* pack, size_t pack_bytes, void* ws, size_t ws_bytes, const float* xh_lig,
-                            const float* xh_pocket, const float* t, int64_t t_count, int32_t zero_nan, float* eps_lig,
-                            float* eps_pocket, int32_t* status) {
+// pack_is_current != 0: the caller holds the pack over an accumulation window -- no re-layout; DSBDD_ERR_STATE unless the
+// pack buffer was last written for exactly these parameter tensors
+int dsbdd_train_net_forward_held(dsbdd_train_net* net, void* stream, const dsbdd_train_graph* g, const float* const* params,
+                                 void* pack, size_t pack_bytes, void* ws, size_t ws_bytes, const float* xh_lig,
+                                 const float* xh_pocket, const float* t, int64_t t_count, int32_t zero_nan, float* eps_lig,
+                                 float* eps_pocket, int32_t* status, int32_t pack_is_current) {
+  if (!net) return fail(DSBDD_ERR_ARG, "null handle");
   StreamDevice stream_device_(stream);
   if (!net || !graph_ok(g) || !params || !pack || !ws || !t || !status || t_count < 1 || (g->n_lig > 0 && (!xh_lig || !eps_lig)) ||
       (g->n_nodes > g->n_lig && (!xh_pocket || !eps_pocket)))
@@ -125,13 +128,22 @@ int dsbdd_train_net_forward(dsbdd_train_net* net, void* stream, const dsbdd_trai
   TrainForward f(net, stream, g, params, pack, ws);
   if (f.pk.bytes > pack_bytes) return fail(DSBDD_ERR_CAPACITY, "pack buffer too small (dsbdd_train_net_pack_bytes)");
   if (f.w.bytes > ws_bytes) return fail(DSBDD_ERR_CAPACITY, "workspace too small (dsbdd_train_net_workspace_bytes)");
-  return f.run(xh_lig, xh_pocket, t, t_count, zero_nan, eps_lig, eps_pocket, status);
+  return f.run(xh_lig, xh_pocket, t, t_count, zero_nan, eps_lig, eps_pocket, status, pack_is_current != 0);
+}
+int dsbdd_train_net_forward(dsbdd_train_net* net, void* stream, const dsbdd_train_graph* g, const float* const* params,
+                            void* pack, size_t pack_bytes, void* ws, size_t ws_bytes, const float* xh_lig,
+                            const float* xh_pocket, const float* t, int64_t t_count, int32_t zero_nan, float* eps_lig,
+                            float* eps_pocket, int32_t* status) {
+  if (!net) return fail(DSBDD_ERR_ARG, "bad argument");
+  return dsbdd_train_net_forward_held(net, stream, g, params, pack, pack_bytes, ws, ws_bytes, xh_lig, xh_pocket, t, t_count,
+                                      zero_nan, eps_lig, eps_pocket, status, 0);
 }
 
-int dsbdd_train_net_backward(dsbdd_train_net* net, void* stream, const dsbdd_train_graph* g, const float* const* params,
-                             float* const* grads, void* pack, size_t pack_bytes, void* ws, size_t ws_bytes,
-                             int64_t e_upd, const float* d_eps_lig, const float* d_eps_pocket, float* d_xh_lig,
-                             float* d_xh_pocket) {
+// accumulate [param_count] or null (null: every gradient is overwritten)
+static int tn_backward(dsbdd_train_net* net, void* stream, const dsbdd_train_graph* g, const float* const* params,
+                       float* const* grads, const uint8_t* accumulate, void* pack, size_t pack_bytes, void* ws,
+                       size_t ws_bytes, int64_t e_upd, const float* d_eps_lig, const float* d_eps_pocket, float* d_xh_lig,
+                       float* d_xh_pocket) {
   StreamDevice stream_device_(stream);      // (makes the stream's device current: the side streams are created on it)
   if (!net || !graph_ok(g) || !g->rev || !params || !grads || !pack || !ws) return fail(DSBDD_ERR_ARG, "bad argument");
   for (int i = 0; i < net->ix.n; ++i)
@@ -139,9 +151,25 @@ int dsbdd_train_net_backward(dsbdd_train_net* net, void* stream, const dsbdd_tra
   if ((g->n_lig > 0 && !d_eps_lig) || (g->n_nodes > g->n_lig && !d_eps_pocket)) return fail(DSBDD_ERR_ARG, "null output gradient");
   if (net->cfg.update_pocket_coords) e_upd = g->n_edges;      // (else: row_ptr[n_lig], the edge prefix of the ligand rows, a host value)
   if (e_upd < 0 || e_upd > g->n_edges) return fail(DSBDD_ERR_ARG, "e_upd out of range");
-  TrainBackward f(net, stream, g, params, grads, pack, ws, e_upd, d_xh_lig || d_xh_pocket);
+  TrainBackward f(net, stream, g, params, grads, accumulate, pack, ws, e_upd, d_xh_lig || d_xh_pocket);
   if (f.pk.bytes > pack_bytes || f.w.bytes > ws_bytes) return fail(DSBDD_ERR_CAPACITY, "buffer too small");
   return f.run(d_eps_lig, d_eps_pocket, d_xh_lig, d_xh_pocket);
+}
+int dsbdd_train_net_backward(dsbdd_train_net* net, void* stream, const dsbdd_train_graph* g, const float* const* params,
+                             float* const* grads, void* pack, size_t pack_bytes, void* ws, size_t ws_bytes,
+                             int64_t e_upd, const float* d_eps_lig, const float* d_eps_pocket, float* d_xh_lig,
+                             float* d_xh_pocket) {
+  return tn_backward(net, stream, g, params, grads, nullptr, pack, pack_bytes, ws, ws_bytes, e_upd, d_eps_lig, d_eps_pocket,
+                     d_xh_lig, d_xh_pocket);
+}
+int dsbdd_train_net_backward_acc(dsbdd_train_net* net, void* stream, const dsbdd_train_graph* g, const float* const* params,
+                                 float* const* grads, const uint8_t* accumulate, void* pack, size_t pack_bytes, void* ws,
+                                 size_t ws_bytes, int64_t e_upd, const float* d_eps_lig, const float* d_eps_pocket,
+                                 float* d_xh_lig, float* d_xh_pocket) {
+  if (!net) return fail(DSBDD_ERR_ARG, "null handle");
+  if (!accumulate) return fail(DSBDD_ERR_ARG, "null accumulate table (one flag per parameter slot)");
+  return tn_backward(net, stream, g, params, grads, accumulate, pack, pack_bytes, ws, ws_bytes, e_upd, d_eps_lig, d_eps_pocket,
+                     d_xh_lig, d_xh_pocket);
 }
 
 // ---- loss terms (loss_head.h) -------------------------------------------------------------------------------------------

@@ -3,20 +3,21 @@
 // dsbdd_train_* entry points over them are in train_api.h.
 #pragma once
 
-// out[i] = sum_p part[p * stride + i] in a fixed order (two levels above 64 parts); tmp: ceil(n_part / 32) * width floats
+// out[i] = sum_p part[p * stride + i] in a fixed order (two levels above 64 parts); tmp: ceil(n_part / 32) * width floats.
+// acc: out[i] += that sum, folded into the LAST level's store (the accumulating parameter gradients of train_net.h)
 static hipError_t reduce_parts(hipStream_t s, const float* part, int n_part, size_t stride, int width, float* out,
-                               float* tmp) {
+                               float* tmp, bool acc = false) {
   const int bx = (width + 255) / 256;
   if (n_part <= 96) {
     hipLaunchKernelGGL(partial_reduce_kernel, dim3(bx, 1), dim3(256), 0, s, part, n_part, stride, width,
-                       n_part > 0 ? n_part : 1, out, (size_t)0);
+                       n_part > 0 ? n_part : 1, out, (size_t)0, acc ? 1 : 0);
     return hipGetLastError();
   }
   const int groups = (n_part + 31) / 32;
   hipLaunchKernelGGL(partial_reduce_kernel, dim3(bx, groups), dim3(256), 0, s, part, n_part, stride, width, 32, tmp,
-                     (size_t)width);
+                     (size_t)width, 0);
   hipLaunchKernelGGL(partial_reduce_kernel, dim3(bx, 1), dim3(256), 0, s, (const float*)tmp, groups, (size_t)width,
-                     width, groups, out, (size_t)0);
+                     width, groups, out, (size_t)0, acc ? 1 : 0);
   return hipGetLastError();
 }
 
@@ -55,13 +56,13 @@ static size_t wgrad_floats_upto(int64_t K_max, int64_t M, int64_t N) {
 }
 
 static int wgrad_impl(hipStream_t s, const float* A, int lda, const float* B, int ldb, int64_t K, int M, int N, float* C,
-                      float* scratch, size_t scratch_floats) {
+                      float* scratch, size_t scratch_floats, bool acc = false) {
   const WgradPlan pl = wgrad_plan(K, M, N);
   if (pl.floats > scratch_floats) return fail(DSBDD_ERR_CAPACITY, "weight-gradient scratch too small for this plan");
   WgradArgs a{A, lda, B, ldb, (int)K, M, N, scratch, pl.kc};
   hipLaunchKernelGGL(wgrad_kernel, dim3((M + 127) / 128, (N + 127) / 128, pl.chunks), dim3(kThreads), 0, s, a);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(reduce_parts(s, scratch, pl.chunks, (size_t)M * N, M * N, C, scratch + (size_t)pl.chunks * M * N));
+  HIP_TRY(reduce_parts(s, scratch, pl.chunks, (size_t)M * N, M * N, C, scratch + (size_t)pl.chunks * M * N, acc));
   return DSBDD_OK;
 }
 
@@ -179,6 +180,7 @@ struct MlpBwdOpts {
   bool already_linked = false;    // the caller joined / forked the side streams itself (coordinate stage)
   const float* z2 = nullptr;      // the second-layer pre-activations the forward pass kept, or null: recompute (kernel A)
   int scratch_set = 0;            // which of the two scratch sets `ts` is (the W2 gradient's event)
+  bool acc_w2 = false;            // out->d_W2 += the gradient instead of = (dsbdd_train_net_backward_acc)
 };
 static int mlp_backward(hipStream_t s, int H, int mode, const dsbdd_train_graph* g, const dsbdd_train_mlp* m, const float* x,
                         int64_t E, TrainEdgeArgs a, const dsbdd_train_mlp_grad* out, const TrainScratch& ts,
@@ -201,7 +203,7 @@ static int mlp_backward(hipStream_t s, int H, int mode, const dsbdd_train_graph*
   // dW2[f][i] = sum_e dz2[e][f] a1[e][i]
   if (side_w) HIP_TRY(sd->link(s, sd->wg));
   if (late_join) { HIP_TRY(sd->link(sd->wg, s)); HIP_TRY(sd->link(sd->co, s)); }
-  RC_TRY(wgrad_impl(side_w ? sd->wg : s, ts.dz2, H, ts.a1, H, E, H, H, out->d_W2, ts.wg, ts.wg_floats));
+  RC_TRY(wgrad_impl(side_w ? sd->wg : s, ts.dz2, H, ts.a1, H, E, H, H, out->d_W2, ts.wg, ts.wg_floats, o.acc_w2));
   if (side_w) { HIP_TRY(hipEventRecord(sd->w2_done[o.scratch_set], sd->wg)); sd->w2_valid[o.scratch_set] = true; }
   // B: dz1, partial first-layer vectors, per-edge distance gradients
   a.Bmat = m->W2; a.dz_in = ts.dz2; a.dz_out = ts.dz1; a.part = ts.partB;
@@ -256,7 +258,8 @@ static int gcl_forward_impl(void* stream, int32_t H, const dsbdd_train_graph* g,
 
 static int gcl_backward_impl(void* stream, int32_t H, const dsbdd_train_graph* g, const dsbdd_train_mlp* m, const float* x,
                              float norm_factor, const float* d_agg, const dsbdd_train_mlp_grad* out, float* d_x,
-                             void* scratch, size_t scratch_bytes, TrainSide* sd, const float* z2 = nullptr) {
+                             void* scratch, size_t scratch_bytes, TrainSide* sd, const float* z2 = nullptr,
+                             bool acc_w2 = false) {
   StreamDevice stream_device_(stream);
   if (!hidden_nf_ok(H) || !graph_ok(g) || !g->rev || !mlp_ok(m) || !x || !d_agg || !out || !out->dP || !out->dQ ||
       !out->d_vec || !out->d_W2 || !out->gd0 || (out->ldo & 3) || !d_x || !scratch)
@@ -267,7 +270,7 @@ static int gcl_backward_impl(void* stream, int32_t H, const dsbdd_train_graph* g
   TrainEdgeArgs a{};
   a.d_agg = d_agg; a.norm_factor = norm_factor;
   MlpBwdOpts o;
-  o.side = sd; o.z2 = z2;
+  o.side = sd; o.z2 = z2; o.acc_w2 = acc_w2;
   RC_TRY(mlp_backward(s, H, MODE_GCL, g, m, x, g->n_edges, a, out, ts, o));
   return radial_backward_impl(s, g, x, ts.gd, d_x);
 }
@@ -309,7 +312,8 @@ static int coord_backward_impl(void* stream, int32_t H, const dsbdd_train_graph*
                                const float* x, const float* mean, int64_t n_upd, int64_t e_upd, float norm_constant,
                                float coords_range, int32_t use_tanh, float norm_factor, const float* d_xout,
                                const dsbdd_train_mlp_grad* out, float* d_x, float* d_mean, void* scratch,
-                               size_t scratch_bytes, TrainSide* sd, const float* z2 = nullptr, size_t z2_stride = 0) {
+                               size_t scratch_bytes, TrainSide* sd, const float* z2 = nullptr, size_t z2_stride = 0,
+                               const bool* acc_w2 = nullptr) {      // acc_w2 [n_mlp]: out[q].d_W2 accumulates
   StreamDevice stream_device_(stream);
   if (!hidden_nf_ok(H) || !graph_ok(g) || !g->rev || n_mlp < 1 || n_mlp > 2 || !mlp_ok(m) ||
       (n_mlp == 2 && (!mlp_ok(m + 1) || !mean || !d_mean)) || !m->head || !x || !d_xout || !out || !d_x || n_upd < 0 ||
@@ -339,6 +343,7 @@ static int coord_backward_impl(void* stream, int32_t H, const dsbdd_train_graph*
     hipStream_t sq = two && q == 1 ? sd->co : s;
     MlpBwdOpts o;
     o.side = sd; o.already_linked = true; o.z2 = z2 ? z2 + (size_t)q * z2_stride : nullptr; o.scratch_set = two && q == 1 ? 1 : 0;
+    o.acc_w2 = acc_w2 && acc_w2[q];
     RC_TRY(mlp_backward(sq, H, MODE_COORD, g, &mq, x, e_upd, a, out + q, tq, o));
     if (sq != s) HIP_TRY(sd->link(sq, s));
     hipLaunchKernelGGL(edge_to_node3_kernel, dim3((N + 3) / 4), dim3(kThreads), 0, s, (const float*)tq.gd,

@@ -13,12 +13,16 @@ struct TnTabDesc {        // tab[ty][o] = b1[o] + sum_e emb[ty][e] W1[o][col0 + 
   const float* W1; int ld; int col0; const float* b1; const float* emb; int enf; float* tab; int H;
 };
 struct TnUnpackDesc {     // one edge MLP's first layer: d W1 [H][ld], d b1 [H], d emb partial [3][enf]
-  float* dW1; int ld; float* db1; float* demb_part;
+  float* dW1; int ld; float* db1; float* demb_part;      // (demb_part is scratch: always overwritten)
   const float* dWpq; int dq_off;      // d W_pq rows [0, H) = P part, rows [dq_off, dq_off + H) = Q part; [.][H]
   const float* d_vec;                 // [8][H]: d_wd, d_wd0, d_tab[0..2], ...
   const float* W1; const float* emb; int enf; int H;
+  int acc_w, acc_b;                   // d W1 / d b1 += instead of =
 };
-struct TnCopyDesc { float* dst; const float* a; const float* b; int n; };    // dst[i] = a[i] (+ b[i])
+struct TnCopyDesc { float* dst; const float* a; const float* b; int n; int acc; };    // dst[i] (+)= a[i] (+ b[i])
+// The accumulating stores (dsbdd_train_net_backward_acc): the complete new gradient `v` first, the old value added last
+// with ONE rounding; __fadd_rn keeps the compiler from contracting the add into the multiply that produced `v`.
+__device__ __forceinline__ void tn_store(float* dst, float v, int acc) { *dst = acc ? __fadd_rn(*dst, v) : v; }
 // The gradient-assembly tables travel BY VALUE in the kernel arguments (<= 4 KB): they depend on the per-call workspace,
 // and a per-step host-to-device copy of a table would need either pinned memory or a synchronisation to be safe.
 constexpr int kTnUnpackPerLaunch = 16, kTnCopyPerLaunch = 64;
@@ -71,11 +75,11 @@ __global__ void tn_unpack_kernel(const TnUnpackTable tab) {
       v = 0.f;
       for (int ty = 0; ty < 3; ++ty) v = fmaf(d.d_vec[(2 + ty) * H + o], d.emb[ty * d.enf + e], v);
     }
-    d.dW1[i] = v;
+    tn_store(d.dW1 + i, v, d.acc_w);
   }
   if (blockIdx.x == 0) {
     for (int o = threadIdx.x; o < H; o += blockDim.x)
-      d.db1[o] = (d.d_vec[2 * H + o] + d.d_vec[3 * H + o]) + d.d_vec[4 * H + o];
+      tn_store(d.db1 + o, (d.d_vec[2 * H + o] + d.d_vec[3 * H + o]) + d.d_vec[4 * H + o], d.acc_b);
     if (d.demb_part)      // d emb[ty][e] = sum_o d_tab[ty][o] W1[o][2H + 2 + e], one thread per entry, fixed order
       for (int i = threadIdx.x; i < 3 * d.enf; i += blockDim.x) {
         const int ty = i / d.enf, e = i % d.enf;
@@ -89,16 +93,16 @@ __global__ void tn_unpack_kernel(const TnUnpackTable tab) {
 __global__ void tn_copy_kernel(const TnCopyTable tab) {
   const TnCopyDesc& d = tab.d[blockIdx.y];
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < d.n; i += gridDim.x * blockDim.x)
-    d.dst[i] = d.b ? d.a[i] + d.b[i] : d.a[i];
+    tn_store(d.dst + i, d.b ? d.a[i] + d.b[i] : d.a[i], d.acc);
 }
 
 // out[i] = sum over k < n_part of part[k * stride + i] in order (the edge-type embedding's gradient over the MLPs)
-__global__ void tn_sum_parts_kernel(const float* part, int n_part, int stride, int n, float* out) {
+__global__ void tn_sum_parts_kernel(const float* part, int n_part, int stride, int n, float* out, int acc) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float v = 0.f;
   for (int k = 0; k < n_part; ++k) v += part[(size_t)k * stride + i];
-  out[i] = v;
+  tn_store(out + i, v, acc);
 }
 
 // dynamics.py:89-93,100: x = cat(ligand, pocket coordinates), the feature parts as contiguous matrices

@@ -233,14 +233,15 @@ static int tn_lin(hipStream_t s, const float* x, int lda, int K, const float* WT
   HIP_TRY(nl(s, x, lda, K, x2, lda2, K2, WT, ldT, bias, R, ldr, y, ldc, M, Nout, 0));
   return DSBDD_OK;
 }
+// (acc: dW / db += the gradient; a gradient of zeros then adds nothing instead of clearing)
 static int tn_wgrad(hipStream_t s, const float* dy, int ldy, const float* x, int ldx, int64_t K, int M, int Nn, float* dW,
-                    const TnWs& w) {
-  if (K <= 0) { HIP_TRY(hipMemsetAsync(dW, 0, (size_t)M * Nn * 4, s)); return DSBDD_OK; }
-  return wgrad_impl(s, dy, ldy, x, ldx, K, M, Nn, dW, w.wg, w.wg_floats);
+                    const TnWs& w, bool acc = false) {
+  if (K <= 0) { if (!acc) HIP_TRY(hipMemsetAsync(dW, 0, (size_t)M * Nn * 4, s)); return DSBDD_OK; }
+  return wgrad_impl(s, dy, ldy, x, ldx, K, M, Nn, dW, w.wg, w.wg_floats, acc);
 }
-static int tn_colsum(hipStream_t s, const float* dy, int ldy, int64_t M, int Nn, float* db, const TnWs& w) {
-  if (M <= 0) { HIP_TRY(hipMemsetAsync(db, 0, (size_t)Nn * 4, s)); return DSBDD_OK; }
-  HIP_TRY(reduce_parts(s, dy, (int)M, (size_t)ldy, Nn, db, w.colscr));
+static int tn_colsum(hipStream_t s, const float* dy, int ldy, int64_t M, int Nn, float* db, const TnWs& w, bool acc = false) {
+  if (M <= 0) { if (!acc) HIP_TRY(hipMemsetAsync(db, 0, (size_t)Nn * 4, s)); return DSBDD_OK; }
+  HIP_TRY(reduce_parts(s, dy, (int)M, (size_t)ldy, Nn, db, w.colscr, acc));
   return DSBDD_OK;
 }
 
@@ -267,15 +268,19 @@ static void tn_coord_mlps(const TnParamIndex& ix, const float* const* P, const T
     mm[q] = tn_mlp(pq4, 2 * H * q, 2 * H * M, H, pk.eqm[b * M + q], P[e.mlp[q].l2_w], P[e.mlp[q].l2_b], P[e.head_w], nullptr);
 }
 
+// the pack buffer holds the re-laid-out copies of exactly these tensors (their VALUES are the caller's business)
+static bool tn_pack_matches(const dsbdd_train_net* net, const float* const* P, const char* pack_base) {
+  bool same = net->last_pack == pack_base && (int)net->last_params.size() == net->ix.n;
+  for (int i = 0; same && i < net->ix.n; ++i) same = net->last_params[i] == P[i];
+  return same;
+}
 // descriptor tables of the weight re-layout; uploaded when the parameter / pack pointers changed
 static int tn_prepare_pack(dsbdd_train_net* net, hipStream_t s, const float* const* P, char* pack_base, const TnPack& pk) {
   const dsbdd_config& c = net->cfg;
   const TnParamIndex& ix = net->ix;
   const int H = c.hidden_nf, L = c.n_layers, S = c.inv_sublayers;
   const int M = ix.n_mlp, enf = c.edge_embedding_dim > 0 ? c.edge_embedding_dim : 0, ld1 = 2 * H + 2 + enf;
-  bool same = net->last_pack == pack_base && (int)net->last_params.size() == ix.n;
-  for (int i = 0; same && i < ix.n; ++i) same = net->last_params[i] == P[i];
-  if (!same) {
+  if (!tn_pack_matches(net, P, pack_base)) {
     std::vector<TnPackDesc> pd;
     std::vector<TnTabDesc> td;
     auto lin = [&](TnLinIx i, const TnLin& l) { pd.push_back(TnPackDesc{P[i.w], l.in, l.out, l.in, l.WT, l.ldT, l.ldT, l.Wp, l.ldP}); };
@@ -417,9 +422,13 @@ struct TrainForward : TrainCall {
                      n_l, n_p, eps_lig, eps_pocket);
   }
 
+  // pack_is_current: the pack buffer already holds these weights (an accumulation window: they cannot have changed
+  // since the window's first forward) -- the two re-layout launches are skipped
   int run(const float* xh_lig, const float* xh_pocket, const float* t, int64_t t_count, int32_t zero_nan, float* eps_lig,
-          float* eps_pocket, int32_t* status) {
-    RC_TRY(tn_prepare_pack(net, s, P, pack_base, pk));
+          float* eps_pocket, int32_t* status, bool pack_is_current = false) {
+    if (pack_is_current && !tn_pack_matches(net, P, pack_base))
+      return fail(DSBDD_ERR_STATE, "the pack buffer does not hold these parameter tensors");
+    if (!pack_is_current) RC_TRY(tn_prepare_pack(net, s, P, pack_base, pk));
     RC_TRY(inputs_and_encoders(xh_lig, xh_pocket, t, t_count));
     for (int b = 0; b < d.L; ++b) {
       if (M == 2) RC_TRY(sample_mean_impl(s, w.x[b], g, w.mean[b]));      // the cross product is taken about it
@@ -434,8 +443,12 @@ struct TrainForward : TrainCall {
 // streams (TrainSide, train_blocks.h) the node-level weight gradients of the blocks go to `sw` and their bias gradients
 // to `sb`, forked from `s` where their operands are complete.  Parameter gradients go straight to G[...]; what the
 // factorised first layers produce in pieces is noted in `ud` / `cd` and assembled at the end.
+// Accumulation (dsbdd_train_net_backward_acc): slot i with A[i] != 0 receives G[i] += g_i, folded into the LAST store of
+// that gradient -- the final level of reduce_parts, tn_unpack / tn_copy / tn_sum_parts -- on the stream where the
+// overwriting store runs; the scratch in between (dWpq, d_vec, demb_part) is overwritten per call either way.
 struct TrainBackward : TrainCall {
   float* const* const G;
+  const uint8_t* const A;             // per parameter slot: accumulate (null: overwrite everything)
   const int64_t e_upd;                // the edge prefix of the rows whose coordinates move
   const bool want_in;                 // the caller asked for input gradients
   TrainSide* sd = nullptr;
@@ -448,19 +461,20 @@ struct TrainBackward : TrainCall {
   std::vector<TnCopyDesc> cd;
 
   TrainBackward(dsbdd_train_net* net_, void* stream, const dsbdd_train_graph* g_, const float* const* params, float* const* grads,
-                void* pack, void* ws, int64_t e_upd_, bool want_in_)
-      : TrainCall(net_, stream, g_, params, pack, ws), G(grads), e_upd(e_upd_), want_in(want_in_), sw(s), sb(s),
+                const uint8_t* accumulate, void* pack, void* ws, int64_t e_upd_, bool want_in_)
+      : TrainCall(net_, stream, g_, params, pack, ws), G(grads), A(accumulate), e_upd(e_upd_), want_in(want_in_), sw(s), sb(s),
         emb(ix.emb_tab >= 0 ? P[ix.emb_tab] : nullptr), d_h(w.d_h[0]), d_h_next(w.d_h[1]), d_x(w.d_x[0]), d_x_next(w.d_x[1]) {}
 
+  bool acc(int slot) const { return A && A[slot]; }
   float* vec_of(int k) const { return w.d_vec + (size_t)k * 8 * H; }      // [8][H]: d_wd, d_wd0, d_tab[0..2], d_b2, d head, d head_b
   int fork_w() { if (sw != s) HIP_TRY(sd->link(s, sd->wg)); return DSBDD_OK; }
   int fork_b() { if (sb != s) HIP_TRY(sd->link(s, sd->co)); return DSBDD_OK; }
   // d W = dy^T x and d b = the column sums of dy, for y = x W^T + b over `rows` rows.  beside: on the side streams, forked here
   int lin_grads(bool beside, const float* dy, int ldy, const float* x, int ldx, int64_t rows, int out, int in, TnLinIx i) {
     if (beside) RC_TRY(fork_w());
-    RC_TRY(tn_wgrad(beside ? sw : s, dy, ldy, x, ldx, rows, out, in, G[i.w], w));
+    RC_TRY(tn_wgrad(beside ? sw : s, dy, ldy, x, ldx, rows, out, in, G[i.w], w, acc(i.w)));
     if (beside) RC_TRY(fork_b());
-    return tn_colsum(beside ? sb : s, dy, ldy, rows, out, G[i.b], w);
+    return tn_colsum(beside ? sb : s, dy, ldy, rows, out, G[i.b], w, acc(i.b));
   }
   int add_gd0(const float* gd) {      // the input distances d0 collect a gradient from every edge MLP
     if (!want_in || E <= 0) return DSBDD_OK;
@@ -469,8 +483,8 @@ struct TrainBackward : TrainCall {
   // notes the assembly of edge MLP k's first layer (d W1, d b1, its share of d emb) and the copy of d b2
   void edge_mlp_grads(int k, int l1_w, int l1_b, int l2_b, const float* dWpq) {
     ud.push_back(TnUnpackDesc{G[l1_w], 2 * H + d.A, G[l1_b], emb ? w.demb_part + (size_t)k * 3 * d.enf : nullptr, dWpq, H, vec_of(k),
-                              P[l1_w], emb, d.enf, H});
-    cd.push_back(TnCopyDesc{G[l2_b], vec_of(k) + 5 * H, nullptr, H});
+                              P[l1_w], emb, d.enf, H, acc(l1_w), acc(l1_b)});
+    cd.push_back(TnCopyDesc{G[l2_b], vec_of(k) + 5 * H, nullptr, H, acc(l2_b)});
   }
 
   // Reads dy [rows][lddy], x [rows][ldx] and m.z / m.act; writes both layers' gradients and, if asked, dx.  w.d_small is
@@ -517,7 +531,9 @@ struct TrainBackward : TrainCall {
     n_edge_mlps += M;
     float* dW4 = w.dWpq + (size_t)(d.G * 2 + b * 2 * M) * H * H;       // [2H M][H]
     dsbdd_train_mlp_grad og[2];
+    bool acc_w2[2] = {false, false};
     for (int q = 0; q < M; ++q) {
+      acc_w2[q] = acc(e.mlp[q].l2_w);
       og[q].dP = w.d_pq4 + 2 * H * q; og[q].dQ = w.d_pq4 + 2 * H * q + H; og[q].ldo = 2 * H * M;
       og[q].d_vec = vec_of(k0 + q); og[q].d_W2 = G[e.mlp[q].l2_w]; og[q].gd0 = w.gd0 + (size_t)q * d.E1;
     }
@@ -525,7 +541,7 @@ struct TrainBackward : TrainCall {
       if (want_in) HIP_TRY(hipMemsetAsync(w.gd0, 0, 2 * d.E1 * 4, s));
       RC_TRY(coord_backward_impl(s, H, g, mm, M, w.x[b], M == 2 ? w.mean[b] : nullptr, n_upd, e_upd, c.norm_constant, c.coords_range,
                                  c.use_tanh, c.normalization_factor, d_x, og, d_x_next, M == 2 ? w.d_mean : nullptr, w.scratch,
-                                 w.scratch_bytes, sd, w.z2c[b], d.E1 * H));
+                                 w.scratch_bytes, sd, w.z2c[b], d.E1 * H, acc_w2));
       for (int q = 0; q < M; ++q) RC_TRY(add_gd0(og[q].gd0));
       RC_TRY(launch_1d(tn_add_kernel, N3, s, d_x_next, d_x, N3));        // identity path x -> x_out
       if (M == 2) RC_TRY(launch_1d(tn_mean_bwd_kernel, N3, s, d_x_next, w.d_mean, g->node_batch, g->lig_off, g->poc_off, N));
@@ -534,17 +550,17 @@ struct TrainBackward : TrainCall {
       std::swap(d_h, d_h_next);
       RC_TRY(fork_w());
       RC_TRY(tn_wgrad(sw, w.d_pq4, 2 * H * M, w.h[(b + 1) * d.S], H, N, 2 * H * M, H, dW4, w));
-    } else {                             // no row moves: the stage is the identity on x, its parameters get zeros
+    } else {                             // no row moves: the stage is the identity on x, its parameters get zeros (accumulating: nothing)
       HIP_TRY(hipMemcpyAsync(d_x_next, d_x, (size_t)N * 12, hipMemcpyDeviceToDevice, s));
       HIP_TRY(hipMemsetAsync(dW4, 0, (size_t)2 * H * M * H * 4, s));
       for (int q = 0; q < M; ++q) {
         HIP_TRY(hipMemsetAsync(vec_of(k0 + q), 0, (size_t)8 * H * 4, s));
-        HIP_TRY(hipMemsetAsync(og[q].d_W2, 0, (size_t)H * H * 4, s));
+        if (!acc_w2[q]) HIP_TRY(hipMemsetAsync(og[q].d_W2, 0, (size_t)H * H * 4, s));
       }
     }
     std::swap(d_x, d_x_next);
     for (int q = 0; q < M; ++q) edge_mlp_grads(k0 + q, e.mlp[q].l1_w, e.mlp[q].l1_b, e.mlp[q].l2_b, dW4 + (size_t)q * 2 * H * H);
-    cd.push_back(TnCopyDesc{G[e.head_w], vec_of(k0) + 6 * H, M == 2 ? vec_of(k0 + 1) + 6 * H : nullptr, H});   // d w3 (shared head)
+    cd.push_back(TnCopyDesc{G[e.head_w], vec_of(k0) + 6 * H, M == 2 ? vec_of(k0 + 1) + 6 * H : nullptr, H, acc(e.head_w)});   // d w3 (shared head)
     return DSBDD_OK;
   }
 
@@ -573,7 +589,7 @@ struct TrainBackward : TrainCall {
     dsbdd_train_mlp_grad o{};
     o.dP = w.d_pq; o.dQ = w.d_pq + H; o.ldo = 2 * H; o.d_vec = vec_of(k); o.d_W2 = G[u.e2_w]; o.gd0 = w.gd0;
     if (want_in) HIP_TRY(hipMemsetAsync(w.gd0, 0, d.E1 * 4, s));
-    RC_TRY(gcl_backward_impl(s, H, g, &m, w.x[b], c.normalization_factor, w.d_agg, &o, w.d_xg, w.scratch, w.scratch_bytes, sd, w.z2[gi]));
+    RC_TRY(gcl_backward_impl(s, H, g, &m, w.x[b], c.normalization_factor, w.d_agg, &o, w.d_xg, w.scratch, w.scratch_bytes, sd, w.z2[gi], acc(u.e2_w)));
     RC_TRY(add_gd0(w.gd0));
     RC_TRY(launch_1d(tn_add_kernel, N3, s, d_x, w.d_xg, N3));
     RC_TRY(tn_lin(s, w.d_pq, 2 * H, 2 * H, pk.Wpq[gi], H, nullptr, d_h, H, d_h_next, H, N, H));
@@ -582,8 +598,8 @@ struct TrainBackward : TrainCall {
     RC_TRY(tn_wgrad(sw, w.d_pq, 2 * H, hin, H, N, 2 * H, H, dWpq, w));
     edge_mlp_grads(k, u.e1_w, u.e1_b, u.e2_b, dWpq);
     if (ix.att) {
-      cd.push_back(TnCopyDesc{G[u.att_w], vec_of(k) + 6 * H, nullptr, H});
-      cd.push_back(TnCopyDesc{G[u.att_b], vec_of(k) + 7 * H, nullptr, 1});
+      cd.push_back(TnCopyDesc{G[u.att_w], vec_of(k) + 6 * H, nullptr, H, acc(u.att_w)});
+      cd.push_back(TnCopyDesc{G[u.att_b], vec_of(k) + 7 * H, nullptr, 1, acc(u.att_b)});
     }
     return DSBDD_OK;
   }
@@ -616,7 +632,7 @@ struct TrainBackward : TrainCall {
     RC_TRY(launch_tables(tn_copy_kernel, 1, cd));
     if (emb) {
       hipLaunchKernelGGL(tn_sum_parts_kernel, dim3(1), dim3(256), 0, s, (const float*)w.demb_part, n_edge_mlps, 3 * d.enf, 3 * d.enf,
-                         G[ix.emb_tab]);
+                         G[ix.emb_tab], (int)acc(ix.emb_tab));
       HIP_TRY(hipGetLastError());
     }
     return DSBDD_OK;

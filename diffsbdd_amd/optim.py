@@ -81,6 +81,23 @@ def attach_queue(state_dict, items, n_clips=0):
     return state_dict
 
 
+class GradientBucket:
+    """ONE flat float32 device tensor that holds every parameter's gradient at the offsets of the optimiser's state
+    (`dsbdd_optim_state_offset`): the destination of the accumulating backward (train_net.accumulating), and the unit a
+    data-parallel all-reduce would work on.  `view(p)` is the region of parameter `p`, shaped like `p`."""
+
+    def __init__(self, params, offsets, elems, device):
+        self.flat = torch.zeros(elems, dtype=torch.float32, device=device)
+        self._views = {id(p): self.flat[o:o + p.numel()].view(p.shape) for p, o in zip(params, offsets)}
+        self._params = list(params)          # (keeps the ids above alive)
+
+    def __contains__(self, p):
+        return id(p) in self._views
+
+    def view(self, p):
+        return self._views[id(p)]
+
+
 class ClippedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-12, clip_grad=True):
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=True, **TORCH_GROUP_DEFAULTS)
@@ -123,6 +140,7 @@ class ClippedAdamW(torch.optim.Optimizer):
         self._grad_arr = (C.c_void_p * n)()
         self._step_arr = (C.c_int32 * n)()
         self.host_copies = 0           # device-to-host copies this object has made (clip_report / state_dict only)
+        self._bucket = None
 
     def __del__(self):
         try:
@@ -141,6 +159,14 @@ class ClippedAdamW(torch.optim.Optimizer):
         m, v, vmax = self._views(i)
         self.state[self._params[i]] = {"step": torch.tensor(float(self._steps[i])), "exp_avg": m, "exp_avg_sq": v,
                                        "max_exp_avg_sq": vmax}
+
+    def gradient_bucket(self):
+        """The optimiser's `GradientBucket`, created on first use and then kept: `step()` reads `p.grad` pointers as ever,
+        which are views of it after an accumulating backward."""
+        if self._bucket is None:
+            self._bucket = GradientBucket(self._params, self._offsets, int(self.lib.dsbdd_optim_state_elems(self._h)),
+                                          self.device)
+        return self._bucket
 
     def zero_grad(self, set_to_none=True):
         """`None` gradients are what "this tensor is skipped" hangs on; zeros would decay and count a step."""

@@ -5,17 +5,25 @@ torch_scatter: the processed-complex reader (dataset.py), `nll_from_terms` (ligh
 Lennard-Jones term (aux_loss.py), `ClippedAdamW` (optim.py) and checkpoints in the Lightning layout that
 `LigandGenerator.from_checkpoint` reads.
 
-Determinism: the shuffling is a function of (seed, epoch), the diffusion times of (seed, global_step) and the noise of
-(seed, sample, row, column, draw) with the draw counter set from global_step, so a resumed run IS the uninterrupted
-run, bit for bit.
+Determinism: the shuffling is a function of (seed, epoch), the diffusion times of (seed, micro_step) and the noise of
+(seed, sample, row, column, draw) with the draw counter set from micro_step (the number of micro-batches seen so far;
+equal to global_step without accumulation), so a resumed run IS the uninterrupted run, bit for bit.
+
+Gradient accumulation (`accumulate_grad_batches: k`, Lightning's semantics): the epoch's batches are walked in windows
+of k (the last one may be shorter and still steps), every micro-batch's loss is `nll.mean(0) / k`, clipping and AdamW
+run once per window and `global_step` counts optimiser steps.  With the HIP optimiser the window's gradients are summed
+by the backward kernels in the optimiser's flat gradient bucket (train_net.accumulating).  `gpus: N` with
+`accumulate_grad_batches: k` of the reference is reached on one GPU with `accumulate_grad_batches: N * k`.
 
 Out of scope (refused with a message): `virtual_nodes` (AppendVirtualNodes draws random virtual atoms per item),
-`augment_noise > 0` / `augment_rotation` (the reference raises NotImplementedError for them), `gpus > 1`.
+`augment_noise > 0` / `augment_rotation` (the reference raises NotImplementedError for them), `gpus > 1` (data-parallel
+ranks; the same effective batch is reached with `accumulate_grad_batches`).
 Accepted and ignored with one warning: `wandb_params`, `visualize_*`, the RDKit-based `eval_params` / `eval_epochs`.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import warnings
@@ -28,7 +36,7 @@ from .aux_loss import LennardJones, WeightSchedule
 from .dataset import ProcessedDataset, epoch_permutation
 from .optim import ClippedAdamW, ReferenceClipper, QUEUE_KEY
 
-DRAWS_PER_STEP = 16          # noise draws reserved per optimiser step (a training forward makes one or two)
+DRAWS_PER_STEP = 16          # noise draws reserved per micro-batch (a training forward makes one or two)
 _EVAL_DRAW_BASE = 1 << 40    # validation draws live apart from the training ones
 _IGNORED = ("wandb_params", "visualize_sample_epoch", "visualize_chain_epoch", "eval_params", "eval_epochs",
             "enable_progress_bar", "num_sanity_val_steps", "num_workers")
@@ -100,10 +108,11 @@ def check_config(cfg):
     if cfg.get("augment_rotation", False):
         raise NotImplementedError("augment_rotation is not supported (the reference raises NotImplementedError too)")
     if int(cfg.get("gpus", 1)) > 1:
-        raise NotImplementedError("gpus > 1: multi-GPU training is out of scope of this trainer; set gpus: 1")
-    if int(cfg.get("accumulate_grad_batches", 1)) != 1:
-        raise NotImplementedError("accumulate_grad_batches > 1 is not supported (the training step re-lays-out the "
-                                  "weights at every forward)")
+        raise NotImplementedError("gpus > 1: multi-GPU training is out of scope of this trainer; set gpus: 1 and multiply "
+                                  "accumulate_grad_batches by the number of GPUs for the same effective batch")
+    k = cfg.get("accumulate_grad_batches", 1)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError(f"accumulate_grad_batches must be an integer >= 1, got {k!r}")
     ignored = [k for k in cfg if k in _IGNORED or k.startswith("visualize_")]
     if ignored:
         warnings.warn("training config: accepted and ignored: " + ", ".join(sorted(ignored)) +
@@ -116,6 +125,14 @@ def check_config(cfg):
     cfg.setdefault("logdir", ".")
     cfg.setdefault("run_name", "run")
     return cfg
+
+
+def accumulation_windows(n_batches, k):
+    """The sizes of the accumulation windows over an epoch of `n_batches` batches: full windows of `k`, then the rest."""
+    n_batches, k = int(n_batches), int(k)
+    if n_batches < 0 or k < 1:
+        raise ValueError("accumulation_windows needs n_batches >= 0 and k >= 1")
+    return [min(k, n_batches - lo) for lo in range(0, n_batches, k)]
 
 
 def load_config(path, resume_hparams=None):
@@ -135,8 +152,9 @@ def load_config(path, resume_hparams=None):
 
 # ---- the loop -----------------------------------------------------------------------------------------------------------
 class Trainer:
-    """fit() / training_step() / validate() / save_checkpoint() / resume() around `ddpm.forward` and the HIP optimiser.
-    `optimizer="torch"` selects torch.optim.AdamW plus the host-side restatement of the reference's clipping (A/B)."""
+    """fit() / training_step() / training_window() / validate() / save_checkpoint() / resume() around `ddpm.forward` and
+    the HIP optimiser.  `optimizer="torch"` selects torch.optim.AdamW plus the host-side restatement of the reference's
+    clipping (A/B); it accumulates through torch."""
 
     def __init__(self, config, node_histogram, train_set=None, val_set=None, device="cuda", optimizer="hip"):
         from .generate import LigandGenerator
@@ -147,6 +165,7 @@ class Trainer:
             raise ValueError("optimizer must be 'hip' or 'torch'")
         self.optimizer_kind = optimizer
         self.seed = int(cfg["seed"])
+        self.accumulate = int(cfg.get("accumulate_grad_batches", 1))
         with torch.random.fork_rng(devices=[self.device] if self.device.type == "cuda" else []):
             torch.manual_seed(self.seed)                   # the initial weights are a function of the seed as well
             gen = LigandGenerator(dataset=cfg["dataset"], egnn_params=cfg["egnn_params"],
@@ -173,6 +192,7 @@ class Trainer:
             self.clipper = ReferenceClipper() if cfg["clip_grad"] else None
         self.train_set, self.val_set = train_set, val_set
         self.epoch, self.global_step, self.batch_in_epoch = 0, 0, 0
+        self.micro_step = 0                # micro-batches seen so far: the key of the noise and the diffusion times
         self.best_val, self.best_path = float("inf"), None
         self.run_dir = os.path.join(cfg["logdir"], cfg["run_name"])
         self.ckpt_dir = os.path.join(self.run_dir, "checkpoints")
@@ -182,7 +202,7 @@ class Trainer:
         self.ddpm.t_int_source = self._draw_t
         self._t_key = 0
 
-    # -- randomness: everything derives from (seed, epoch, global_step) ----------------------------------------------------
+    # -- randomness: everything derives from (seed, epoch, micro_step) -----------------------------------------------------
     def _draw_t(self, batch):
         lowest = 0 if self.ddpm.training else 1
         self._t_gen.manual_seed((self.seed * 7919 + self._t_key) % (2 ** 63))
@@ -209,19 +229,41 @@ class Trainer:
                               x_dims=self.x_dims, atom_nf=self.atom_nf, residue_nf=self.residue_nf, aux=self.aux)
 
     def training_step(self, data):
-        """forward -> backward -> clip -> AdamW for one batch; -> the loss as a device scalar (no read-back)."""
+        """A window of one batch (see training_window)."""
+        return self.training_window([data])
+
+    def _window(self):
+        """Where the window's gradients are summed: the optimiser's bucket (HIP optimiser, k > 1), else torch's p.grad."""
+        if self.accumulate > 1 and isinstance(self.optimizer, ClippedAdamW):
+            from .train_net import accumulating
+            return accumulating(self.ddpm.dynamics, self.optimizer.gradient_bucket())
+        return contextlib.nullcontext()
+
+    def training_window(self, batches):
+        """forward -> backward for every micro-batch of one accumulation window (at most `accumulate_grad_batches`; every
+        loss is nll.mean(0) / accumulate_grad_batches, in a short window too), then clip -> AdamW once; -> the sum of the
+        scaled losses as a device scalar (no read-back)."""
+        if not 1 <= len(batches) <= self.accumulate:
+            raise ValueError("a window holds 1 to accumulate_grad_batches (%d) batches, got %d" % (self.accumulate, len(batches)))
         self.ddpm.train()
-        self._key_step(self.global_step)
-        nll, info = self.forward(data)
-        loss = nll.mean(0)
-        loss.backward()
+        total = None
+        with self._window():
+            for data in batches:
+                self._key_step(self.micro_step)
+                nll, info = self.forward(data)
+                loss = nll.mean(0)
+                if self.accumulate > 1:
+                    loss = loss / self.accumulate
+                loss.backward()
+                self.micro_step += 1
+                total = loss.detach() if total is None else total + loss.detach()
         if self.clipper is not None:
             self.clipper.clip(self.params)
         self.optimizer.step()
         self.optimizer.zero_grad(set_to_none=True)
         self.global_step += 1
-        self._pending.append((self.global_step, loss.detach()))
-        return loss.detach()
+        self._pending.append((self.global_step, total))
+        return total
 
     @torch.no_grad()
     def validate(self):
@@ -268,12 +310,15 @@ class Trainer:
         while self.epoch < int(cfg["n_epochs"]):
             order = epoch_permutation(n, self.seed, self.epoch).tolist()
             batches = [order[i:i + bs] for i in range(0, n, bs)]
+            # batch_in_epoch only ever stops at a window boundary: a checkpoint never holds a half-filled bucket
+            starts = np.cumsum([0] + accumulation_windows(len(batches), self.accumulate)).tolist()
             while self.batch_in_epoch < len(batches):
                 if max_steps is not None and self.global_step >= max_steps:
                     self.flush_metrics()
                     return
-                self.training_step(self.train_set.collate(batches[self.batch_in_epoch]))
-                self.batch_in_epoch += 1
+                hi = min(b for b in starts if b > self.batch_in_epoch)
+                self.training_window([self.train_set.collate(b) for b in batches[self.batch_in_epoch:hi]])
+                self.batch_in_epoch = hi
                 if self.global_step % int(cfg["log_every"]) == 0:
                     self.flush_metrics()
             self.flush_metrics()
@@ -304,6 +349,7 @@ class Trainer:
         sd = {"ddpm." + k: v.detach().cpu() for k, v in self.ddpm.state_dict().items()}
         return {"state_dict": sd, "hyper_parameters": self.hyper_parameters(), "optimizer_states": [opt],
                 "epoch": self.epoch, "global_step": self.global_step, "batch_in_epoch": self.batch_in_epoch,
+                "micro_step": self.micro_step,
                 "optimizer_kind": self.optimizer_kind, QUEUE_KEY: opt.get(QUEUE_KEY), "best_val": self.best_val}
 
     def save_checkpoint(self, val_loss=None):
@@ -338,6 +384,7 @@ class Trainer:
         self.optimizer.load_state_dict(opt)
         self.epoch, self.global_step = int(ck.get("epoch", 0)), int(ck.get("global_step", 0))
         self.batch_in_epoch = int(ck.get("batch_in_epoch", 0))
+        self.micro_step = int(ck.get("micro_step", self.global_step))      # (checkpoints written before accumulation)
         self.best_val = float(ck.get("best_val", float("inf")))
 
     @classmethod

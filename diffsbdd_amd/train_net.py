@@ -9,10 +9,17 @@ tensors, the per-call workspace and the stream.
 
 `DSBDD_TRAIN=functions` selects the per-stage Functions of train_hip.py (A/B, and the only path for gradients of
 gradients, which neither implements), `DSBDD_TRAIN=torch` round 3's eager path.
+
+Gradient accumulation: inside `accumulating(module, bucket)` the backward writes the parameter gradients straight into
+the optimiser's flat `GradientBucket` (`dsbdd_train_net_backward_acc`: overwrite on the first micro-batch of the window,
+add in place from the second on) and the forward re-lays-out the weights once per window
+(`dsbdd_train_net_forward_held`).  `DSBDD_GRAD_BUCKET=0` leaves the accumulation to torch (A/B).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import os
 import weakref
 
 import torch
@@ -64,6 +71,7 @@ class _Net:
         self.pack_bytes = int(self.lib.dsbdd_train_net_pack_bytes(h))
         self.pack = None
         self.device = None
+        self.window = None          # the open accumulation window (`accumulating`), or None
 
     def pack_for(self, dev):
         if self.pack is None or self.device != dev:
@@ -95,6 +103,41 @@ def _ptr_table(tensors):
     return arr
 
 
+class _Window:
+    """One accumulation window of a module: which parameters the bucket already holds a gradient of, whether the pack
+    buffer holds the current weights, and throw-away destinations for gradients that autograd drops."""
+
+    def __init__(self, bucket):
+        self.bucket = bucket
+        self.written = set()        # id(parameter)
+        self.packed = None          # the parameter pointers the pack was written for in this window
+        self.spare = {}             # slot -> tensor for a gradient nobody keeps (a decoder the loss never read)
+        self.forwards = self.held = self.backwards = 0      # bookkeeping (tests, tools/train_step_bench.py)
+
+
+def bucket_enabled():
+    return os.environ.get("DSBDD_GRAD_BUCKET", "1") != "0"
+
+
+@contextlib.contextmanager
+def accumulating(module, bucket):
+    """One accumulation window over `module` (an EGNNDynamics): every `EGNNTrainFunction.backward` inside it adds into
+    `bucket` (optim.GradientBucket) -- the first write of a parameter overwrites and sets `p.grad = bucket.view(p)`,
+    later ones accumulate in the kernels' last stores -- and autograd receives None for those parameters.  The first
+    forward re-lays-out the weights, later ones reuse the pack: the weights must not change inside a window.  Leaving
+    the window releases both.  `DSBDD_GRAD_BUCKET=0`: bookkeeping only, torch accumulates (A/B); DSBDD_TRAIN=functions /
+    torch never reach this node and accumulate through torch as well.  -> the window (counters `forwards`, `held`)."""
+    net = _net_of(module)
+    if net.window is not None:
+        raise RuntimeError("accumulation windows do not nest")
+    win = _Window(bucket if bucket_enabled() else None)
+    net.window = win
+    try:
+        yield win
+    finally:
+        net.window = None
+
+
 class EGNNTrainFunction(torch.autograd.Function):
     """(xh_atoms, xh_residues, *parameters) -> (eps_atoms, eps_residues); forward and backward are one C call each."""
 
@@ -118,11 +161,21 @@ class EGNNTrainFunction(torch.autograd.Function):
         eps_l = torch.empty_like(xl)
         eps_p = torch.empty_like(xp)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.check(lib.dsbdd_train_net_forward(
-            net.handle, _stream(dev), C.byref(g.c), _ptr_table(ps), pack.data_ptr(), pack.numel(), ws.data_ptr(), ws.numel(),
+        win = net.window if net.window is not None and net.window.bucket is not None else None
+        ptrs = _ptr_table(ps)
+        key = (pack.data_ptr(), tuple(ptrs))
+        held = win is not None and win.packed == key
+        _lib.check(lib.dsbdd_train_net_forward_held(
+            net.handle, _stream(dev), C.byref(g.c), ptrs, pack.data_ptr(), pack.numel(), ws.data_ptr(), ws.numel(),
             xl.data_ptr(), xp.data_ptr(), tt.data_ptr(), tt.numel(), int(bool(zero_nan)), eps_l.data_ptr(), eps_p.data_ptr(),
-            status.data_ptr()), "dsbdd_train_net_forward")
+            status.data_ptr(), int(held)), "dsbdd_train_net_forward_held")
+        if net.window is not None:
+            net.window.forwards += 1
+        if win is not None:
+            win.packed = key
+            win.held += int(held)
         ctx.net, ctx.g, ctx.ws, ctx.pack, ctx.ps = net, g, ws, pack, ps
+        ctx.params = params
         ctx.status = status
         ctx.in_grad = (xh_atoms.requires_grad, xh_residues.requires_grad)
         ctx.shapes = (xl.shape, xp.shape)
@@ -142,23 +195,51 @@ class EGNNTrainFunction(torch.autograd.Function):
         ctx.none_l, ctx.none_p = d_l is None, d_p is None
         d_l = torch.zeros(ctx.shapes[0], **f32) if d_l is None else d_l.to(**f32).contiguous()
         d_p = torch.zeros(ctx.shapes[1], **f32) if d_p is None else d_p.to(**f32).contiguous()
-        grads = [torch.empty_like(p) for p in ps]
+        unused = tuple(prefix for none, prefix in ((ctx.none_l, "atom_decoder."), (ctx.none_p, "residue_decoder.")) if none)
+        win = net.window if net.window is not None and net.window.bucket is not None else None
+        if win is None:
+            grads = [torch.empty_like(p) for p in ps]
+            flags = None
+        else:
+            # the destinations are the bucket's views; what autograd would drop goes to a spare tensor, what the bucket
+            # does not hold (a parameter outside the optimiser) to a fresh one, both overwritten
+            grads, mine = [], []
+            flags = (C.c_uint8 * len(ps))()
+            for i, (p, q) in enumerate(zip(ctx.params, ps)):
+                if net.names[i].startswith(unused):
+                    if i not in win.spare:
+                        win.spare[i] = torch.empty_like(q)
+                    grads.append(win.spare[i])
+                elif p in win.bucket and p.requires_grad:
+                    grads.append(win.bucket.view(p))
+                    flags[i] = int(id(p) in win.written)
+                    mine.append(i)
+                else:
+                    grads.append(torch.empty_like(q))
+            win.backwards += 1
         want_l, want_p = ctx.in_grad
         dx_l = torch.empty(ctx.shapes[0], **f32) if (want_l or want_p) else None
         dx_p = torch.empty(ctx.shapes[1], **f32) if (want_l or want_p) else None
-        _lib.check(lib.dsbdd_train_net_backward(
-            net.handle, _stream(dev), C.byref(g.c), _ptr_table(ps), _ptr_table(grads), pack.data_ptr(), pack.numel(),
-            ws.data_ptr(), ws.numel(), int(g.e_lig), d_l.data_ptr(), d_p.data_ptr(),
-            dx_l.data_ptr() if dx_l is not None else None, dx_p.data_ptr() if dx_p is not None else None),
-            "dsbdd_train_net_backward")
+        tail = (pack.data_ptr(), pack.numel(), ws.data_ptr(), ws.numel(), int(g.e_lig), d_l.data_ptr(), d_p.data_ptr(),
+                dx_l.data_ptr() if dx_l is not None else None, dx_p.data_ptr() if dx_p is not None else None)
+        head = (net.handle, _stream(dev), C.byref(g.c), _ptr_table(ps), _ptr_table(grads))
+        if flags is None:
+            _lib.check(lib.dsbdd_train_net_backward(*head, *tail), "dsbdd_train_net_backward")
+        else:
+            _lib.check(lib.dsbdd_train_net_backward_acc(*head, flags, *tail), "dsbdd_train_net_backward_acc")
+            for i in mine:
+                p = ctx.params[i]
+                if id(p) not in win.written:
+                    win.written.add(id(p))
+                    p.grad = grads[i]
+                grads[i] = None        # autograd has nothing to add: no AccumulateGrad launch
         ctx.ws = None          # the activations are consumed
         # a decoder whose output the loss never read has NO gradient (autograd's None, as for the reference's modules:
         # the pocket-conditioned loss ignores eps_pocket, so residue_decoder stays untouched by the optimiser), not zeros
-        for unused, prefix in ((ctx.none_l, "atom_decoder."), (ctx.none_p, "residue_decoder.")):
-            if unused:
-                for i, n in enumerate(net.names):
-                    if n.startswith(prefix):
-                        grads[i] = None
+        if unused:
+            for i, n in enumerate(net.names):
+                if n.startswith(unused):
+                    grads[i] = None
         return (None, None, None, None, None, dx_l if want_l else None, dx_p if want_p else None, *grads)
 
 

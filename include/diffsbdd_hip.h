@@ -509,6 +509,23 @@ int dsbdd_train_net_backward(dsbdd_train_net* net, void* stream, const dsbdd_tra
                              float* const* grads, void* pack, size_t pack_bytes, void* ws, size_t ws_bytes,
                              int64_t e_upd, const float* d_eps_lig, const float* d_eps_pocket, float* d_xh_lig,
                              float* d_xh_pocket);
+/* Gradient accumulation over the micro-batches of one optimiser step.
+ * _backward_acc: `accumulate` holds one flag per parameter slot (never NULL).  Flag 0: grads[i] is overwritten as by
+ * dsbdd_train_net_backward.  Flag 1: grads[i] = grads[i] + g_i, where g_i is bit for bit what dsbdd_train_net_backward
+ * would have written: the complete new gradient is formed first, in its fixed order, and the old value is added last with
+ * one rounding, inside the kernel that does the last store of that gradient (no staging copy, no extra launch; on the
+ * side streams where the overwriting stores run).  The gradient tensors may be views of ONE contiguous bucket.
+ * _forward_held: dsbdd_train_net_forward with a trailing pack_is_current.  Non-zero: the weights cannot have changed since
+ * the previous forward (same accumulation window), the two re-layout launches are skipped and the pack buffer is used as
+ * it is; DSBDD_ERR_STATE unless the handle last packed exactly these parameter tensors into exactly this buffer. */
+int dsbdd_train_net_forward_held(dsbdd_train_net* net, void* stream, const dsbdd_train_graph* g, const float* const* params,
+                                 void* pack, size_t pack_bytes, void* ws, size_t ws_bytes, const float* xh_lig,
+                                 const float* xh_pocket, const float* t, int64_t t_count, int32_t zero_nan, float* eps_lig,
+                                 float* eps_pocket, int32_t* status, int32_t pack_is_current);
+int dsbdd_train_net_backward_acc(dsbdd_train_net* net, void* stream, const dsbdd_train_graph* g, const float* const* params,
+                                 float* const* grads, const uint8_t* accumulate, void* pack, size_t pack_bytes, void* ws,
+                                 size_t ws_bytes, int64_t e_upd, const float* d_eps_lig, const float* d_eps_pocket,
+                                 float* d_xh_lig, float* d_xh_pocket);
 
 /* ---- the loss terms of the pocket-conditioned training step --------------------------------------------
  * ConditionalDDPM.forward around the network call (conditional_model.py:202-330 -> en_diffusion.py:109-262 for the terms):

@@ -6,7 +6,14 @@ Synthetic batch: the 3rfm pocket x B with the anchored 23-atom ligand pose (diff
 
     python tools/train_step_bench.py [--workload crossdock_fullatom_cond] [--batch 16] [--steps 5]
 Prints one markdown table row per path: the step with a synchronisation after every phase (forward / backward / optimiser
-times) and the same step in a free-running loop (no synchronisation inside: how a training loop runs it)."""
+times) and the same step in a free-running loop (no synchronisation inside: how a training loop runs it).
+
+    python tools/train_step_bench.py --accumulate 4 [--workload ...] [--batch ...] [--steps 5] [--rounds 6]
+Gradient accumulation: optimiser steps of K micro-batches (ClippedAdamW with clipping, free-running, one synchronisation
+per timed block of --steps optimiser steps) on the two legs of DSBDD_GRAD_BUCKET -- `bucket`: the backward kernels add into
+the optimiser's flat gradient bucket and the weights are re-laid-out once per window; `torch`: fresh gradient tensors and
+torch's AccumulateGrad adds, a re-layout per forward.  The legs share one model and alternate block by block (--rounds
+blocks each, the order reversed every round); the table gives the median and the range of the blocks."""
 import argparse
 import os
 import sys
@@ -42,6 +49,46 @@ def loss_of(terms):
     return sum(torch.as_tensor(terms[i]).float().mean() for i in (1, 2, 4, 5, 6))
 
 
+def accumulate_bench(a, dev, key, B):
+    from diffsbdd_amd.optim import ClippedAdamW
+    from diffsbdd_amd.train_net import accumulating
+    os.environ["DSBDD_TRAIN"] = "net"
+    K = a.accumulate
+    model, cfg, dd = build(a.workload, dev)
+    model.train(True)
+    opt = ClippedAdamW(list(model.parameters()), lr=1e-4, weight_decay=1e-12, clip_grad=True)
+    bucket = opt.gradient_bucket()
+    batches = [(S.load_pocket(key, B, dev), S.anchor_ligand(B, 23, cfg["atom_nf"], dev)) for _ in range(K)]
+
+    def step(leg):
+        os.environ["DSBDD_GRAD_BUCKET"] = "1" if leg == "bucket" else "0"       # (read when the window opens)
+        with accumulating(model.dynamics, bucket):
+            for pocket, ligand in batches:
+                (loss_of(model(ligand, pocket)) / K).backward()
+        opt.step()
+        opt.zero_grad(set_to_none=True)
+    legs = a.legs.split(",")
+    for leg in legs:
+        for _ in range(a.warmup):
+            step(leg)
+    times = {leg: [] for leg in legs}
+    for r in range(a.rounds):
+        for leg in (legs if r % 2 == 0 else legs[::-1]):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                step(leg)
+            torch.cuda.synchronize()
+            if a.steps:
+                times[leg].append((time.perf_counter() - t0) / a.steps * 1e3)
+    print("| workload | batch | K | leg | ms / optimiser step (median) | ms / micro-batch (median) | min - max ms / micro-batch | blocks x steps |")
+    print("|---|---|---|---|---|---|---|---|")
+    for leg in legs:
+        t = np.array(times[leg]) if times[leg] else np.array([float("nan")])
+        print(f"| {a.workload} | {B} | {K} | {leg} | {np.median(t):.2f} | {np.median(t) / K:.2f} | {t.min() / K:.2f} - {t.max() / K:.2f} | "
+              f"{len(times[leg])} x {a.steps} |", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="crossdock_fullatom_cond")
@@ -62,6 +109,12 @@ def main():
                          "its read-backs (lightning_modules.py:874-899), hip = inside ClippedAdamW (needs --optimizer hip)")
     ap.add_argument("--optimizer", choices=("torch", "hip"), default="torch",
                     help="torch.optim.AdamW(amsgrad=True), or diffsbdd_amd.optim.ClippedAdamW (csrc/optim.h)")
+    ap.add_argument("--accumulate", type=int, default=0,
+                    help="K > 0: time optimiser steps of K accumulated micro-batches on the gradient-bucket leg and on the torch "
+                         "leg (DSBDD_GRAD_BUCKET=0), interleaved; the other options except --workload / --batch / --steps / "
+                         "--warmup do not apply")
+    ap.add_argument("--legs", default="bucket,torch", help="--accumulate: the legs to run (a profiler run takes one)")
+    ap.add_argument("--rounds", type=int, default=6, help="--accumulate: timed blocks of --steps optimiser steps per leg")
     a = ap.parse_args()
     if a.clip == "hip" and a.optimizer != "hip":
         ap.error("--clip hip is part of --optimizer hip")
@@ -71,6 +124,8 @@ def main():
     dev = torch.device("cuda:0")
     key = "ca" if "ca_" in a.workload else "fa"
     B = a.batch or (96 if key == "ca" else 16)
+    if a.accumulate > 0:
+        return accumulate_bench(a, dev, key, B)
     print(f"| workload | batch | path | ms / training step | forward ms | backward ms | optimiser ms | nodes | edges | ms / step, free-running loop |")
     print(f"|---|---|---|---|---|---|---|---|---|---|")
     for path in a.paths.split(","):
