@@ -161,6 +161,11 @@ SIGNATURES = {
     "dsbdd_loss_cond_pre": (C.c_int, [_P, C.POINTER(LossCfg)] + [_P] * 17),
     "dsbdd_loss_cond_post": (C.c_int, [_P, C.POINTER(LossCfg)] + [_P] * 8),
     "dsbdd_loss_cond_post_backward": (C.c_int, [_P, C.POINTER(LossCfg)] + [_P] * 9),
+    # the same for the joint model (both node sets noised and scored)
+    "dsbdd_loss_joint_out_rows": (C.c_int, []),
+    "dsbdd_loss_joint_pre": (C.c_int, [_P, C.POINTER(LossCfg)] + [_P] * 20),
+    "dsbdd_loss_joint_post": (C.c_int, [_P, C.POINTER(LossCfg)] + [_P] * 10),
+    "dsbdd_loss_joint_post_backward": (C.c_int, [_P, C.POINTER(LossCfg)] + [_P] * 14),
     # the optimiser step and the auxiliary loss of the native training loop (csrc/optim.h, csrc/lj_loss.h)
     "dsbdd_optim_create": (C.c_int, [C.POINTER(OptimCfg), _I32, C.POINTER(_I64), C.POINTER(_P)]),
     "dsbdd_optim_destroy": (None, [_P]),

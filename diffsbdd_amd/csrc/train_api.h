@@ -232,6 +232,64 @@ int dsbdd_loss_cond_post_backward(void* stream, const dsbdd_loss_cfg* cfg, const
   return DSBDD_OK;
 }
 
+// the joint model: both node sets are noised and scored (cfg->remove_com and cfg->vnode_idx are not read)
+int dsbdd_loss_joint_out_rows(void) { return LJ_ROWS; }
+
+int dsbdd_loss_joint_pre(void* stream, const dsbdd_loss_cfg* cfg, const float* lig_x, const float* lig_h, const int64_t* lig_mask,
+                         const float* pocket_x, const float* pocket_h, const int64_t* pocket_mask, const float* noise_lig,
+                         const float* noise_pocket, const float* t_int, const float* gamma_table, const float* logpn_table,
+                         float* eps_lig, float* eps_pocket, float* z_lig, float* z_pocket, float* per_sample, float* lig_x_norm,
+                         float* lig_h_norm, float* pocket_x_norm, float* pocket_h_norm) {
+  StreamDevice stream_device_(stream);
+  if (!loss_cfg_ok(cfg) || !t_int || !gamma_table || !per_sample ||
+      (cfg->n_lig > 0 && (!lig_x || !lig_h || !lig_mask || !noise_lig || !eps_lig || !z_lig)) ||
+      (cfg->n_pocket > 0 && (!pocket_x || !pocket_h || !pocket_mask || !noise_pocket || !eps_pocket || !z_pocket)) ||
+      (logpn_table && (cfg->n1_tab < 1 || cfg->n2_tab < 1)))
+    return fail(DSBDD_ERR_ARG, "bad argument");
+  hipLaunchKernelGGL(loss_joint_pre_kernel, dim3((unsigned)cfg->batch), dim3(kLossThreads), 0, static_cast<hipStream_t>(stream),
+                     loss_cfg_of(cfg), lig_x, lig_h, reinterpret_cast<const long long*>(lig_mask), pocket_x, pocket_h,
+                     reinterpret_cast<const long long*>(pocket_mask), noise_lig, noise_pocket, t_int, gamma_table, logpn_table,
+                     eps_lig, eps_pocket, z_lig, z_pocket, per_sample, lig_x_norm, lig_h_norm, pocket_x_norm, pocket_h_norm);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_loss_joint_post(void* stream, const dsbdd_loss_cfg* cfg, const float* net_lig, const float* net_pocket,
+                          const float* eps_lig, const float* eps_pocket, const float* z_lig, const int64_t* lig_mask,
+                          const int64_t* pocket_mask, const float* per_sample, float* xh_lig_hat, float* out) {
+  StreamDevice stream_device_(stream);
+  if (!loss_cfg_ok(cfg) || !per_sample || !out ||
+      (cfg->n_lig > 0 && (!net_lig || !eps_lig || !z_lig || !lig_mask || !xh_lig_hat)) ||
+      (cfg->n_pocket > 0 && (!net_pocket || !eps_pocket || !pocket_mask)))
+    return fail(DSBDD_ERR_ARG, "bad argument");
+  hipLaunchKernelGGL(loss_joint_post_kernel, dim3((unsigned)cfg->batch), dim3(kLossThreads), 0, static_cast<hipStream_t>(stream),
+                     loss_cfg_of(cfg), net_lig, net_pocket, eps_lig, eps_pocket, z_lig, reinterpret_cast<const long long*>(lig_mask),
+                     reinterpret_cast<const long long*>(pocket_mask), per_sample, xh_lig_hat, out);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_loss_joint_post_backward(void* stream, const dsbdd_loss_cfg* cfg, const float* net_lig, const float* net_pocket,
+                                   const float* eps_lig, const float* eps_pocket, const int64_t* lig_mask,
+                                   const int64_t* pocket_mask, const float* per_sample, const float* g_err_lig,
+                                   const float* g_err_pocket, const float* g_l0x_lig, const float* g_l0x_pocket,
+                                   const float* g_xh_lig_hat, float* d_net_lig, float* d_net_pocket) {
+  StreamDevice stream_device_(stream);
+  if (!loss_cfg_ok(cfg) || !per_sample || (cfg->n_lig > 0 && (!net_lig || !eps_lig || !lig_mask || !d_net_lig)) ||
+      (cfg->n_pocket > 0 && (!net_pocket || !eps_pocket || !pocket_mask || !d_net_pocket)))
+    return fail(DSBDD_ERR_ARG, "bad argument");
+  const size_t n = (size_t)cfg->n_lig * (3 + cfg->atom_nf) + (size_t)cfg->n_pocket * (3 + cfg->residue_nf);
+  if (n == 0) return DSBDD_OK;
+  unsigned grid = (unsigned)((n + kLossThreads - 1) / kLossThreads);
+  if (grid > 1024) grid = 1024;
+  hipLaunchKernelGGL(loss_joint_post_bwd_kernel, dim3(grid), dim3(kLossThreads), 0, static_cast<hipStream_t>(stream),
+                     loss_cfg_of(cfg), net_lig, net_pocket, eps_lig, eps_pocket, reinterpret_cast<const long long*>(lig_mask),
+                     reinterpret_cast<const long long*>(pocket_mask), per_sample, g_err_lig, g_err_pocket, g_l0x_lig, g_l0x_pocket,
+                     g_xh_lig_hat, d_net_lig, d_net_pocket);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
 }  // extern "C"
 
 struct dsbdd_optim {

@@ -11,9 +11,12 @@ syncs per step).  The COM / NaN invariants the reference assert
 with `.item()` every step are checked once at the end of the chain from device
 flags.
 
-Out of scope: the training loss (`forward`, `kl_prior*`,
-`log_pxh_given_z0_without_constants`, the learned `GammaNetwork`).  They raise
-NotImplementedError here.
+The training loss (`forward`, en_diffusion.py:336-469): in training mode under
+autograd with a predefined noise schedule the twelve terms run on three HIP
+launches around the network call (`loss_head.joint_forward`, csrc/loss_head.h);
+evaluation mode, `torch.no_grad()`, learned schedules (`GammaNetwork`) and
+`DSBDD_LOSS=torch` evaluate the torch mirror of the reference's terms below
+(`kl_prior_with_pocket`, `_log_ph_given_z0`, ...).
 """
 from __future__ import annotations
 
@@ -196,19 +199,18 @@ class DistributionNodes:
 
     def log_prob(self, batch_n_nodes_1, batch_n_nodes_2):
         assert batch_n_nodes_1.dim() == 1 and batch_n_nodes_2.dim() == 1
-        key = (2, str(batch_n_nodes_1.device))
-        if key not in self._tables:          # the joint categorical's logits as an [n1][n2] table on the device
-            self._tables[key] = self.m.logits.view(self.prob.shape).to(batch_n_nodes_1.device)
-        return self._tables[key][batch_n_nodes_1.long(), batch_n_nodes_2.long()]
+        return self._table(2, batch_n_nodes_1.device)[batch_n_nodes_1.long(), batch_n_nodes_2.long()]
 
     def _table(self, which, device):
-        """[n1][n2] log-probabilities of the conditional categoricals -- the `logits` the per-sample
-        `Categorical.log_prob` calls gather from (same numbers), on `device`, built once: one gather per batch instead
-        of a host loop over the samples with two device-to-host copies."""
+        """[n1][n2] log-probabilities of the conditional categoricals (0, 1) or of the joint one (2) -- the `logits` the
+        per-sample `Categorical.log_prob` calls gather from (same numbers), on `device`, built once: one gather per batch
+        instead of a host loop over the samples with two device-to-host copies."""
         key = (which, str(device))
         if key not in self._tables:
             if which == 0:     # log p(n1 | n2)
                 t = torch.stack([d.logits for d in self.n1_given_n2], dim=1)
+            elif which == 2:   # log p(n1, n2)
+                t = self.m.logits.view(self.prob.shape)
             else:              # log p(n2 | n1)
                 t = torch.stack([d.logits for d in self.n2_given_n1], dim=0)
             self._tables[key] = t.to(device)
@@ -552,6 +554,11 @@ class EnVariationalDiffusion(nn.Module):
         """The reference's loss terms (en_diffusion.py:336-469), same 12-tuple (+ info):
         (delta_log_px, error_t_lig, error_t_pocket, SNR_weight, loss_0_x_ligand, loss_0_x_pocket,
          loss_0_h, neg_log_constants, kl_prior, log_pN, t_int, xh_lig_hat)."""
+        from . import loss_head
+        if loss_head.fused_ok(self, self._hip_device(None)):
+            # training mode under autograd, predefined schedule: the same terms on three HIP launches around the network
+            # call (csrc/loss_head.h, the loss_joint_* kernels); DSBDD_LOSS=torch keeps the torch terms below
+            return loss_head.joint_forward(self, ligand, pocket, return_info)
         with self._loss_context():
             dev = self._hip_device(None)
             ligand, pocket = self._to_device(ligand, dev), self._to_device(pocket, dev)

@@ -569,6 +569,37 @@ int dsbdd_loss_cond_post_backward(void* stream, const dsbdd_loss_cfg* cfg, const
                                   const int64_t* lig_mask, const float* per_sample, const float* g_err, const float* g_l0x,
                                   const float* g_hat, float* d_net);
 
+/* ---- the loss terms of the joint training step -------------------------------------------------------------------------
+ * EnVariationalDiffusion.forward around the network call (en_diffusion.py:336-469), training mode, predefined schedules:
+ * the same three launches for the model that diffuses ligand and pocket together.  Same dsbdd_loss_cfg; its remove_com and
+ * vnode_idx fields are IGNORED here (the joint model neither centres the data nor masks virtual atoms).  Inputs as above;
+ *   noise_lig [n_lig][3 + atom_nf], noise_pocket [n_pocket][3 + residue_nf] standard normal draws, x part NOT centred;
+ *   logpn_table [n1_tab][n2_tab] = log p(n_lig, n_pocket) (the joint categorical) or NULL.
+ * _pre writes eps_lig / eps_pocket (the noise with its x part centred over the sample's ligand + pocket rows, count clamped
+ *   to >= 1: en_diffusion.py:559-578), z_lig = alpha_t xh_lig + sigma_t eps_lig and z_pocket likewise (xh normalised, not
+ *   centred), per_sample [dsbdd_loss_rows()][batch] with the rows listed above -- neg_log_constants and delta_log_px with
+ *   dof = 3 (n_lig + n_pocket - 1), kl_prior over both node sets (en_diffusion.py:109-155), loss_0_h = - sum of the
+ *   categorical log-likelihood of z_t over ligand rows (atom_nf classes) and pocket rows (residue_nf classes) (x [t = 0]) --
+ *   and optionally (non-NULL) the normalised batch.
+ * _post writes xh_lig_hat [n_lig][3 + atom_nf] and out [dsbdd_loss_joint_out_rows()][batch]: error_t_lig, error_t_pocket
+ *   (x [t > 0]), loss_0_x_ligand, loss_0_x_pocket (x [t = 0]), and the per-sample means of |net_lig_x|, |net_lig_h|,
+ *   |net_pocket_x|, |net_pocket_h|.  _post_backward: d_net_lig and d_net_pocket from the per-sample gradients of the four
+ *   error terms (each may be NULL) and of xh_lig_hat (or NULL; ligand only).  Fixed-order sums, no atomics. */
+int dsbdd_loss_joint_out_rows(void);
+int dsbdd_loss_joint_pre(void* stream, const dsbdd_loss_cfg* cfg, const float* lig_x, const float* lig_h, const int64_t* lig_mask,
+                         const float* pocket_x, const float* pocket_h, const int64_t* pocket_mask, const float* noise_lig,
+                         const float* noise_pocket, const float* t_int, const float* gamma_table, const float* logpn_table,
+                         float* eps_lig, float* eps_pocket, float* z_lig, float* z_pocket, float* per_sample, float* lig_x_norm,
+                         float* lig_h_norm, float* pocket_x_norm, float* pocket_h_norm);
+int dsbdd_loss_joint_post(void* stream, const dsbdd_loss_cfg* cfg, const float* net_lig, const float* net_pocket,
+                          const float* eps_lig, const float* eps_pocket, const float* z_lig, const int64_t* lig_mask,
+                          const int64_t* pocket_mask, const float* per_sample, float* xh_lig_hat, float* out);
+int dsbdd_loss_joint_post_backward(void* stream, const dsbdd_loss_cfg* cfg, const float* net_lig, const float* net_pocket,
+                                   const float* eps_lig, const float* eps_pocket, const int64_t* lig_mask,
+                                   const int64_t* pocket_mask, const float* per_sample, const float* g_err_lig,
+                                   const float* g_err_pocket, const float* g_l0x_lig, const float* g_l0x_pocket,
+                                   const float* g_xh_lig_hat, float* d_net_lig, float* d_net_pocket);
+
 /* ---- the optimiser step of the native training loop (csrc/optim.h) --------------------------------------------------------
  * One step = configure_gradient_clipping (lightning_modules.py:874-899) + torch.optim.AdamW(amsgrad=True).step() of the
  * reference in two launches and without a device-to-host copy: per-chunk sums of g^2 in a fixed order; then every
