@@ -106,6 +106,11 @@ struct EdgeArgs {
   // pass reads it instead of recomputing the H x H layer (train.h, edge_bwd_e_kernel / edge_bwd_ec_kernel)
   float* z2_out;
   size_t z2_stride;       // MODE_COORD: floats between the two MLPs' copies of z2
+  // edge_wave_kernel<.., MSG = true> (MODE_GCL, shell stages of the forward cone): the wave tiles [0, msg_tiles) of the
+  // first list -- the ghost segment, wt_base == 0 -- also keep the gated, un-normalised message m_ij * att of every
+  // slot, [32 msg_tiles][H]: what the segmented row sum adds (agg_complete_shell_kernel gathers them)
+  float* msg_out;
+  int msg_tiles;
 };
 
 enum { MODE_GCL = 0, MODE_COORD = 1 };
@@ -178,6 +183,89 @@ __global__ __launch_bounds__(kThreads) void agg_complete2_kernel(
     }
     *reinterpret_cast<float4*>(agg + (size_t)row * H + k) = v;
   }
+}
+
+
+// Completion of a shell stage of the forward cone (forward.h): the rows of level < shell_level and the ghost rows are
+// completed as agg_complete_kernel does.  A row of level == shell_level ran only its edges from columns of a lower
+// level, in the stage's shell list (head_s / sh_ptr / sh_deg): that sum is formed first, in tile order (0 for a row
+// without such edges -- agg[row] is not read then).  The messages of its other edges -- pocket columns of level >=
+// shell_level -- are the canonical pocket's: edge number e of the row (natural column order; a row of level >= 2 has
+// no ligand column) is slot row_ptr_ghost[twin] + e of the ghost segment, whose messages the same launch left in msg.
+// They are added in ascending slot order as one fp32 chain, scaled like the edge kernel's flush.  Rows of a higher
+// level are not evaluated by the stage and are left alone.
+__global__ __launch_bounds__(kThreads) void agg_complete_shell_kernel(
+    float* agg, const float* agg_head, const int* row_ptr, const int* deg, int n_rows, int H, int max_tile,
+    const int* lvl, int shell_level, int n_lig, int n_nodes, const float* head_s, const int* sh_ptr, const int* sh_deg,
+    const int* row_ptr_nat, const int* ecol_nat, int e_cap_nat, const int* twin_local, const int* row_ptr_ghost,
+    const float* msg, int msg_slots, float inv_norm) {
+  const int row = (blockIdx.x * kThreads + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  if (row >= n_rows) return;
+  const int L = (row >= n_lig && row < n_nodes) ? lvl[row] : 0;      // (ligand and ghost rows: always evaluated)
+  if (L > shell_level) return;
+  if (L < shell_level) {
+    const int d = deg[row], s = row_ptr[row];
+    const int t0 = s >> 5, t1 = min((s + d - 1) >> 5, max_tile);
+    if (d > 0 && t1 == t0) return;
+    for (int k = 4 * lane; k < H; k += 256) {
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (d > 0) {
+        v = ld4(agg + (size_t)row * H + k);
+        for (int T = t0 + 1; T <= t1; ++T) {
+          const float4 h = ld4(agg_head + (size_t)T * H + k);
+          v.x += h.x; v.y += h.y; v.z += h.z; v.w += h.w;
+        }
+      }
+      *reinterpret_cast<float4*>(agg + (size_t)row * H + k) = v;
+    }
+    return;
+  }
+  const int d = sh_deg[row], s = sh_ptr[row];
+  const int t0 = s >> 5, t1 = min((s + d - 1) >> 5, max_tile);
+  const int dn = deg[row], sn = row_ptr_nat[row];
+  const int e_lo = max(sn, 0), e_hi = min(sn + dn, e_cap_nat);
+  const int base = row_ptr_ghost[twin_local[row - n_lig]] - sn;      // ghost slot of natural edge e: base + e
+  // (H <= 256: one 16-byte piece per lane; every lane takes part in the ballots below, `on` guards the memory accesses)
+  const int k = min(4 * lane, H - 4);
+  const bool on = 4 * lane < H;
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (d > 0 && on) {
+    v = ld4(agg + (size_t)row * H + k);
+    for (int T = t0 + 1; T <= t1; ++T) {
+      const float4 h = ld4(head_s + (size_t)T * H + k);
+      v.x += h.x; v.y += h.y; v.z += h.z; v.w += h.w;
+    }
+  }
+  // which edges: lane q looks at edge e0 + q (no lane waits for another one's column / level); then the messages in
+  // slot order, four loads in flight, added one after the other
+  float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int e0 = e_lo; e0 < e_hi; e0 += 64) {
+    const int e = e0 + lane;
+    bool take = false;
+    if (e < e_hi) {
+      const int j = ecol_nat[e];
+      take = (unsigned)j < (unsigned)n_nodes && j >= n_lig && lvl[j] >= shell_level &&      // else: in the shell list (or stale)
+             (unsigned)(base + e) < (unsigned)msg_slots;
+    }
+    unsigned long long mk = __ballot(take);
+    while (mk) {
+      const float* src[4];
+      int n = 0;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (mk) {
+          src[n++] = msg + (size_t)(base + e0 + (__ffsll((long long)mk) - 1)) * H + k;
+          mk &= mk - 1;
+        }
+      float4 m[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) if (u < n) m[u] = ld4(src[u]);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) if (u < n) { c.x += m[u].x; c.y += m[u].y; c.z += m[u].z; c.w += m[u].w; }
+    }
+  }
+  v.x += c.x * inv_norm; v.y += c.y * inv_norm; v.z += c.z * inv_norm; v.w += c.w * inv_norm;
+  if (on) *reinterpret_cast<float4*>(agg + (size_t)row * H + k) = v;
 }
 
 }  // namespace dsbdd

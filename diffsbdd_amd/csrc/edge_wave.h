@@ -165,10 +165,11 @@ __global__ __launch_bounds__(256) void pack_w2e_kernel(const float* __restrict__
   out[base + 1024] = (unsigned short)(__float_as_uint(lo) >> 16);
 }
 
-template <int H, int MODE, bool BPERM, int EMU = 0, bool STORE = false>
+template <int H, int MODE, bool BPERM, int EMU = 0, bool STORE = false, bool MSG = false>
 __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
   using L = WaveLayout<H, MODE, EMU>;
   static_assert(!STORE || (!BPERM && EMU == 0), "z2 is stored by the plain exact kernels only");
+  static_assert(!MSG || (MODE == MODE_GCL && EMU == 0 && !STORE), "messages are kept by the exact message kernel only");
   constexpr int BK = L::BK;
   constexpr int CT = H / 32;            // 32-col MFMA tiles per wave (all features)
   constexpr int NK = H / BK;            // K slices per unit
@@ -555,6 +556,29 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
         for (int c = 0; c < CT; ++c)
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[c][r] *= part[r];       // mij * att, egnn_new.py:40
+      }
+      if constexpr (MSG) {
+        // shell stage of the forward cone: the ghost segment's tiles of the first list keep the gated, un-normalised
+        // messages of their valid slots (128-byte row segments per half-wave, like the z2 store above); the tile index
+        // is wave-uniform (wt_base == 0: the list starts at slot 0)
+        const int wt = __builtin_amdgcn_readfirstlane(my_wt);
+        if (!my_lb && wt < p.msg_tiles) {
+          const int e0 = wt * BMW;
+          // feat(c) = 32 c + j, with the two halves of the column tiles swapped for the lanes that read B swapped
+          // (CT == 8 only): two lane bases, every other offset a compile-time constant
+          float* mb = p.msg_out + (size_t)e0 * H + (4 * half) * H + j;
+          float* const mlo = mb + 128 * swb;
+          float* const mhi = mb - 128 * swb;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int row = 8 * (r >> 2) + 4 * half + (r & 3);
+            if (e0 + row < E) {
+#pragma unroll
+              for (int c = 0; c < CT; ++c)
+                (c < 4 ? mlo : mhi)[(8 * (r >> 2) + (r & 3)) * H + 32 * c] = acc[c][r];
+            }
+          }
+        }
       }
       // Segmented sums over the tile's 32 rows.  Accumulator register rr of half h is row 8*(rr>>2) + 4*h + (rr&3):
       // the rows alternate between the halves in groups of 4.  Every half adds up ITS rows of the running segment in

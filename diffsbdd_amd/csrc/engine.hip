@@ -129,6 +129,7 @@ int dsbdd_engine_bind_workspace(dsbdd_engine* e, void* ws, size_t bytes, int64_t
   e->cap_lig = nl; e->cap_poc = np; e->cap_batch = B; e->cap_edges = E;
   e->cap_edgesL = 2 * E + 32 * kLevels * B;
   e->cap_tiles = e->cap_edgesL / 32 + 2;
+  e->cap_shell = E + 32 * B;
   e->cap_tiles16 = e->cap_edgesL / 16 + 2;   // head slots of the 16-edge-granule kernels (edge_wave16.h); <= 2 * cap_tiles
   e->lvl_stats_zeroed = false;          // cleared by the first (eager) call that uses it
   e->frame = false;               // a pocket frame lives in the workspace
@@ -219,6 +220,7 @@ int dsbdd_engine_set_option(dsbdd_engine* e, int which, int value) {
     case DSBDD_OPT_EMU:                                                            // 0 exact fp32; 6 / 9: emulated on the bf16 matrix cores
       if (value != 0 && value != 6 && value != 9) return fail(DSBDD_ERR_ARG, "DSBDD_OPT_EMU takes 0, 6 or 9");
       e->emu = value; break;
+    case DSBDD_OPT_SHELL: e->shell = value ? 1 : 0; break;
     default: return fail(DSBDD_ERR_ARG, "unknown option");
   }
   e->drop_graphs();
@@ -233,6 +235,7 @@ int dsbdd_engine_get_option(const dsbdd_engine* e, int which) {
     case DSBDD_OPT_GRANULE16: return (int)e->granule16;
     case DSBDD_OPT_SPLITK: return (int)e->splitk;
     case DSBDD_OPT_EMU: return e->emu;
+    case DSBDD_OPT_SHELL: return e->shell;
   }
   return fail(DSBDD_ERR_ARG, "unknown option");
 }
@@ -287,6 +290,27 @@ int dsbdd_engine_buffer(const dsbdd_engine* e, int which, void** out) {
   return DSBDD_OK;
 }
 
+int dsbdd_engine_shell_read(const dsbdd_engine* e, int which, int list, void* dst, int64_t count) {
+  if (!e || !dst || count < 0) return fail(DSBDD_ERR_ARG, "bad argument");
+  if (!e->shell_mem) return fail(DSBDD_ERR_STATE, "no shell stage has run on this engine");
+  const int64_t N = e->shell_key[0], SL = e->shell_key[2];
+  const void* src = nullptr;
+  int64_t have = 0, size = 4;
+  const bool lst = list >= 0 && list < kShellLists;
+  switch (which) {
+    case DSBDD_SHELL_STATS: src = e->sh_stats; have = 8; size = 8; break;
+    case DSBDD_SHELL_COUNT: src = e->sh_cnt; have = kShellLists; break;
+    case DSBDD_SHELL_ROW: if (lst) { src = e->sh_row + (size_t)list * SL; have = SL; } break;
+    case DSBDD_SHELL_COL: if (lst) { src = e->sh_col + (size_t)list * SL; have = SL; } break;
+    case DSBDD_SHELL_PTR: src = e->sh_ptr; have = N; break;
+    case DSBDD_SHELL_DEG: src = e->sh_deg; have = N; break;
+  }
+  if (!src) return fail(DSBDD_ERR_ARG, "unknown shell buffer");
+  if (count > have) return fail(DSBDD_ERR_CAPACITY, "shell read past the buffer");
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(dst, src, (size_t)(count * size), hipMemcpyDeviceToHost));
+  return DSBDD_OK;
+}
 
 int dsbdd_dynamics_forward(dsbdd_engine* e, void* stream, const float* xh_lig, const float* xh_pocket,
                            const float* t, int64_t t_count, const int64_t* mask_lig,

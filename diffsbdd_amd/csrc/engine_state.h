@@ -170,6 +170,19 @@ struct dsbdd_engine : Workspace {
   // the rest take the values of the canonical pocket, computed once on ghost rows N .. N + n_ghost
   int cone = 1;                         // DSBDD_CONE=0: off, 1: when the cost model says it pays (default), 2: always
   int64_t ghost_slots = 0;              // slots of the ghost segment at the front of the level-ordered list
+  int shell = 1;                        // DSBDD_OPT_SHELL: shell rows of the cone's ascending stages reuse the ghost rows' messages
+  int64_t cap_shell = 0;                // slots of one shell list: a level's rows, one padded segment per sample
+  // Memory of the shell stages: the shell lists (graph.h, LevelArgs::sh_*) and the messages of the ghost segment,
+  // [ghost_slots][H].  The bound workspace keeps its recorded layout and the message buffer's size is the frame's, not
+  // known at bind time, so the engine owns this block: laid out by shell_memory (graph_cache.h) before the first call
+  // that runs a shell stage -- eagerly, never inside a capture --, kept until the capacities or the frame outgrow it.
+  char* shell_mem = nullptr;
+  int64_t shell_key[3] = {0, 0, 0};     // node / batch / list capacity it was laid out for
+  int *sh_seg = nullptr, *sh_deg = nullptr, *sh_ptr = nullptr, *sh_row = nullptr, *sh_col = nullptr, *sh_cnt = nullptr;
+  float* sh_d0 = nullptr;
+  unsigned long long* sh_stats = nullptr;
+  float* msg_buf = nullptr;
+  int64_t msg_cap = 0;                  // slots
   // plan of the last forward (host side): radius and ghost use of every message stage, level of the timed launches
   std::vector<int> plan_radius, plan_ghost;
   int plan_timed_level = kLevels - 1;
@@ -249,6 +262,7 @@ struct dsbdd_engine : Workspace {
     if (side_stream) (void)hipStreamDestroy(side_stream);
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     if (ev_join) (void)hipEventDestroy(ev_join);
+    if (shell_mem) (void)hipFree(shell_mem);
   }
 };
 

@@ -125,6 +125,24 @@ struct Forward : ForwardArgs {
       }
     return last;
   }
+  // Shell (DSBDD_OPT_SHELL): the same argument edge by edge.  In an ascending stage g >= 1 the rows of level g + 1 -- the
+  // stage's shell -- still hold canonical h (and P|Q), and so do their neighbours of level >= g + 1; pocket-pocket distances
+  // do not depend on the ligand.  The message of an edge (shell row, column of level >= g + 1) is therefore the one the
+  // ghost rows compute for the twin edge in the same launch, and every sample would compute it again.  Such a stage runs
+  // list A = [ghost segment | rows of level <= g] of the main list and list B = the stage's shell list (graph.h: the shell
+  // rows' edges from columns of level <= g) in one persistent grid, the ghost tiles keep their messages, and
+  // agg_complete_shell_kernel adds them to the shell rows' own sums in a fixed order.  Only for exact levels (g + 1 < LV)
+  // and the default exact kernel at hidden_nf 256; the kernel variants of the 16-edge / split-K masks and the emulated
+  // path run their stages as before.  Never switched by size: a sample's bits do not depend on its batch.
+  bool shell_stage(int g) const {
+    return cone && e->shell && g > 0 && g <= g_ghost_last && radius_of(g) == g + 1 && g + 1 < LV && g <= kShellLists &&
+           H == 256 && !e->emu && w2_enabled(e, W2_PERM);
+  }
+  int n_shell() const {                        // shell lists to build: list g - 1 serves stage g
+    int n = 0;
+    for (int g = 1; g <= kShellLists && g < G_stages; ++g) if (shell_stage(g)) n = g;
+    return n;
+  }
   // rows of the nodes of level <= r (r >= kLevels - 1: everything), with or without the ghost rows in front
   // (round 4 experiment, DSBDD_LEVEL_ROWS=1: the all-row stages of a pruned call walk the level list as well -- a
   //  permutation of the rows -- so that the active nodes and the ligand rows are PREFIXES of every stage's row list and the
@@ -270,6 +288,10 @@ struct Forward : ForwardArgs {
         // block 0's per-sample mean (coord2cross) rides in the levels launch: one launch less per pruned call
         mean_in_levels = e->fold_scan && n_mlp == 2;
         if (mean_in_levels) { la.mean_x = e->x; la.mean_out = e->mean; }
+        // the shell lists ride in the level launches: levels_kernel counts, level_place_kernel places and writes them
+        la.n_shell = e->shell_mem ? n_shell() : 0;         // (shell_memory ran in frame_upkeep; message_stage insists on it)
+        la.sh_seg = e->sh_seg; la.sh_deg = e->sh_deg; la.sh_ptr = e->sh_ptr; la.sh_row = e->sh_row; la.sh_col = e->sh_col;
+        la.sh_d0 = e->sh_d0; la.sh_cap = (int)e->cap_shell; la.sh_cnt = e->sh_cnt; la.sh_stats = e->sh_stats;
         if (!e->lvl_stats_zeroed) {
           HIP_TRY(zero_async(e->lvl_stats, 128, s));
           e->lvl_stats_zeroed = true;
@@ -393,9 +415,31 @@ struct Forward : ForwardArgs {
                          (const float*)e->aggB, (const float*)e->agg_headB, (const int*)e->row_ptr3,
                          (const int*)e->deg3, (const int*)e->twin, N, nlig, N, H, cone ? n_ghost : 0, (int)e->cap_tiles - 1);
       HIP_TRY(hipGetLastError());
+    } else if (shell_stage(g) && !g16 && !gsk) {
+      // shell stage: list A = [ghost segment | level <= g], list B = the shell rows' edges from columns of level <= g; the
+      // shell rows are no rows of list A, so both lists write agg, and B's head slots are block 0's, free since its
+      // completion.  Not bracketed by the profiling events: the timed launches stay whole prefixes of the main list.
+      const int sl = g - 1;
+      if (!e->msg_buf || e->msg_cap < ghost_slots) return fail(DSBDD_ERR_STATE, "shell stage without a message buffer");
+      ea.e_count = e->lvl_end + (radius - 1);
+      ea.erow_b = e->sh_row + (size_t)sl * e->cap_shell; ea.ecol_b = e->sh_col + (size_t)sl * e->cap_shell;
+      ea.ed0_b = e->sh_d0 + (size_t)sl * e->cap_shell; ea.e_count_b = e->sh_cnt + sl; ea.e_cap_b = (int)e->cap_shell;
+      ea.wt_base_b = 0; ea.agg_b = e->agg; ea.agg_head_b = e->agg_headB;
+      ea.msg_out = e->msg_buf; ea.msg_tiles = (int)(ghost_slots / 32);
+      HIP_TRY(launch_edge(e, s, MODE_GCL, ea, L_bound() + 128));
+      const int n_rows = N + n_ghost;
+      hipLaunchKernelGGL(agg_complete_shell_kernel, dim3((n_rows + 3) / 4), dim3(kThreads), 0, s, e->agg,
+                         (const float*)e->agg_head, L_ptr, (const int*)e->deg, n_rows, H, (int)e->cap_tiles - 1,
+                         (const int*)e->lvl, radius, nlig, N, (const float*)e->agg_headB, (const int*)e->sh_ptr,
+                         (const int*)e->sh_deg, (const int*)e->row_ptr, (const int*)e->ecol, (int)e->cap_edges,
+                         (const int*)e->twin, (const int*)(e->row_ptrL + N), (const float*)e->msg_buf, (int)ghost_slots,
+                         1.0f / c.normalization_factor);
+      HIP_TRY(hipGetLastError());
     } else {
       // (timed: the launches over the whole list only, so that every timed launch is the same work)
-      const bool timed = e->time_now && (all_rows || radius == e->plan_timed_level) && e->ev_used + 2 <= e->ev.size();
+      // (a stage that would run a shell list but for its kernel variant is not timed either: `timed` is decided by the plan)
+      const bool timed = e->time_now && (all_rows || radius == e->plan_timed_level) && !shell_stage(g) &&
+                         e->ev_used + 2 <= e->ev.size();
       if (timed) HIP_TRY(hipEventRecord(e->ev[e->ev_used], s));
       HIP_TRY(launch_edge(e, s, MODE_GCL, ea, L_bound(), g16 && !gsk, gsk));
       if (timed) {

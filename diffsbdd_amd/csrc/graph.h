@@ -15,6 +15,7 @@ namespace dsbdd {
 constexpr int kTileCtrInts = 32;   // 16 queue heads (8 XCDs x 2 MLP populations) + completion count
 constexpr int kEdgeAlign = 32;     // edges of one (sample, node set) start at a multiple of a wave tile
 constexpr int kLevels = 5;         // hop levels of the level-ordered edge list: 0 ligand, 1..3, 4 = farther
+constexpr int kShellLists = 2;     // shell lists of the forward cone: rows of level 2 and of level 3 (the exact levels past 1)
 
 struct Cutoffs {
   int has_l, has_p, has_i;
@@ -296,7 +297,7 @@ __device__ void scan_one(const int* deg, int* row_ptr, int n, SegAlign seg, int*
 //                   (level 1 comes from the count pass), then rows / edges per (level, sample)
 //   level_scan_kernel   one workgroup: exclusive scans over the kLevels * B segments
 //   level_place_kernel  one workgroup per sample, wave L places level L: new row_ptr, lvl_list, pads
-//   level_copy_kernel   one thread per natural-list slot: move the edge to its new position
+//   level_copy_kernel   one thread per natural-list slot: move the edge to its new position (and to its shell list)
 // mean[b] = mean of x over ALL nodes of sample b = blockIdx.x (egnn_new.py:307-310); one fixed reduction tree, shared
 // by sample_mean_kernel and levels_kernel (round 5: block 0's mean of a pruned call rides in the levels launch)
 __device__ __forceinline__ void sample_mean_body(const float* x, const int* lig_off, const int* poc_off, int n_lig,
@@ -343,16 +344,28 @@ struct LevelArgs {
   int e_cap_nat;            // capacity of the natural-order list: never indexed past it, even when the radius graph
                             // overflowed (status bit 1 is then set by edges_kernel and the call's result is discarded)
   const float* mean_x; float* mean_out;   // optional: levels_kernel also writes the per-sample mean of mean_x (sample_mean_body)
+  // Shell lists of the forward cone (forward.h, "shell"): list s = 0 .. n_shell - 1 holds the rows of level s + 2 with
+  // only their edges from columns of level <= s + 1, laid out like the main list (sorted by (sample, row), a row's edges
+  // contiguous in their natural column order, one 32-aligned segment per sample).  n_shell == 0: not built.
+  int n_shell;
+  int* sh_seg;              // [kShellLists][B] edges of list s in sample b (not padded)
+  int* sh_deg; int* sh_ptr; // [N] a shell row's degree / position in its list (a row has one level: one array serves all lists)
+  int* sh_row; int* sh_col; float* sh_d0; int sh_cap;   // [kShellLists][sh_cap]
+  int* sh_cnt;              // [kShellLists] slots of list s (padded): device scalars
+  // running sums over calls, per list: [3 s] edges of the list, [3 s + 1] its slots, [3 s + 2] edges of its rows that are
+  // NOT in it (columns of level >= s + 2: references to the canonical pocket's messages); [3 kShellLists] calls
+  unsigned long long* sh_stats;
 };
 
 __global__ __launch_bounds__(kThreads) void levels_kernel(LevelArgs a) {
-  __shared__ int s_rows[kLevels], s_edges[kLevels];
+  __shared__ int s_rows[kLevels], s_edges[kLevels], s_shell[kShellLists];
   __shared__ float s_red[3][kThreads];
   if (a.mean_out) sample_mean_body(a.mean_x, a.lig_off, a.poc_off, a.n_lig, a.mean_out, s_red);
   const int b = blockIdx.x, t = threadIdx.x;
   const int p0 = a.n_lig + a.poc_off[b], p1 = a.n_lig + a.poc_off[b + 1];
   const int l0 = a.lig_off[b], l1 = a.lig_off[b + 1];
   if (t < kLevels) { s_rows[t] = 0; s_edges[t] = 0; }
+  if (t < kShellLists) s_shell[t] = 0;
   for (int k = 2; k < kLevels - 1; ++k) {
     __syncthreads();                       // level k-1 is final (global writes of this workgroup are visible to it)
     for (int i = p0 + t; i < p1; i += kThreads) {
@@ -371,6 +384,16 @@ __global__ __launch_bounds__(kThreads) void levels_kernel(LevelArgs a) {
     const int L = a.lvl[i];
     atomicAdd(&s_rows[L], 1);              // integer sums: order does not matter
     atomicAdd(&s_edges[L], a.deg[i]);
+    if (L >= 2 && L - 2 < a.n_shell) {     // a shell row: its edges from columns one level further in
+      const int s = a.row_ptr_nat[i], d = a.deg[i];
+      int d2 = 0;
+      for (int e = max(s, 0); e < min(s + d, a.e_cap_nat); ++e) {
+        const int j = a.ecol_nat[e];
+        d2 += (j < a.n_lig || a.lvl[j] < L) ? 1 : 0;
+      }
+      a.sh_deg[i] = d2;
+      atomicAdd(&s_shell[L - 2], d2);
+    }
   }
   int le = 0;
   for (int i = l0 + t; i < l1; i += kThreads) le += a.deg[i];
@@ -380,6 +403,7 @@ __global__ __launch_bounds__(kThreads) void levels_kernel(LevelArgs a) {
     a.seg_rows[t * a.B + b] = t == 0 ? (l1 - l0) : s_rows[t];
     a.seg_edges[t * a.B + b] = s_edges[t];
   }
+  if (t < a.n_shell) a.sh_seg[t * a.B + b] = s_shell[t];
 }
 
 __global__ __launch_bounds__(1024) void level_scan_kernel(LevelArgs a, int n_nodes) {
@@ -480,6 +504,19 @@ __global__ __launch_bounds__(kThreads) void level_place_kernel(LevelArgs a, int 
   int n_run, e_run;
   if (fold_scan) level_bases(a, L * a.B + b, lane, n_run, e_run);
   else { n_run = a.node_base[L * a.B + b]; e_run = a.edge_base[L * a.B + b]; }
+  // this wave's level is a shell: the rows' second list (sample b's segment starts behind the padded ones before it)
+  const int sl = L - 2;
+  const bool shell = sl >= 0 && sl < a.n_shell;
+  int s_run = 0;
+  if (shell) {
+    int sp = 0;
+    for (int k0 = 0; k0 < b; k0 += 64) {
+      const int kk = k0 + lane;
+      if (kk < b) sp += (a.sh_seg[sl * a.B + kk] + kEdgeAlign - 1) & ~(kEdgeAlign - 1);
+    }
+    s_run = wave_sum_i(sp);
+  }
+  const int s_begin = s_run;
   for (int i0 = p0; i0 < p1; i0 += 64) {
     const int i = i0 + lane;
     const bool mine = i < p1 && a.lvl[i] == L;
@@ -497,8 +534,36 @@ __global__ __launch_bounds__(kThreads) void level_place_kernel(LevelArgs a, int 
     }
     n_run += __popcll(m);
     e_run += __shfl(incl, 63);
+    if (shell) {
+      const int d2 = mine ? a.sh_deg[i] : 0;
+      int incl2 = d2;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(incl2, o);
+        if (lane >= o) incl2 += u;
+      }
+      if (mine) a.sh_ptr[i] = s_run + incl2 - d2;              // (level_copy_kernel moves the edges)
+      s_run += __shfl(incl2, 63);
+    }
   }
   pads(e_run);
+  if (shell) {
+    const int to = (s_run + kEdgeAlign - 1) & ~(kEdgeAlign - 1), pos = s_run + lane;
+    if (pos < to && pos < a.sh_cap) {
+      a.sh_row[(size_t)sl * a.sh_cap + pos] = -1; a.sh_col[(size_t)sl * a.sh_cap + pos] = 0;
+      a.sh_d0[(size_t)sl * a.sh_cap + pos] = 0.f;
+    }
+    if (lane == 0) {
+      if (b == a.B - 1) a.sh_cnt[sl] = to;
+      if (a.sh_stats) {
+        const int own = s_run - s_begin;
+        atomicAdd(&a.sh_stats[3 * sl], (unsigned long long)own);
+        atomicAdd(&a.sh_stats[3 * sl + 1], (unsigned long long)(to - s_begin));
+        atomicAdd(&a.sh_stats[3 * sl + 2], (unsigned long long)(a.seg_edges[L * a.B + b] - own));
+        if (b == 0 && sl == 0) atomicAdd(&a.sh_stats[3 * kShellLists], 1ull);
+      }
+    }
+  }
 }
 
 // Ghost rows of the canonical pocket: the static pocket-pocket list of the frame's representative (node ids
@@ -561,6 +626,23 @@ __global__ void level_copy_kernel(LevelArgs a, int n_nodes) {
     if (i < 0 || i >= n_nodes) continue;    // padding of the natural-order list
     const int pos = a.row_ptr[i] + (e - a.row_ptr_nat[i]);
     if (pos >= 0 && pos < a.e_cap) { a.erow[pos] = i; a.ecol[pos] = a.ecol_nat[e]; a.ed0[pos] = a.ed0_nat[e]; }
+    // a shell row's edge from a column of a lower level also goes to the row's shell list, behind the row's earlier
+    // edges of that kind (the same test as levels_kernel's count; one thread per edge: a walk over the row's few edges
+    // in front of it is cheaper here than a serial walk per row in level_place_kernel, 58 -> 10 us at the benchmark size)
+    const int L = i >= a.n_lig ? a.lvl[i] : 0;
+    if (L >= 2 && L - 2 < a.n_shell) {
+      const int j = a.ecol_nat[e];
+      if (j < a.n_lig || a.lvl[j] < L) {
+        int rank = 0;
+        for (int q = max(a.row_ptr_nat[i], 0); q < e; ++q) {
+          const int jq = a.ecol_nat[q];
+          rank += (jq < a.n_lig || a.lvl[jq] < L) ? 1 : 0;
+        }
+        const int ps = a.sh_ptr[i] + rank;
+        const size_t o = (size_t)(L - 2) * a.sh_cap;
+        if (ps >= 0 && ps < a.sh_cap) { a.sh_row[o + ps] = i; a.sh_col[o + ps] = j; a.sh_d0[o + ps] = a.ed0_nat[e]; }
+      }
+    }
   }
 }
 

@@ -18,6 +18,32 @@ static int ghost_setup(dsbdd_engine* e, hipStream_t s) {
   return DSBDD_OK;
 }
 
+// The engine-owned memory of the cone's shell stages (engine_state.h: shell_mem): laid out for the bound capacities and
+// the frame's ghost segment, zero-filled (the counters start with it); a block that still fits is kept.
+static int shell_memory(dsbdd_engine* e, hipStream_t s) {
+  const int64_t N = e->cap_lig + e->cap_poc, B = e->cap_batch, SL = e->cap_shell;
+  if (e->shell_mem && e->shell_key[0] == N && e->shell_key[1] == B && e->shell_key[2] == SL && e->msg_cap >= e->ghost_slots)
+    return DSBDD_OK;
+  HIP_TRY(hipStreamSynchronize(s));
+  e->drop_graphs();                          // captured graphs hold the old block's pointers
+  if (e->shell_mem) (void)hipFree(e->shell_mem);
+  e->shell_mem = nullptr; e->msg_cap = 0;
+  auto lay = [&](Carver c) {
+    auto ints = [&](size_t n) { return reinterpret_cast<int*>(c.bytes(n * 4)); };
+    e->sh_seg = ints((size_t)kShellLists * B); e->sh_deg = ints((size_t)N); e->sh_ptr = ints((size_t)N); e->sh_cnt = ints(4);
+    e->sh_stats = reinterpret_cast<unsigned long long*>(c.bytes(64));
+    e->sh_row = ints((size_t)kShellLists * SL); e->sh_col = ints((size_t)kShellLists * SL); e->sh_d0 = c.f((size_t)kShellLists * SL);
+    e->msg_buf = c.f1((size_t)e->ghost_slots * e->cfg.hidden_nf);
+    return c.off;
+  };
+  const size_t total = lay(Carver{nullptr});
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&e->shell_mem), total));
+  HIP_TRY(hipMemset(e->shell_mem, 0, total));
+  lay(Carver{e->shell_mem});
+  e->shell_key[0] = N; e->shell_key[1] = B; e->shell_key[2] = SL; e->msg_cap = e->ghost_slots;
+  return DSBDD_OK;
+}
+
 // Ghost rows of a pocket frame (set once per chain) share the node arrays with the real nodes: a call the frame
 // does not apply to (other sizes, teacher-forced edges) may write over them -- eagerly or through a replayed
 // graph --, so they are re-written from the pristine frame data before the next framed call, whichever way it runs.
@@ -31,6 +57,7 @@ static int frame_upkeep(dsbdd_engine* e, hipStream_t s, const ForwardArgs& a) {
     int rc = ghost_setup(e, s);
     if (rc) return rc;
   }
+  if (Forward(e, s, a).n_shell() > 0) RC_TRY(shell_memory(e, s));
   if (!e->h0_pocket_valid) {
     // the residue encoder on the chain's pocket features, once per chain (and again after a call the frame does not
     // apply to overwrote the rows): dynamics.py:97

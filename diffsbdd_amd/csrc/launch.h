@@ -118,6 +118,11 @@ static hipError_t launch_edge(const dsbdd_engine* e, hipStream_t s, int mode, co
   if (sk && a.mlp[0].W2SK) return launch_edge_sk(e, s, mode, a, edge_bound);
   if (g16) return launch_edge16(e, s, mode, a, edge_bound);
   const int grid = edge_wave_grid(mode, a, edge_bound, e->n_cu, e->edge_max_wg);
+  if (a.msg_out) {      // shell stage of the forward cone (forward.h): the default exact message kernel + the message store
+    if (mode != MODE_GCL || e->cfg.hidden_nf != 256 || e->emu || !a.mlp[0].W2TP || a.wt_base) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((edge_wave_kernel<256, MODE_GCL, true, 0, false, true>), dim3(grid), dim3(kThreads), 0, s, a);
+    return hipGetLastError();
+  }
   const int emu = (e->emu && a.mlp[0].W2E && a.mlp[1].W2E) ? e->emu : 0;   // fp32 emulated on the bf16 matrix cores (engine option, opt-in)
   return with_hidden(e->cfg.hidden_nf, [&](auto h) {
     constexpr int H = decltype(h)::value;

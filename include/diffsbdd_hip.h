@@ -241,8 +241,21 @@ int dsbdd_engine_last_plan(const dsbdd_engine* e, int32_t* radius, int32_t* ghos
  * mask is IGNORED (every edge stage of a forward call runs the emulated 32-edge kernel, so a chain never mixes exact and
  * emulated stages); the training step (dsbdd_train_*) always computes in exact fp32.
  * (Round 5 also made the fma of cond_update_kernel / cond_repaint_kernel explicit: the un-fused reverse-step path
- * differs from earlier rounds' results by up to 1 ulp.) */
-enum { DSBDD_OPT_PRUNE = 0, DSBDD_OPT_CONE = 1, DSBDD_OPT_GRANULE16 = 2, DSBDD_OPT_EMU = 3, DSBDD_OPT_SPLITK = 4 };
+ * differs from earlier rounds' results by up to 1 ulp.)
+ * DSBDD_OPT_SHELL (0 / 1, default 1; no environment variable): in the ascending stages g >= 1 of the forward cone the rows
+ * of level g + 1 (the stage's "shell") evaluate only their edges from columns of level <= g; the messages of their
+ * other edges are the canonical pocket's and are gathered from the ghost rows' messages of the same launch
+ * (csrc/forward.h, "Shell").  hidden_nf = 256 with the default exact kernel only: a stage named in the 16-edge or split-K
+ * mask, and every stage with DSBDD_OPT_EMU != 0, runs as with 0.  0 = the launch sequence without it, bit for bit.  On / off
+ * differ in rounding (association of the row sum; canonical messages evaluated on the frame's raw pocket coordinates).
+ * Part of a chain's definition like DSBDD_OPT_CONE: never changed by the engine, a sample's bits do not depend on its batch.
+ * Memory: the shell lists and the ghost segment's messages live in a device block the ENGINE owns (the bound workspace
+ * keeps its layout; the message buffer's size is the frame's).  It is allocated by the first dsbdd_dynamics_forward that
+ * runs a shell stage after dsbdd_engine_bind_workspace / dsbdd_engine_set_pocket_frame changed the capacities or enlarged
+ * the ghost segment: that one call synchronises `stream`, drops the captured graphs and calls hipMalloc, so it must not be
+ * issued while the caller is capturing `stream` (the engine's own graph cache runs its first call of a signature eagerly). */
+enum { DSBDD_OPT_PRUNE = 0, DSBDD_OPT_CONE = 1, DSBDD_OPT_GRANULE16 = 2, DSBDD_OPT_EMU = 3, DSBDD_OPT_SPLITK = 4,
+       DSBDD_OPT_SHELL = 5 };
 int dsbdd_engine_set_option(dsbdd_engine* e, int which, int value);
 /* current value of an option (what the environment / set_option left); DSBDD_ERR_ARG (< 0) for an unknown id */
 int dsbdd_engine_get_option(const dsbdd_engine* e, int which);
@@ -260,6 +273,16 @@ enum {
   DSBDD_BUF_LEVEL_STATS
 };
 int dsbdd_engine_buffer(const dsbdd_engine* e, int which, void** ptr_out);
+
+/* Read-out of the shell lists of the last forward-cone call (csrc/graph.h, LevelArgs::sh_*; DSBDD_OPT_SHELL): copies
+ * `count` elements to host memory (synchronises the device).  List s = 0, 1 holds the rows of level s + 2 with their edges
+ * from columns of level <= s + 1.  STATS: uint64[8] sums over the calls that built the lists, [3 s] edges of list s,
+ * [3 s + 1] its slots (32-aligned sample segments), [3 s + 2] the rows' other edges = references to the canonical pocket's
+ * messages, [6] calls; COUNT: int32[2] slots of either list; ROW / COL: int32 entries of list `list` (padding: row -1);
+ * PTR / DEG: int32 per node, position and degree of a row of level 2 or 3 in its list.  `list` is ignored elsewhere.
+ * DSBDD_ERR_STATE before the first call that ran a shell stage (the memory is laid out then). */
+enum { DSBDD_SHELL_STATS = 0, DSBDD_SHELL_COUNT, DSBDD_SHELL_ROW, DSBDD_SHELL_COL, DSBDD_SHELL_PTR, DSBDD_SHELL_DEG };
+int dsbdd_engine_shell_read(const dsbdd_engine* e, int which, int list, void* dst, int64_t count);
 
 /* ---- DDPM reverse-step updates -------------------------------------------
  * ConditionalDDPM.sample_p_zs_given_zt after the dynamics call

@@ -11,7 +11,7 @@ from collections import OrderedDict
 
 
 def short(name):
-    return re.sub(r"\(.*", "", name).replace("void ", "").replace("dsbdd::", "")[:44]
+    return re.sub(r"\(.*", "", name).replace("void ", "").replace("dsbdd::", "")[:48]
 
 
 def main():
