@@ -435,6 +435,16 @@ class ConditionalDDPM(EnVariationalDiffusion):
     def log_pN(self, N_lig, N_pocket):
         return self.size_distribution.log_prob_n1_given_n2(N_lig, N_pocket)
 
+    # ---- likelihood bound of given ligands (score.py, csrc/score.h) ------------------------------------------------
+    def nll_given_pocket(self, ligand, pocket, n_times=None, times=None, weights=None, seed=0, ligand_ids=None,
+                         max_states=64, return_terms=False):
+        """The model's negative log-likelihood bound of GIVEN ligands in their pockets: K time slots and one zero slot
+        per ligand, all (ligand, time) states evaluated by one network call per chunk of `max_states` states
+        (diffsbdd_amd/score.py has the estimator, the time grid and the noise keying).  -> nll float32 [B]."""
+        from . import score
+        return score.nll_given_pocket(self, ligand, pocket, n_times=n_times, times=times, weights=weights, seed=seed,
+                                      ligand_ids=ligand_ids, max_states=max_states, return_terms=return_terms)
+
 
 class SimpleConditionalDDPM(ConditionalDDPM):
     """The same model without the subspace trick (conditional_model.py:702-746):

@@ -10,7 +10,7 @@
 //   capi_kernels.h  C-ABI wrappers of the stand-alone kernels
 //   train_blocks.h  the training step's building blocks: weight gradients, scratch, side streams, one edge stage each way
 //   train_net.h     the training step of the whole network: parameter index, pack buffer, workspace, the two walks
-//   train_api.h     every dsbdd_train_* / dsbdd_loss_* / dsbdd_optim_* entry point
+//   train_api.h     every dsbdd_train_* / dsbdd_loss_* / dsbdd_score_* / dsbdd_optim_* entry point
 // (device code: the kernel headers included first; train_kernels.h holds the network walk's own kernels)
 #include "../../include/diffsbdd_hip.h"
 
@@ -51,6 +51,7 @@ using namespace dsbdd;
 #include "train_blocks.h"
 #include "train_net.h"
 #include "loss_head.h"
+#include "score.h"
 #include "optim.h"
 #include "lj_loss.h"
 #include "train_api.h"

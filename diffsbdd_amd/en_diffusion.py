@@ -1128,6 +1128,11 @@ class EnVariationalDiffusion(nn.Module):
         alpha_t, sigma_t = self.alpha(gamma_t, z_t), self.sigma(gamma_t, z_t)
         return z_t / alpha_t[batch_mask] - epsilon * sigma_t[batch_mask] / alpha_t[batch_mask]
 
+    def nll_given_pocket(self, ligand, pocket, **kwargs):
+        """Scoring given ligands is defined for the pocket-conditioned models (ConditionalDDPM.nll_given_pocket)."""
+        raise NotImplementedError(f"{type(self).__name__}: ligands are scored under pocket-conditioned models only "
+                                  "(the joint model is out of scope)")
+
     def log_pN(self, N_lig, N_pocket):
         return self.size_distribution.log_prob(N_lig, N_pocket)
 

@@ -16,7 +16,8 @@ or OpenBabel:
 Ligands as input (`ligand_io.py`) carry the reference's two other workflows: `inpaint_ligands` /
 `inpaint_for_pockets` (inpaint.py: a fixed substructure, the rest designed) and `diversify_ligands` /
 `optimize_ligands` (optimize.py: partial noising + denoising of a population, selection by a caller-supplied
-objective).  Their packed batches are written by one HIP launch (`ligand_io.pack_ligands`).
+objective) -- and `score_ligands` (score.py: the model's own likelihood bound of given molecules, the built-in objective).
+Their packed batches are written by one HIP launch (`ligand_io.pack_ligands`).
 
 Molecules are built with the distance-table bonds of `molecules.py` (the
 reference's `use_openbabel=False` path); `sanitize` / `relax_iter` need RDKit and
@@ -482,6 +483,31 @@ class LigandGenerator:
         xh_lig, lig_mask = self._diversify_chain(pocket, ligand, noising_steps)
         x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
         return build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=n)
+
+    # -- scoring given ligands (score.py) ---------------------------------------------------------------------
+    @torch.no_grad()
+    def score_ligands(self, pdb_file, molecules, pocket_ids=None, ref_ligand=None, n_times=10, seed=0, max_states=64):
+        """The model's negative log-likelihood bound of given molecules in one pocket (`ddpm.nll_given_pocket`; lower =
+        more likely under the model).  `molecules` as for `diversify_ligands`: `Molecule` objects, (xyz, elements) pairs
+        or an SDF path; the pocket is selected as in `generate_ligands`.  `n_times` time slots per molecule on one seeded
+        grid shared by all of them ('all': every diffusion time).  Returns one dict per molecule, in order:
+        {'nll', 'loss_t', 'loss_0', 'kl_prior', 'log_pN', 'n_atoms'}."""
+        if not hasattr(self.ddpm, "diversify"):
+            raise NotImplementedError(f"{type(self.ddpm).__name__}: ligands are scored under pocket-conditioned models only")
+        templates = ligand_io.as_templates(molecules, self.lig_type_encoder)
+        n = len(templates)
+        if n < 1:
+            raise ValueError("no molecule to score")
+        residues = self.select_pocket_residues(pdb_file, pocket_ids, ref_ligand)
+        pocket = self.prepare_pocket(residues, repeats=n)
+        tmpl_x, tmpl_t, tmpl_sizes = ligand_io.upload_templates(templates, self.device)
+        ligand, _ = ligand_io.pack_ligands(tmpl_x, tmpl_t, tmpl_sizes, list(range(n)), tmpl_sizes, self.atom_nf)
+        grid = dict(times="all") if isinstance(n_times, str) else dict(n_times=n_times)
+        nll, terms = self.ddpm.nll_given_pocket(ligand, pocket, seed=seed, max_states=max_states, return_terms=True, **grid)
+        loss_0 = (terms["loss_0_x"] + terms["loss_0_h"]) + terms["neg_log_constants"]
+        cols = torch.stack([nll, terms["loss_t"], loss_0, terms["kl_prior"], terms["log_pN"]]).cpu().tolist()
+        return [dict(nll=cols[0][i], loss_t=cols[1][i], loss_0=cols[2][i], kl_prior=cols[3][i], log_pN=cols[4][i],
+                     n_atoms=int(tmpl_sizes[i])) for i in range(n)]
 
     def reference_ligand(self, pdb_file, ref_ligand):
         """(xyz, element symbols) of the ligand that defines the pocket: first record of an SDF file, or the group

@@ -623,6 +623,44 @@ int dsbdd_loss_joint_post_backward(void* stream, const dsbdd_loss_cfg* cfg, cons
                                    const float* g_err_pocket, const float* g_l0x_lig, const float* g_l0x_pocket,
                                    const float* g_xh_lig_hat, float* d_net_lig, float* d_net_pocket);
 
+/* ---- the likelihood bound of given ligands (csrc/score.h; diffsbdd_amd/score.py) --------------------------------------------
+ * ConditionalDDPM.nll_given_pocket: the evaluation branch of ConditionalDDPM.forward (conditional_model.py:202-330) for K
+ * integer times per ligand instead of one random time, with all (ligand, slot) states of a call evaluated by few large
+ * network calls.  Pocket-conditioned models, predefined schedules, no virtual atoms (cfg->vnode_idx must be -1).
+ *   States: g = b * n_slots + k with n_slots = K + 1; k < K are the time slots, k = K is the zero slot (t = 0).  A chunk is
+ *   the states [first_state, first_state + chunk_states), one network call; it may begin and end inside a ligand's slots.
+ *   cfg->batch = number of ligands B; cfg->n_lig / n_pocket, lig_* / pocket_* = the caller's batch as for dsbdd_loss_cond_pre
+ *   (pocket b belongs to ligand b; masks sorted ascending); cfg->n1_tab / n2_tab + logpn_table (required) = log p(n_lig |
+ *   n_pocket), every size of the batch inside the table.
+ *   Chunk arrays: state g owns the ligand rows [P(g) - P(first_state), + n_lig(b)) with P(g) = n_slots * (first row of ligand
+ *   b) + k * n_lig(b), and its pocket rows likewise.  cap_lig / cap_pocket = rows of the chunk arrays; a state that does not
+ *   fit writes no row and NaN scalars.
+ * _rows(which): number of rows of per_state (0), per_ligand (1), out (2).
+ * _pre: eps [cap_lig][3 + atom_nf] standard normal draws in chunk layout; t_int [B * n_slots] integer-valued floats in
+ *   [1, timesteps] (zero slots: not read).  Writes z [cap_lig][3 + atom_nf], xh_pocket [cap_pocket][3 + residue_nf] (each state
+ *   its own centred copy), mask_lig_out / mask_pocket_out (int64, state ids local to the chunk, sorted), t_out [chunk_states]
+ *   = t / timesteps, per_state [_rows(0)][B * n_slots]: rows t, gamma_t, alpha_t, sigma_t, SNR_weight (and, by _post, error_t,
+ *   loss_0_x, loss_0_h) in column g, and -- on the state that is a ligand's slot 0 -- per_ligand [_rows(1)][B]: kl_prior,
+ *   neg_log_constants, delta_log_px, log_pN.
+ * _post: net = the network's output for (z, xh_pocket, t_out).  Time slots: error_t = sum over the ligand's rows and all
+ *   columns of (eps - net)^2; zero slots: loss_0_x = 0.5 sum over the coordinates, loss_0_h = - sum log p(h | z_0).
+ * _reduce: once per call after every chunk; weights [B * n_slots] (zero slots: not read).  out [_rows(2)][B]: nll, loss_t,
+ *   loss_0_x, loss_0_h, neg_log_constants, kl_prior, delta_log_px, log_pN with
+ *     loss_t = sum_k ((-0.5 w[b][k]) SNR_weight) error_t   (k ascending, float32)
+ *     nll    = (((loss_t + ((loss_0_x + loss_0_h) + neg_log_constants)) + kl_prior) - delta_log_px) - log_pN.
+ * Every sum is taken in a fixed order; no atomics. */
+int dsbdd_score_rows(int32_t which);
+int dsbdd_score_cond_pre(void* stream, const dsbdd_loss_cfg* cfg, int32_t n_slots, int64_t first_state, int64_t chunk_states,
+                         int64_t cap_lig, int64_t cap_pocket, const float* lig_x, const float* lig_h, const int64_t* lig_mask,
+                         const float* pocket_x, const float* pocket_h, const int64_t* pocket_mask, const float* eps,
+                         const float* t_int, const float* gamma_table, const float* logpn_table, float* z, float* xh_pocket,
+                         int64_t* mask_lig_out, int64_t* mask_pocket_out, float* t_out, float* per_state, float* per_ligand);
+int dsbdd_score_cond_post(void* stream, const dsbdd_loss_cfg* cfg, int32_t n_slots, int64_t first_state, int64_t chunk_states,
+                          int64_t cap_lig, int64_t cap_pocket, const float* lig_h, const int64_t* lig_mask,
+                          const int64_t* pocket_mask, const float* net, const float* eps, const float* z, float* per_state);
+int dsbdd_score_reduce(void* stream, int64_t batch, int32_t n_slots, const float* weights, const float* per_state,
+                       const float* per_ligand, float* out);
+
 /* ---- the optimiser step of the native training loop (csrc/optim.h) --------------------------------------------------------
  * One step = configure_gradient_clipping (lightning_modules.py:874-899) + torch.optim.AdamW(amsgrad=True).step() of the
  * reference in two launches and without a device-to-host copy: per-chunk sums of g^2 in a fixed order; then every
