@@ -111,6 +111,10 @@ struct EdgeArgs {
   // slot, [32 msg_tiles][H]: what the segmented row sum adds (agg_complete_shell_kernel gathers them)
   float* msg_out;
   int msg_tiles;
+  // edge_wave_kernel, exact message kernels at H = 256 (edge_wave.h, "quarter items"): 0 = every tile is a 128-edge
+  // workgroup item; S > 0 = the tiles of the launch's last, partly filled round over S resident workgroups run as
+  // 32-edge quarter items, split over the column tiles (the launch's grid then covers 4 workgroups per tile up to S)
+  int tail_s;
 };
 
 enum { MODE_GCL = 0, MODE_COORD = 1 };

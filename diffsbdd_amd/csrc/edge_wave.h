@@ -165,6 +165,245 @@ __global__ __launch_bounds__(256) void pack_w2e_kernel(const float* __restrict__
   out[base + 1024] = (unsigned short)(__float_as_uint(lo) >> 16);
 }
 
+// ---- quarter items (exact message kernels, H = 256, lane-grouped B copy) ---------------------------------------------
+// A launch costs the slowest CU's stack of whole 128-edge items, so the tiles of its last, partly filled round run as
+// QUARTER items instead: one 32-edge wave tile evaluated by all four waves of a workgroup, wave w owning the accumulator
+// tiles {2w, 2w + 1} of the eight.  Every output element keeps its fmaf chain over k and every sum its operands and
+// order, so the result is the whole item's bit for bit:
+//   * every wave evaluates the A operand of all k for the tile's 32 edges (the same expressions; the redundancy is
+//     paid on these tiles only), the W2^T slices stream through LDS as in the main loop, a wave reads only its columns;
+//   * the attention logit is ONE fma chain over the accumulator tiles c = 0 .. 7 per lane: wave w continues the chain
+//     that wave w - 1 left in LDS (16 floats per lane, three hand-offs, a workgroup barrier each), wave 3 reduces, takes
+//     the sigmoids and the gates go back to all waves through LDS;
+//   * the segmented row sums follow the rules of the main loop for the wave's two tiles; at a flush the halves exchange
+//     the same two partial sums (half 0 ends with tile 2w, half 1 with tile 2w + 1) and store them to the same address;
+//   * the shell instantiation's message store writes the wave's columns of the same rows.
+// Item u of the workgroup's share is wave tile (u & 3) of 128-edge tile tile0 + (u >> 2); u = u0, u0 + ustep, ... < nq.
+// The second half of the W2^T double buffer carries the hand-off: nobody reads it between the last K step's barrier
+// and the first K step of the next item.
+template <int H, bool MSG>
+__device__ __forceinline__ void edge_quarter_items(const EdgeArgs& p, float* smem, int u0, int ustep, int nq, int tile0,
+                                                   int nt_a, int E, int E_b, float att_b, float inv_norm) {
+  using L = WaveLayout<H, MODE_GCL, 0>;
+  constexpr int BK = L::BK, NK = H / BK, CT = H / 32, BMW = 32, BMB = 128;
+  constexpr int BI = BK * (H / 4) / kThreads;            // float4 units of a W2^T slice per thread
+  static_assert(CT == 8 && NK % 2 == 0, "quarter items: H = 256");
+  float* sB = smem + L::B_OFF;
+  const float* vq = smem + L::VEC_OFF;
+  float* s_hand = sB + L::B_BUF;                          // [4][64 lanes] float4: the attention chain between two waves
+  float* s_gate = s_hand + 16 * 64;                       // [2 halves][16]
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int half = lane >> 5, j = lane & 31;
+  const int swb = (j >> 3) & 1;                           // this lane reads its halves swapped (see the kernel)
+  const int c0 = 2 * w;                                   // accumulator tiles c0, c0 + 1 of the whole item's eight
+  const int feat0 = ((c0 ^ (4 * swb)) * 32) + j, feat1 = feat0 + 32;
+  // word of accumulator tile c0 in the lane's group of CT: tiles 0..3 at [4 swb, +4), tiles 4..7 at [4 - 4 swb, +4)
+  const int boff = j * CT + (w < 2 ? 4 * swb + c0 : 4 - 4 * swb + (c0 - 4));
+  const float* W2 = p.mlp[0].W2TP;
+
+#pragma unroll 1
+  for (int u = u0; u < nq; u += ustep) {
+    const int tile = tile0 + (u >> 2), sub = u & 3;
+    const bool lb = tile >= nt_a;                         // a tile of the second list
+    const int tl = lb ? tile - nt_a : tile, El = lb ? E_b : E;
+    const int* er = lb ? p.erow_b : p.erow;
+    const int* ec = lb ? p.ecol_b : p.ecol;
+    const float* ed = lb ? p.ed0_b : p.ed0;
+    const int e0 = tl * BMB + sub * BMW, e = e0 + j;
+    if (e0 >= El) continue;                               // a wave tile behind the list's end: nothing to write
+    const int my_wt = (lb ? p.wt_base_b : p.wt_base) + tl * 4 + sub;
+    int my_r = -1, my_c = 0, my_ty = 0, my_prev = -1;
+    float my_d0 = 0.f, my_d = 0.f;
+    if (e < El) { my_r = er[e]; my_c = ec[e]; my_d0 = ed[e]; }
+    if (e0 > 0) my_prev = er[e0 - 1];
+    // first W2^T slice
+    {
+      f32x4 s0[BI];
+#pragma unroll
+      for (int i = 0; i < BI; ++i) s0[i] = ldv4(W2 + kThreads * 4 * i + t * 4);
+#pragma unroll
+      for (int i = 0; i < BI; ++i) *reinterpret_cast<f32x4*>(sB + kThreads * 4 * i + t * 4) = s0[i];
+    }
+    if ((unsigned)my_r >= (unsigned)p.n_nodes || (unsigned)my_c >= (unsigned)p.n_nodes) { my_r = -1; my_c = 0; }
+    if (my_r >= 0) {
+      float xr[3], xc[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { xr[k] = p.x[3 * my_r + k]; xc[k] = p.x[3 * my_c + k]; }
+      const float dx = xr[0] - xc[0], dy = xr[1] - xc[1], dz = xr[2] - xc[2];
+      my_d = dx * dx + dy * dy + dz * dz;
+      const bool rl = my_r < p.n_lig, cl = my_c < p.n_lig;
+      my_ty = (rl && cl) ? 1 : ((!rl && !cl) ? 2 : 0);
+    }
+    const float* Pp = p.mlp[0].P + (size_t)(my_r < 0 ? 0 : my_r) * p.ldpq + 4 * half;
+    const float* Qp = p.mlp[0].Q + (size_t)my_c * p.ldpq + 4 * half;
+    f32x4 pc = ldv4(Pp), qc = ldv4(Qp), pn = pc, qn4 = qc;
+    f32x16 acc0, acc1;
+    __syncthreads();          // sV + slice 0 visible
+    {
+      const float b0 = vq[5 * H + feat0], b1 = vq[5 * H + feat1];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { acc0[r] = b0; acc1[r] = b1; }
+    }
+    const f32x2 dd = splat2(my_d), dz = splat2(my_d0);
+
+#pragma unroll 1
+    for (int kt = 0; kt < NK; ++kt) {
+      const bool more = kt + 1 < NK;
+      f32x4 stg[BI];
+      if (more) {
+        const float* src = W2 + (size_t)(kt + 1) * BK * H + t * 4;
+#pragma unroll
+        for (int i = 0; i < BI; ++i) stg[i] = ldv4(src + kThreads * 4 * i);
+      }
+      const float* bcur = sB + (kt & 1) * L::B_BUF + (4 * half) * H + boff;
+      const float* vk = vq + kt * BK + 4 * half;           // this lane's k = kt*BK + 8g + 4*half + i
+      const float* vt = vk + (2 + my_ty) * H;
+#pragma unroll
+      for (int g = 0; g < BK / 8; ++g) {
+        const int kb = kt * BK + 8 * g;
+        if (g + 1 < BK / 8 || more) {
+          pn = ldv4(Pp + kb + 8);
+          qn4 = ldv4(Qp + kb + 8);
+        }
+        // A operand: the main loop's expressions
+        const f32x4 wd4 = *reinterpret_cast<const f32x4*>(vk + 8 * g);
+        const f32x4 wz4 = *reinterpret_cast<const f32x4*>(vk + H + 8 * g);
+        const f32x4 tb4 = *reinterpret_cast<const f32x4*>(vt + 8 * g);
+        f32x2 alo = pk_fma(dz, wz4.xy, pk_fma(dd, wd4.xy, pc.xy + qc.xy)) + tb4.xy;
+        f32x2 ahi = pk_fma(dz, wz4.zw, pk_fma(dd, wd4.zw, pc.zw + qc.zw)) + tb4.zw;
+        alo = silu2(alo);
+        ahi = silu2(ahi);
+        const float a[4] = {alo.x, alo.y, ahi.x, ahi.y};
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const f32x2 bv = *reinterpret_cast<const f32x2*>(bcur + (8 * g + i) * H);
+          acc0 = mfma32(a[i], bv.x, acc0);
+          acc1 = mfma32(a[i], bv.y, acc1);
+        }
+        __builtin_amdgcn_s_setprio(0);
+        pc = pn; qc = qn4;
+      }
+      if (more) {
+        float* dst = sB + ((kt + 1) & 1) * L::B_BUF + t * 4;
+#pragma unroll
+        for (int i = 0; i < BI; ++i) *reinterpret_cast<f32x4*>(dst + kThreads * 4 * i) = stg[i];
+      }
+      __syncthreads();
+    }
+
+    // ---- epilogue: the main loop's, for accumulator tiles c0 and c0 + 1 ----
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+      const f32x2 m0 = silu2(f32x2{acc0[r], acc0[r + 1]});
+      acc0[r] = m0.x; acc0[r + 1] = m0.y;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+      const f32x2 m1 = silu2(f32x2{acc1[r], acc1[r + 1]});
+      acc1[r] = m1.x; acc1[r + 1] = m1.y;
+    }
+    if (p.attention) {
+      float part[16];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        if (w == s) {                                      // (wave-uniform; the barrier below is outside)
+          f32x2 part2[8];
+          if (s == 0) {
+#pragma unroll
+            for (int r = 0; r < 8; ++r) part2[r] = splat2(0.f);
+          } else {
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+              const f32x4 h4 = *reinterpret_cast<const f32x4*>(s_hand + (q4 * 64 + lane) * 4);
+              part2[2 * q4] = h4.xy; part2[2 * q4 + 1] = h4.zw;
+            }
+          }
+          const f32x2 aw0 = splat2(vq[6 * H + feat0]), aw1 = splat2(vq[6 * H + feat1]);
+#pragma unroll
+          for (int r = 0; r < 8; ++r) part2[r] = pk_fma(f32x2{acc0[2 * r], acc0[2 * r + 1]}, aw0, part2[r]);
+#pragma unroll
+          for (int r = 0; r < 8; ++r) part2[r] = pk_fma(f32x2{acc1[2 * r], acc1[2 * r + 1]}, aw1, part2[r]);
+          if (s < 3) {
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+              f32x4 h4;
+              h4.xy = part2[2 * q4]; h4.zw = part2[2 * q4 + 1];
+              *reinterpret_cast<f32x4*>(s_hand + (q4 * 64 + lane) * 4) = h4;
+            }
+          } else {
+#pragma unroll
+            for (int r = 0; r < 8; ++r) { part[2 * r] = part2[r].x; part[2 * r + 1] = part2[r].y; }
+            const float gate = sigmoidf_fast(reduce16_half_wave(part, j) + att_b);
+            s_gate[16 * half + (j >> 1)] = gate;
+          }
+        }
+        __syncthreads();
+      }
+#pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4) {
+        const float4 g4 = *reinterpret_cast<const float4*>(s_gate + 16 * half + 4 * q4);
+        part[4 * q4] = g4.x; part[4 * q4 + 1] = g4.y; part[4 * q4 + 2] = g4.z; part[4 * q4 + 3] = g4.w;
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc0[r] *= part[r];     // mij * att
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc1[r] *= part[r];
+    }
+    if constexpr (MSG) {
+      if (!lb && my_wt < p.msg_tiles) {                    // (wt_base == 0: the list starts at slot 0)
+        float* mb = p.msg_out + (size_t)e0 * H + (4 * half) * H;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = 8 * (r >> 2) + 4 * half + (r & 3);
+          if (e0 + row < E) {
+            mb[(8 * (r >> 2) + (r & 3)) * H + feat0] = acc0[r];
+            mb[(8 * (r >> 2) + (r & 3)) * H + feat1] = acc1[r];
+          }
+        }
+      }
+    }
+    // segmented row sums (the main loop's walk; two column tiles)
+    f32x2 sum0 = splat2(0.f), sum1 = splat2(0.f);
+    int cur = -1;
+    const int row0 = __builtin_amdgcn_readlane(my_r, 0);
+    bool to_head = row0 >= 0 && row0 == __builtin_amdgcn_readfirstlane(my_prev);
+    auto flush = [&]() {
+      if (cur >= 0) {
+        float* dst = to_head ? (lb ? p.agg_head_b : p.agg_head) + (size_t)my_wt * H
+                             : (lb ? p.agg_b : p.agg) + (size_t)cur * H;
+        // half 0: tile c0, half 1: tile c0 + 1 (its own partial sum + the other half's)
+        const float tot = pair_sum_halves(sum0.x + sum0.y, sum1.x + sum1.y);
+        dst[half ? feat1 : feat0] = tot * inv_norm;
+        to_head = false;
+      }
+      sum0 = splat2(0.f); sum1 = splat2(0.f);
+    };
+#pragma unroll
+    for (int gb = 0; gb < 8; ++gb) {
+      const int hh = gb & 1;
+#pragma unroll
+      for (int ip = 0; ip < 4; ip += 2) {
+        const int k = 4 * (gb >> 1) + ip;
+        const int rn0 = __builtin_amdgcn_readlane(my_r, 4 * gb + ip);
+        const int rn1 = __builtin_amdgcn_readlane(my_r, 4 * gb + ip + 1);
+        if (rn0 != cur) {
+          flush();
+          cur = rn0;
+        }
+        if (half == hh) { sum0.x += acc0[k]; sum1.x += acc1[k]; }
+        if (rn1 != rn0) {
+          flush();
+          cur = rn1;
+        }
+        if (half == hh) { sum0.y += acc0[k + 1]; sum1.y += acc1[k + 1]; }
+      }
+    }
+    flush();
+  }
+}
+
 template <int H, int MODE, bool BPERM, int EMU = 0, bool STORE = false, bool MSG = false>
 __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
   using L = WaveLayout<H, MODE, EMU>;
@@ -237,11 +476,34 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
   const int kx = split ? (blockIdx.x >> 4) : (blockIdx.x >> 3);
   const int gx = split ? (gridDim.x >> 4) : (gridDim.x >> 3);
   const int tq = ntiles / 8, tr = ntiles % 8;
-  const int csize = tq + (xcd < tr ? 1 : 0);
+  const int csize_all = tq + (xcd < tr ? 1 : 0);
   const int cbase = (xcd < tr) ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
+  // Quarter items (edge_quarter_items above): the last `nsplit` tiles of the XCD's range run as 4 quarter items each,
+  // behind the whole items.  With S = the resident workgroups of an XCD (EdgeArgs::tail_s / 8) and R = the XCD's tiles
+  // mod S, the tiles of the last round: R <= S/4 -> all R (one quarter item per workgroup at most, where a whole item
+  // would keep one CU busy for its full length); S/2 < R <= 3S/4 -> the last R - S/2 (the first S/2 fill every CU once,
+  // the quarter items go to the other workgroups first: qoff); otherwise none -- two whole items per CU are the
+  // steady state.  A pure function of the tile count and the grid, the same in every workgroup of the XCD.
+  constexpr bool QT = H == 256 && MODE == MODE_GCL && BPERM && EMU == 0 && !STORE;
+  int nsplit = 0, qoff = 0;
+  if constexpr (QT) {
+    if (p.tail_s > 0) {
+      const int S = max(p.tail_s >> 3, 1), R = csize_all % S;
+      if (4 * R <= S) nsplit = R;
+      else if (2 * R > S && 4 * R <= 3 * S) { nsplit = R - S / 2; qoff = gx >> 1; }
+    }
+  }
+  const int csize = csize_all - nsplit;                   // whole items of the XCD
+  const int nq = 4 * nsplit;
+  const int qu0 = kx >= qoff ? kx - qoff : kx - qoff + gx;   // this workgroup's first quarter item
   // Static round-robin over the XCD's tiles: local tiles kx, kx + gx, ... (with two resident workgroups per CU the static
   // order keeps the (kx, kx + n_CU) pairs of a CU balanced; a work queue measured 3 % slower, see the top of the file)
-  if (kx >= csize) return;
+  if (kx >= csize) {
+    if constexpr (QT) {
+      if (qu0 < nq) edge_quarter_items<H, MSG>(p, smem, qu0, gx, nq, cbase + csize, nt_a, E, E_b, att_b, inv_norm);
+    }
+    return;
+  }
 
 
   // ---- W2^T slice stream through staging registers --------------------------------------------------------
@@ -736,6 +998,10 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
       ++q;
     }
   }  // units
+  // this workgroup's quarter items (every wave is behind the last K step's barrier: the W2^T buffers are free)
+  if constexpr (QT) {
+    if (qu0 < nq) edge_quarter_items<H, MSG>(p, smem, qu0, gx, nq, cbase + csize, nt_a, E, E_b, att_b, inv_norm);
+  }
 }
 
 }  // namespace dsbdd

@@ -222,6 +222,9 @@ int dsbdd_engine_set_option(dsbdd_engine* e, int which, int value) {
       if (value != 0 && value != 6 && value != 9) return fail(DSBDD_ERR_ARG, "DSBDD_OPT_EMU takes 0, 6 or 9");
       e->emu = value; break;
     case DSBDD_OPT_SHELL: e->shell = value ? 1 : 0; break;
+    case DSBDD_OPT_TAIL:                                                           // 0 off, 1 on, n > 1: n resident workgroups in the rule
+      if (value < 0) return fail(DSBDD_ERR_ARG, "DSBDD_OPT_TAIL takes a value >= 0");
+      e->tail = value; break;
     default: return fail(DSBDD_ERR_ARG, "unknown option");
   }
   e->drop_graphs();
@@ -237,6 +240,7 @@ int dsbdd_engine_get_option(const dsbdd_engine* e, int which) {
     case DSBDD_OPT_SPLITK: return (int)e->splitk;
     case DSBDD_OPT_EMU: return e->emu;
     case DSBDD_OPT_SHELL: return e->shell;
+    case DSBDD_OPT_TAIL: return e->tail;
   }
   return fail(DSBDD_ERR_ARG, "unknown option");
 }

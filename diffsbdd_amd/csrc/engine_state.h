@@ -171,6 +171,8 @@ struct dsbdd_engine : Workspace {
   int cone = 1;                         // DSBDD_CONE=0: off, 1: when the cost model says it pays (default), 2: always
   int64_t ghost_slots = 0;              // slots of the ghost segment at the front of the level-ordered list
   int shell = 1;                        // DSBDD_OPT_SHELL: shell rows of the cone's ascending stages reuse the ghost rows' messages
+  int tail = 1;                         // DSBDD_OPT_TAIL: the last round of the exact H = 256 message launches on quarter items (edge_wave.h);
+                                        // 0 off, 1 on (default), n > 1: n in place of the resident workgroups in the rule (test hook); DSBDD_TAIL
   int64_t cap_shell = 0;                // slots of one shell list: a level's rows, one padded segment per sample
   // Memory of the shell stages: the shell lists (graph.h, LevelArgs::sh_*) and the messages of the ghost segment,
   // [ghost_slots][H].  The bound workspace keeps its recorded layout and the message buffer's size is the frame's, not
@@ -344,4 +346,5 @@ static void read_env_switches(dsbdd_engine* e) {
   if (env_int("DSBDD_CONE", &v)) e->cone = v <= 0 ? 0 : (v >= 2 ? 2 : 1);
   if (env_int("DSBDD_NODE_CHAIN_MIN_ROWS", &v) && v >= 0) e->chain_min_rows = v;
   if (env_int("DSBDD_EDGE_MAX_WG", &v) && v > 0) e->edge_max_wg = (int)v;
+  if (env_int("DSBDD_TAIL", &v) && v >= 0) e->tail = (int)v;
 }

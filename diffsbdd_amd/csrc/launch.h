@@ -113,17 +113,25 @@ static int edge_wave_grid(int mode, const EdgeArgs& a, int64_t edge_bound, int n
   return persistent_grid(split ? 2 * tiles : tiles, n_cu, 2, max_wg, split ? 16 : 8);   // 8 XCDs (x 2 MLPs)
 }
 
-static hipError_t launch_edge(const dsbdd_engine* e, hipStream_t s, int mode, const EdgeArgs& a,
+static hipError_t launch_edge(const dsbdd_engine* e, hipStream_t s, int mode, const EdgeArgs& a0,
                               int64_t edge_bound, bool g16 = false, bool sk = false) {
-  if (sk && a.mlp[0].W2SK) return launch_edge_sk(e, s, mode, a, edge_bound);
-  if (g16) return launch_edge16(e, s, mode, a, edge_bound);
-  const int grid = edge_wave_grid(mode, a, edge_bound, e->n_cu, e->edge_max_wg);
+  if (sk && a0.mlp[0].W2SK) return launch_edge_sk(e, s, mode, a0, edge_bound);
+  if (g16) return launch_edge16(e, s, mode, a0, edge_bound);
+  int grid = edge_wave_grid(mode, a0, edge_bound, e->n_cu, e->edge_max_wg);
+  const int emu = (e->emu && a0.mlp[0].W2E && a0.mlp[1].W2E) ? e->emu : 0;   // fp32 emulated on the bf16 matrix cores (engine option, opt-in)
+  EdgeArgs a = a0;
+  // quarter items (DSBDD_OPT_TAIL; edge_wave.h): the exact message kernels at hidden_nf 256 on the lane-grouped W2^T copy.
+  // The rule's S is the resident grid (or the option's value, a test hook); a tile may take four workgroups.
+  if (e->tail > 0 && mode == MODE_GCL && e->cfg.hidden_nf == 256 && !emu && a.mlp[0].W2TP && a.mlp[1].W2TP) {
+    const int resident = persistent_grid(INT64_MAX / 2, e->n_cu, 2, e->edge_max_wg, 8);
+    a.tail_s = e->tail > 1 ? e->tail : resident;
+    grid = persistent_grid((edge_bound + 127) / 128 * 4, e->n_cu, 2, e->edge_max_wg, 8);
+  }
   if (a.msg_out) {      // shell stage of the forward cone (forward.h): the default exact message kernel + the message store
     if (mode != MODE_GCL || e->cfg.hidden_nf != 256 || e->emu || !a.mlp[0].W2TP || a.wt_base) return hipErrorInvalidValue;
     hipLaunchKernelGGL((edge_wave_kernel<256, MODE_GCL, true, 0, false, true>), dim3(grid), dim3(kThreads), 0, s, a);
     return hipGetLastError();
   }
-  const int emu = (e->emu && a.mlp[0].W2E && a.mlp[1].W2E) ? e->emu : 0;   // fp32 emulated on the bf16 matrix cores (engine option, opt-in)
   return with_hidden(e->cfg.hidden_nf, [&](auto h) {
     constexpr int H = decltype(h)::value;
     return emu ? launch_wave_emu_t<H>(s, mode, a, grid, emu) : launch_wave_t<H>(s, mode, a, grid);

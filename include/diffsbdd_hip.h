@@ -253,9 +253,15 @@ int dsbdd_engine_last_plan(const dsbdd_engine* e, int32_t* radius, int32_t* ghos
  * keeps its layout; the message buffer's size is the frame's).  It is allocated by the first dsbdd_dynamics_forward that
  * runs a shell stage after dsbdd_engine_bind_workspace / dsbdd_engine_set_pocket_frame changed the capacities or enlarged
  * the ghost segment: that one call synchronises `stream`, drops the captured graphs and calls hipMalloc, so it must not be
- * issued while the caller is capturing `stream` (the engine's own graph cache runs its first call of a signature eagerly). */
+ * issued while the caller is capturing `stream` (the engine's own graph cache runs its first call of a signature eagerly).
+ * DSBDD_OPT_TAIL (environment DSBDD_TAIL; default 1): the exact message kernels at hidden_nf = 256 finish a launch's last, partly
+ * filled round of 128-edge tiles on QUARTER items -- a 32-edge wave tile evaluated by all four waves of a workgroup, split
+ * over the column tiles (csrc/edge_wave.h).  0 = whole items only (the launch sequence without the option), 1 = on,
+ * n > 1 = on with n in place of the resident workgroup count in the rule that picks the split tiles (a test hook: a launch
+ * of a few dozen tiles then holds whole rounds and a split remainder).  Every value gives the same bits: the split keeps
+ * every output's fmaf chain and every sum's order.  The workspace layout does not depend on it. */
 enum { DSBDD_OPT_PRUNE = 0, DSBDD_OPT_CONE = 1, DSBDD_OPT_GRANULE16 = 2, DSBDD_OPT_EMU = 3, DSBDD_OPT_SPLITK = 4,
-       DSBDD_OPT_SHELL = 5 };
+       DSBDD_OPT_SHELL = 5, DSBDD_OPT_TAIL = 6 };
 int dsbdd_engine_set_option(dsbdd_engine* e, int which, int value);
 /* current value of an option (what the environment / set_option left); DSBDD_ERR_ARG (< 0) for an unknown id */
 int dsbdd_engine_get_option(const dsbdd_engine* e, int which);

@@ -4,6 +4,11 @@
 // variants against each other (they differ in rounding only).  Test / measurement infrastructure, not product code.
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/microbench16.hip -o tools/bin/mb16 && tools/bin/mb16 [B] [reps] [ca]
+//
+// `tools/bin/mb16 [B] [reps] tail`: the quarter items of edge_wave.h (EdgeArgs::tail_s) instead -- a launch of only
+// quarter items against a launch of only whole items at 64 / 128 / 256 tiles, then launches of I tiles on the resident
+// grid with the last round on quarter items (tail_s = the resident workgroups) against whole items only, attention on
+// and off; every pair's agg and head-slot words are compared bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -72,6 +77,7 @@ int main(int argc, char** argv) {
   const int B = argc > 1 ? atoi(argv[1]) : 64;
   const int reps = argc > 2 ? atoi(argv[2]) : 20;
   const bool ca = argc > 3 && !strcmp(argv[3], "ca");
+  const bool tail = argc > 3 && !strcmp(argv[3], "tail");
   constexpr int H = 256;
   const int nl = 23, np = ca ? 36 : 286;
   const float boxw = ca ? 24.f : 17.5f, cut2 = ca ? 100.f : 25.f;      // C-alpha: ~ the density of the 3rfm CA pocket in model units x 2
@@ -170,6 +176,55 @@ int main(int argc, char** argv) {
   // rows whose edges lie in the prefix `cnt`: the completion kernels only look at rows [0, n_rows)
   auto rows_in = [&](int cnt) { int r = 0; while (r < N && row_ptr[r] + deg[r] <= cnt) ++r; return r; };
 
+  if (tail) {
+    float* d_head2 = dev_zero<float>(slots16 * H);
+    std::vector<int> cnt_h(1);
+    int* d_cnt = dev(cnt_h);
+    const int resident = 2 * n_cu;
+    // words that differ between the two launches' outputs (agg rows and head slots, both cleared before either launch)
+    auto differing = [&](const float* a, const float* b, size_t n) {
+      std::vector<unsigned> ha(n), hb(n);
+      CK(hipMemcpy(ha.data(), a, n * 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(hb.data(), b, n * 4, hipMemcpyDeviceToHost));
+      size_t d = 0, nz = 0;
+      for (size_t k = 0; k < n; ++k) { d += ha[k] != hb[k]; nz += ha[k] != 0; }
+      return std::make_pair(d, nz);
+    };
+    auto run = [&](int tiles, int tail_s, int grid, int attention, float* agg, float* head) {
+      cnt_h[0] = std::min(tiles * 128, E);
+      CK(hipMemcpy(d_cnt, cnt_h.data(), 4, hipMemcpyHostToDevice));
+      EdgeArgs a = edge_args(MODE_GCL, 0, agg);
+      a.e_count = d_cnt; a.agg_head = head; a.tail_s = tail_s; a.attention = attention;
+      CK(hipMemset(agg, 0, (size_t)N * H * 4)); CK(hipMemset(head, 0, slots16 * H * 4));
+      return time_us([&] { hipLaunchKernelGGL((edge_wave_kernel<H, MODE_GCL, true>), dim3(grid), dim3(kThreads), 0, 0, a); }, reps);
+    };
+    printf("| tiles (128 edges) | attention | whole items only: us (grid) | quarter items only: us (grid) | ratio | differing words / non-zero words |\n|---|---|---|---|---|---|\n");
+    for (int att : {1, 0})
+      for (int tiles : {64, 128, 256}) {
+        const int gw = grid32(MODE_GCL, tiles * 128), gq = std::min(resident, 4 * tiles);
+        // (either launch twice, alternating, the faster time of each: the first launch after the host-side comparison
+        //  of the previous row runs on a GPU that has clocked down)
+        float uw = run(tiles, 0, gw, att, d_agg[0], d_head);
+        float uq = run(tiles, 1 << 24, gq, att, d_agg[1], d_head2);      // S far above the tile count: every tile is split
+        uw = std::min(uw, run(tiles, 0, gw, att, d_agg[0], d_head));
+        uq = std::min(uq, run(tiles, 1 << 24, gq, att, d_agg[1], d_head2));
+        const auto da = differing(d_agg[0], d_agg[1], (size_t)N * H), dh = differing(d_head, d_head2, slots16 * H);
+        printf("| %d | %d | %.1f (%d) | %.1f (%d) | %.2f | %zu / %zu, heads %zu / %zu |\n", tiles, att, uw, gw, uq, gq, uq / uw, da.first, da.second,
+               dh.first, dh.second);
+      }
+    printf("\n| tiles I | I mod %d | whole items only: us | last round on quarter items: us | saved us | differing words / non-zero words |\n|---|---|---|---|---|---|\n", resident);
+    for (int extra : {0, 19, 64, 128, 160, 256, 288, 320, 384, 448})
+      for (int rounds : {1, 2, 4}) {
+        const int tiles = rounds * resident + extra;
+        if ((long)tiles * 128 > E) continue;
+        float uw = run(tiles, 0, resident, 1, d_agg[0], d_head);
+        float uq = run(tiles, resident, resident, 1, d_agg[1], d_head2);
+        uw = std::min(uw, run(tiles, 0, resident, 1, d_agg[0], d_head));
+        uq = std::min(uq, run(tiles, resident, resident, 1, d_agg[1], d_head2));
+        const auto da = differing(d_agg[0], d_agg[1], (size_t)N * H), dh = differing(d_head, d_head2, slots16 * H);
+        printf("| %d | %d | %.1f | %.1f | %.1f | %zu / %zu, heads %zu / %zu |\n", tiles, extra, uw, uq, uw - uq, da.first, da.second, dh.first, dh.second);
+      }
+    return 0;
+  }
   printf("| stage | edges | 32-edge us (grid) | frac | 16-edge us (grid 2/CU) | frac | 16-edge us (grid 3/CU) | max rel diff 16 vs 32 |\n|---|---|---|---|---|---|---|---|\n");
   for (int ci : {0, 3, 5, 2, 4, 1}) {
     const int cnt = counts[ci], nr = rows_in(cnt);
