@@ -18,7 +18,7 @@ def deps():
         [os.path.join(ROOT, "include", "diffsbdd_hip.h")]
 
 
-def kernel_source_hash(names=("edge_wave.h", "edge_mlp.h", "common.h")):
+def kernel_source_hash(names=("edge_wave.h", "edge_parts.h", "edge_mlp.h", "common.h")):
     """sha256 / 16 hex digits of the sources of the dominant kernel (edge_wave_kernel): what a PMC measurement of that
     kernel is valid for (tools/pmc_traffic.sh stamps it into profiles/<tag>_pmc_traffic.json, bench.py compares)."""
     import hashlib

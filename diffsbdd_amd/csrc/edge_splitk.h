@@ -1,4 +1,5 @@
-// Split-K variant of the fused edge-MLP kernels (same math, arguments and aggregation protocol as edge_wave.h / edge_mlp.h;
+// Split-K variant of the fused edge-MLP kernels (same math, arguments and aggregation protocol as edge_wave.h / edge_mlp.h,
+// through the shared functions of edge_parts.h;
 // reference: GCL.edge_model egnn_new.py:31-46, EquivariantUpdate.coord_model :96-122) for launches that do not fill the
 // chip with 128-edge workgroup tiles -- the latency regime (crossdock_ca_cond x 32: 153 tiles on 256 CUs; the
 // free-running full-atom chain: 272 - 509 tiles on 512 resident workgroups).
@@ -22,7 +23,7 @@
 //     two buffers, three barriers), after which wave w holds z2 of 32 edges x its H/4 columns (second-layer bias: the
 //     owner's accumulators start from it).  Attention dot / scalar head: per-wave partial sums over its columns
 //     (reduce16_half_wave), the four partials added in wave order through 512 bytes of LDS, one sigmoid per lane.
-//     Segmented row sums and the stores follow edge_wave.h on the wave's own columns: the same aggregation protocol (head
+//     Segmented row sums and the stores are edge_parts.h's on the wave's own columns: the same aggregation protocol (head
 //     slots per 32-edge tile), so every per-row sum is still a pure function of the sample's own data.
 //   * one work item = (32-edge tile, MLP); static round-robin inside each XCD's contiguous range, 2 workgroups per CU.
 //
@@ -102,6 +103,8 @@ __global__ __launch_bounds__(kThreads, 2) void edge_splitk_kernel(EdgeArgs p) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) load_b(0, i);
 
+  // per MLP: wd, wd0, tab0..2, b2, w-out.  Written out in each kernel on purpose: as a call to a shared function the
+  // compiler orders the prologue another way, and every launch waits for its prologue (profiles/edge_parts.md)
   for (int i = t; i < H; i += kThreads) {
     sV[i] = mw.wd[i];
     sV[H + i] = mw.wd0[i];
@@ -123,62 +126,29 @@ __global__ __launch_bounds__(kThreads, 2) void edge_splitk_kernel(EdgeArgs p) {
   const int xcd = blockIdx.x & 7;
   const int kx = split ? (blockIdx.x >> 4) : (blockIdx.x >> 3);
   const int gx = split ? (gridDim.x >> 4) : (gridDim.x >> 3);
-  const int tq = ntiles / 8, tr = ntiles % 8;
-  const int csize = tq + (xcd < tr ? 1 : 0);
-  const int cbase = (xcd < tr) ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
+  int cbase, csize;
+  xcd_range(ntiles, xcd, cbase, csize);
   if (kx >= csize) return;
 
   // ---- this lane's edge (current item) and the prefetched one (next item) ----------------
-  int my_r = -1, my_c = 0, my_ty = 0;
-  float my_d = 0.f, my_d0 = 0.f, xr[3] = {0.f, 0.f, 0.f}, xc[3] = {0.f, 0.f, 0.f};
-  int nx_r = -1, nx_c = 0;
-  int my_prev = -1, nx_prev = -1;      // row of the edge just before this tile (wave-uniform)
-  int my_wt = 0, nx_wt = 0;            // global wave-tile index
-  bool my_lb = false, nx_lb = false;   // the tile belongs to the stage's second list
-  float nx_d0 = 0.f, nxr[3] = {0.f, 0.f, 0.f}, nxc[3] = {0.f, 0.f, 0.f};
-  int vzero;
-  asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));
-  auto fetch_idx = [&](int tile) {
+  EdgeCursor eg;
+  auto request_tile = [&](int tile) {
     const bool lb = MODE == MODE_GCL && tile >= nt_a;
     const int tl = lb ? tile - nt_a : tile, El = lb ? E_b : E;
-    const int* er = lb ? p.erow_b : p.erow;
-    const int* ec = lb ? p.ecol_b : p.ecol;
-    const float* ed = lb ? p.ed0_b : p.ed0;
-    const int e0 = tl * BMW, e = e0 + j;
-    nx_r = -1; nx_c = 0; nx_d0 = 0.f; nx_prev = -1; nx_wt = (lb ? p.wt_base_b : p.wt_base) + tl; nx_lb = lb;
-    if (e < El) { nx_r = er[e]; nx_c = ec[e]; nx_d0 = ed[e]; }
-    if (e0 > 0 && e0 < El) nx_prev = er[e0 - 1 + vzero];
-  };
-  auto fetch_x = [&]() {
-    // entries that do not name two rows of this call (stale workspace words after an overflowed build) are inactive
-    if ((unsigned)nx_r >= (unsigned)p.n_nodes || (unsigned)nx_c >= (unsigned)p.n_nodes) { nx_r = -1; nx_c = 0; }
-    if (nx_r >= 0) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { nxr[k] = p.x[3 * nx_r + k]; nxc[k] = p.x[3 * nx_c + k]; }
-    }
-  };
-  auto commit_edge = [&]() {
-    my_r = nx_r; my_c = nx_c; my_d0 = nx_d0; my_d = 0.f; my_ty = 0;
-    my_prev = nx_prev; my_wt = nx_wt; my_lb = nx_lb;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { xr[k] = nxr[k]; xc[k] = nxc[k]; }
-    if (my_r >= 0) {
-      const float dx = xr[0] - xc[0], dy = xr[1] - xc[1], dz = xr[2] - xc[2];
-      my_d = dx * dx + dy * dy + dz * dz;                  // coord2diff radial, egnn_new.py:298-299
-      const bool rl = my_r < p.n_lig, cl = my_c < p.n_lig;
-      my_ty = (rl && cl) ? 1 : ((!rl && !cl) ? 2 : 0);     // dynamics.py:119-124
-    }
+    const int e0 = tl * BMW;
+    eg.request(lb ? p.erow_b : p.erow, lb ? p.ecol_b : p.ecol, lb ? p.ed0_b : p.ed0, e0, e0 + j, El,
+               (lb ? p.wt_base_b : p.wt_base) + tl, lb);
   };
 
-  fetch_idx(cbase + kx);
-  fetch_x();
-  commit_edge();
+  request_tile(cbase + kx);
+  eg.resolve(p);
+  eg.commit(p);
   __syncthreads();          // vectors visible
 
   // this lane's k of group g: w KW + 8 g + 4 half + i
   const int koff = w * KW + 4 * half;
-  const float* Pp = mw.P + (size_t)(my_r < 0 ? 0 : my_r) * p.ldpq + koff;
-  const float* Qp = mw.Q + (size_t)my_c * p.ldpq + koff;
+  const float* Pp = mw.P + (size_t)(eg.my_r < 0 ? 0 : eg.my_r) * p.ldpq + koff;
+  const float* Qp = mw.Q + (size_t)eg.my_c * p.ldpq + koff;
   f32x4 pc = ldv4(Pp), qc = ldv4(Qp);
   const float* vk = sV + koff;
 
@@ -196,8 +166,8 @@ __global__ __launch_bounds__(kThreads, 2) void edge_splitk_kernel(EdgeArgs p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[cl][r] = bv;
     }
-    const float* vt = vk + (2 + my_ty) * H;
-    const f32x2 dd = splat2(my_d), dz = splat2(my_d0);
+    const float* vt = vk + (2 + eg.my_ty) * H;
+    const f32x2 dd = splat2(eg.my_d), dz = splat2(eg.my_d0);
 
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
@@ -205,25 +175,17 @@ __global__ __launch_bounds__(kThreads, 2) void edge_splitk_kernel(EdgeArgs p) {
       if (g == 0) {
         next_li = li + gx;
         has_next = next_li < csize;
-        if (has_next) fetch_idx(cbase + next_li);
+        if (has_next) request_tile(cbase + next_li);
       }
-      if (g == 2 && has_next) fetch_x();
-      // A operand: SiLU((P + Q) + d wd + d0 wd0 + tab), the arithmetic of edge_wave.h
-      const f32x4 wd4 = *reinterpret_cast<const f32x4*>(vk + 8 * g);
-      const f32x4 wz4 = *reinterpret_cast<const f32x4*>(vk + H + 8 * g);
-      const f32x4 tb4 = *reinterpret_cast<const f32x4*>(vt + 8 * g);
-      f32x2 alo = pk_fma(dz, wz4.xy, pk_fma(dd, wd4.xy, pc.xy + qc.xy)) + tb4.xy;
-      f32x2 ahi = pk_fma(dz, wz4.zw, pk_fma(dd, wd4.zw, pc.zw + qc.zw)) + tb4.zw;
-      alo = silu2(alo);
-      ahi = silu2(ahi);
-      const float a[4] = {alo.x, alo.y, ahi.x, ahi.y};
+      if (g == 2 && has_next) eg.resolve(p);
+      const f32x4 a = first_layer_act4<H>(pc, qc, dd, dz, vk, vt, 8 * g);
       // the next chunk of this lane's P / Q rows (the last group: the first chunk of the next item's rows)
       if (g + 1 < NG) {
         pc = ldv4(Pp + 8 * (g + 1));
         qc = ldv4(Qp + 8 * (g + 1));
       } else if (has_next) {
-        Pp = mw.P + (size_t)(nx_r < 0 ? 0 : nx_r) * p.ldpq + koff;
-        Qp = mw.Q + (size_t)nx_c * p.ldpq + koff;
+        Pp = mw.P + (size_t)(eg.nx_r < 0 ? 0 : eg.nx_r) * p.ldpq + koff;
+        Qp = mw.Q + (size_t)eg.nx_c * p.ldpq + koff;
         pc = ldv4(Pp);
         qc = ldv4(Qp);
       }
@@ -265,24 +227,14 @@ __global__ __launch_bounds__(kThreads, 2) void edge_splitk_kernel(EdgeArgs p) {
     const bool last_item = !has_next;
     // ================= epilogue on this wave's OWN column tiles =================
     if (MODE == MODE_GCL) {
-      // messages m = SiLU(acc)   (egnn_new.py:18-19; the bias is already in the accumulators)
 #pragma unroll
-      for (int c = 0; c < OWN; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const f32x2 m2 = silu2(f32x2{acc[c][r], acc[c][r + 1]});
-          acc[c][r] = m2.x; acc[c][r + 1] = m2.y;
-        }
+      for (int c = 0; c < OWN; ++c) silu_tile(acc[c]);
       if (p.attention) {   // att = sigmoid(w_a . m + b_a): partial over this wave's columns, the four partials in wave order
         f32x2 part2[8];
 #pragma unroll
         for (int r = 0; r < 8; ++r) part2[r] = splat2(0.f);
 #pragma unroll
-        for (int c = 0; c < OWN; ++c) {
-          const f32x2 aw = splat2(sV[6 * H + feat(c)]);
-#pragma unroll
-          for (int r = 0; r < 8; ++r) part2[r] = pk_fma(f32x2{acc[c][2 * r], acc[c][2 * r + 1]}, aw, part2[r]);
-        }
+        for (int c = 0; c < OWN; ++c) att_accumulate(acc[c], sV[6 * H + feat(c)], part2);
         float part[16];
 #pragma unroll
         for (int r = 0; r < 8; ++r) { part[2 * r] = part2[r].x; part[2 * r + 1] = part2[r].y; }
@@ -295,66 +247,16 @@ __global__ __launch_bounds__(kThreads, 2) void edge_splitk_kernel(EdgeArgs p) {
         const float gate = sigmoidf_fast(dot + att_b);
         s_phi[16 * half + (j >> 1)] = gate;
         wave_lds_fence();
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-          const float4 g4 = *reinterpret_cast<const float4*>(s_phi + 16 * half + 4 * q4);
-          part[4 * q4] = g4.x; part[4 * q4 + 1] = g4.y; part[4 * q4 + 2] = g4.z; part[4 * q4 + 3] = g4.w;
-        }
+        gates_from_lds(s_phi, half, part);
         wave_lds_fence();   // the words are rewritten by the next item
 #pragma unroll
-        for (int c = 0; c < OWN; ++c)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[c][r] *= part[r];       // mij * att, egnn_new.py:40
+        for (int c = 0; c < OWN; ++c) scale_tile(acc[c], part);
       } else {
         __syncthreads();    // (keeps the barrier count of an item independent of the flag)
       }
-      // segmented sums over the tile's 32 rows on this wave's columns (edge_wave.h: accumulator register rr of half h is
-      // row 8 (rr >> 2) + 4 h + (rr & 3); every half adds up its rows of the running segment, the halves meet at a flush)
-      f32x2 sum2[OWN];
-#pragma unroll
-      for (int c = 0; c < OWN; ++c) sum2[c] = splat2(0.f);
-      int cur = -1;
-      const int row0 = __builtin_amdgcn_readlane(my_r, 0);
-      bool to_head = row0 >= 0 && row0 == __builtin_amdgcn_readfirstlane(my_prev);
-      auto flush = [&]() {
-        if (cur >= 0) {
-          float* dst = to_head ? (my_lb ? p.agg_head_b : p.agg_head) + (size_t)my_wt * H
-                               : (my_lb ? p.agg_b : p.agg) + (size_t)cur * H;
-          // half 0 receives and stores own tile 0, half 1 own tile 1
-          const float tot = pair_sum_halves(sum2[0].x + sum2[0].y, sum2[1].x + sum2[1].y);
-          dst[feat(half)] = tot * inv_norm;
-          to_head = false;
-        }
-#pragma unroll
-        for (int c = 0; c < OWN; ++c) sum2[c] = splat2(0.f);
-      };
-#pragma unroll
-      for (int gb = 0; gb < 8; ++gb) {
-        const int hh = gb & 1;
-#pragma unroll
-        for (int ip = 0; ip < 4; ip += 2) {
-          const int k = 4 * (gb >> 1) + ip;
-          const int rn0 = __builtin_amdgcn_readlane(my_r, 4 * gb + ip);
-          const int rn1 = __builtin_amdgcn_readlane(my_r, 4 * gb + ip + 1);
-          if (rn0 != cur) {
-            flush();
-            cur = rn0;
-          }
-          if (half == hh) {
-#pragma unroll
-            for (int c = 0; c < OWN; ++c) sum2[c].x += acc[c][k];
-          }
-          if (rn1 != rn0) {
-            flush();
-            cur = rn1;
-          }
-          if (half == hh) {
-#pragma unroll
-            for (int c = 0; c < OWN; ++c) sum2[c].y += acc[c][k + 1];
-          }
-        }
-      }
-      flush();
+      // segmented sums over the tile's 32 rows on this wave's own tiles: after the reduce-scatter they are acc[0] and
+      // acc[1] (NT = OWN = 2), the first two elements of acc[CT]; the other elements are not read
+      segmented_row_sums<H, OWN>(acc, p, eg, half, feat, inv_norm);
     } else {
       // scalar head: phi = w3 . SiLU(acc)   (egnn_new.py:80-92), partial over this wave's columns
       f32x2 part2[8];
@@ -375,68 +277,22 @@ __global__ __launch_bounds__(kThreads, 2) void edge_splitk_kernel(EdgeArgs p) {
       __syncthreads();
       if (w == 0) {
         const float ph = ((s_red[j] + s_red[32 + j]) + s_red[64 + j]) + s_red[96 + j];     // this lane's edge
-        // trans = u*phi + cross*phi_x   (egnn_new.py:100-109, 296-316); lane = edge; this workgroup adds its MLP's term
-        float tx = 0.f, ty = 0.f, tz = 0.f;
-        if (my_r >= 0) {
-          if (qsel == 0) {
-            const float dx = xr[0] - xc[0], dy = xr[1] - xc[1], dzz = xr[2] - xc[2];
-            const float den = sqrtf(my_d + 1e-8f) + p.norm_constant;
-            const float ux = dx / den, uy = dy / den, uz = dzz / den;
-            if (p.use_tanh) {
-              const float th = tanhf(ph);
-              tx = ux * th * p.coords_range; ty = uy * th * p.coords_range; tz = uz * th * p.coords_range;
-            } else {
-              tx = ux * ph; ty = uy * ph; tz = uz * ph;
-            }
-          } else {
-            const int b = p.node_batch[my_r];
-            const float m0 = p.mean[3 * b], m1 = p.mean[3 * b + 1], m2 = p.mean[3 * b + 2];
-            const float a0 = xr[0] - m0, a1 = xr[1] - m1, a2 = xr[2] - m2;
-            const float b0 = xc[0] - m0, b1 = xc[1] - m1, b2 = xc[2] - m2;
-            const float c0 = a1 * b2 - a2 * b1, c1 = a2 * b0 - a0 * b2, c2 = a0 * b1 - a1 * b0;
-            const float cden = sqrtf(c0 * c0 + c1 * c1 + c2 * c2) + p.norm_constant;
-            float phx = ph;
-            if (p.use_tanh) phx = tanhf(phx) * p.coords_range;
-            tx = c0 / cden * phx; ty = c1 / cden * phx; tz = c2 / cden * phx;
-          }
-        }
-        if (half == 0) { s_tr[3 * j] = tx; s_tr[3 * j + 1] = ty; s_tr[3 * j + 2] = tz; }
+        // lane = edge; this workgroup adds its MLP's term
+        float tr[3];
+        edge_translation(p, eg, qsel == 0, qsel != 0, ph, ph, tr);
+        if (half == 0) { s_tr[3 * j] = tr[0]; s_tr[3 * j + 1] = tr[1]; s_tr[3 * j + 2] = tr[2]; }
         wave_lds_fence();
         float trv[32];
 #pragma unroll
         for (int e = 0; e < 32; ++e) trv[e] = s_tr[3 * e + (lane < 3 ? lane : 0)];
-        if (lane < 3) {
-          float* xa = p.xagg + qsel * p.xagg_stride;
-          float* xh = p.xagg_head + qsel * p.xhead_stride;
-          const int row0 = __builtin_amdgcn_readlane(my_r, 0);
-          bool to_head = row0 >= 0 && row0 == __builtin_amdgcn_readfirstlane(my_prev);
-          int cur = -1;
-          float sum = 0.f;
-          auto put = [&]() {
-            if (cur >= 0) {
-              const float v = sum / p.norm_factor;
-              if (to_head) xh[4 * (size_t)my_wt + lane] = v; else xa[(size_t)cur * 3 + lane] = v;
-              to_head = false;
-            }
-          };
-#pragma unroll
-          for (int e = 0; e < 32; ++e) {
-            const int rn = __builtin_amdgcn_readlane(my_r, e);
-            if (rn != cur) {
-              put();
-              cur = rn;
-              sum = 0.f;
-            }
-            sum += trv[e];
-          }
-          put();
-        }
+        segmented_sum3<32>(trv, eg.my_r, eg.my_prev, lane, p.xagg + qsel * p.xagg_stride, p.xagg_head + qsel * p.xhead_stride,
+                           eg.my_wt, p.norm_factor);
         wave_lds_fence();   // scratch is reused by the next item
       }
     }
 
     if (last_item) break;
-    commit_edge();
+    eg.commit(p);
     li = next_li;
   }
 }

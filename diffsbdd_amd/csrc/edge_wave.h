@@ -1,5 +1,7 @@
 // Third structure of the fused edge-MLP kernels (same math and arguments as
-// edge_mlp.h -- see there for the algorithm and the reference citations).
+// edge_mlp.h -- see there for the algorithm and the reference citations).  This file holds the tiling, the W2^T stream
+// and the column ownership of the default kernel and of its quarter items; the parts it shares with edge_splitk.h and
+// edge_wave16.h -- first-layer activation, edge prefetch, gate, segmented sums, translation -- are in edge_parts.h.
 //
 // What the hardware counters said about the LDS-tiled kernel (rocprofv3 --pmc,
 // profiles/): matrix pipe 52 % busy; every wave parked 28 % of its time at
@@ -43,6 +45,7 @@
 #pragma once
 #include "common.h"
 #include "edge_mlp.h"
+#include "edge_parts.h"
 #include "graph.h"
 
 namespace dsbdd {
@@ -65,66 +68,6 @@ struct WaveLayout {
   static constexpr int B_OFF = (SCR_OFF + 4 * SCR_PER + 4 + 255) / 256 * 256;   // [2][BK][H], 1 KB aligned
   static constexpr int TOTAL = B_OFF + 2 * B_BUF;
 };
-
-__device__ __forceinline__ void wave_lds_fence() {
-  // LDS operations of one wave complete in order; this only stops the compiler
-  // from moving the later reads above the earlier writes.
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-
-// ---- cross-lane helpers of the wave-private epilogue (gfx950: v_permlane{16,32}_swap, DPP) -----------------
-// Lane exchanges never go through the LDS crossbar (ds_bpermute, what __shfl_xor compiles to): the two swaps move a
-// whole 16- / 32-lane row between two registers in one VALU instruction, the rest are DPP operands.
-__device__ __forceinline__ float dpp_xor1(float v) {   // quad_perm [1,0,3,2]
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float dpp_xor2(float v) {   // quad_perm [2,3,0,1]
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float dpp_half_mirror(float v) {   // lane i <-> 7 - i inside every group of 8
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float dpp_ror8(float v) {   // lane i <-> i ^ 8 inside every row of 16
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xF, 0xF, true));
-}
-// p: this lane keeps it when its row (16 lanes) is even; q: kept when odd.  Returns own kept value + the partner row's
-// (lane ^ 16) value of the same register.
-__device__ __forceinline__ float pair_sum_rows16(float p, float q) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(p), __float_as_uint(q), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-// the same across the two 32-lane halves: half 0 gets p(own) + p(lane + 32), half 1 gets q(lane - 32) + q(own)
-__device__ __forceinline__ float pair_sum_halves(float p, float q) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(p), __float_as_uint(q), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// Sum of 16 per-lane values over the 32 lanes of a half-wave as a reduce-scatter: every step halves the number of
-// registers a lane carries (16 + 8 + 4 + 2 + 1 exchanges instead of 5 x 16 for a butterfly on every register).
-// On return lane j of either half holds the total of register  rs_index(j) = j >> 1.
-__device__ __forceinline__ float reduce16_half_wave(const float (&part)[16], int j) {
-  float k8[8], k4[4], k2[2];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) k8[i] = pair_sum_rows16(part[i], part[i + 8]);          // lanes ^ 16: keep [8 b4, +8)
-  const bool b3 = (j >> 3) & 1, b2 = (j >> 2) & 1, b1 = (j >> 1) & 1;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {                                                       // lanes ^ 8: keep [.. + 4 b3, +4)
-    const float send = b3 ? k8[i] : k8[i + 4], keep = b3 ? k8[i + 4] : k8[i];
-    k4[i] = keep + dpp_ror8(send);
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {                                                       // lane i <-> 7 - i: keep [.. + 2 b2, +2)
-    const float send = b2 ? k4[i] : k4[i + 2], keep = b2 ? k4[i + 2] : k4[i];
-    k2[i] = keep + dpp_half_mirror(send);
-  }
-  const float send = b1 ? k2[0] : k2[1], keep = b1 ? k2[1] : k2[0];                   // lanes ^ 2: keep [.. + b1]
-  const float k1 = keep + dpp_xor2(send);
-  return k1 + dpp_xor1(k1);                                                           // lanes ^ 1: both hold the total
-}
 
 // ---- emulated path (EMU = 6 / 9): fp32 on the bf16 matrix cores ------------------------------------------------------
 // The fp32 MFMA runs at 1/16 of the bf16 MFMA rate on gfx950 (MI355X_MICROARCH.md), and it runs ON the vector ALUs.  The
@@ -170,13 +113,14 @@ __global__ __launch_bounds__(256) void pack_w2e_kernel(const float* __restrict__
 // QUARTER items instead: one 32-edge wave tile evaluated by all four waves of a workgroup, wave w owning the accumulator
 // tiles {2w, 2w + 1} of the eight.  Every output element keeps its fmaf chain over k and every sum its operands and
 // order, so the result is the whole item's bit for bit:
-//   * every wave evaluates the A operand of all k for the tile's 32 edges (the same expressions; the redundancy is
+//   * every wave evaluates the A operand of all k for the tile's 32 edges (the same function; the redundancy is
 //     paid on these tiles only), the W2^T slices stream through LDS as in the main loop, a wave reads only its columns;
 //   * the attention logit is ONE fma chain over the accumulator tiles c = 0 .. 7 per lane: wave w continues the chain
 //     that wave w - 1 left in LDS (16 floats per lane, three hand-offs, a workgroup barrier each), wave 3 reduces, takes
 //     the sigmoids and the gates go back to all waves through LDS;
-//   * the segmented row sums follow the rules of the main loop for the wave's two tiles; at a flush the halves exchange
-//     the same two partial sums (half 0 ends with tile 2w, half 1 with tile 2w + 1) and store them to the same address;
+//   * the segmented row sums are the main loop's function (segmented_row_sums, edge_parts.h) on the wave's two tiles: at a
+//     flush the halves exchange the same two partial sums (half 0 ends with tile 2w, half 1 with tile 2w + 1) and store
+//     them to the same address;
 //   * the shell instantiation's message store writes the wave's columns of the same rows.
 // Item u of the workgroup's share is wave tile (u & 3) of 128-edge tile tile0 + (u >> 2); u = u0, u0 + ustep, ... < nq.
 // The second half of the W2^T double buffer carries the hand-off: nobody reads it between the last K step's barrier
@@ -202,21 +146,17 @@ __device__ __forceinline__ void edge_quarter_items(const EdgeArgs& p, float* sme
   const int boff = j * CT + (w < 2 ? 4 * swb + c0 : 4 - 4 * swb + (c0 - 4));
   const float* W2 = p.mlp[0].W2TP;
 
+  const auto feat_of = [&](int c) { return c ? feat1 : feat0; };
 #pragma unroll 1
   for (int u = u0; u < nq; u += ustep) {
     const int tile = tile0 + (u >> 2), sub = u & 3;
     const bool lb = tile >= nt_a;                         // a tile of the second list
     const int tl = lb ? tile - nt_a : tile, El = lb ? E_b : E;
-    const int* er = lb ? p.erow_b : p.erow;
-    const int* ec = lb ? p.ecol_b : p.ecol;
-    const float* ed = lb ? p.ed0_b : p.ed0;
-    const int e0 = tl * BMB + sub * BMW, e = e0 + j;
+    const int e0 = tl * BMB + sub * BMW;
     if (e0 >= El) continue;                               // a wave tile behind the list's end: nothing to write
-    const int my_wt = (lb ? p.wt_base_b : p.wt_base) + tl * 4 + sub;
-    int my_r = -1, my_c = 0, my_ty = 0, my_prev = -1;
-    float my_d0 = 0.f, my_d = 0.f;
-    if (e < El) { my_r = er[e]; my_c = ec[e]; my_d0 = ed[e]; }
-    if (e0 > 0) my_prev = er[e0 - 1];
+    EdgeCursor eg;
+    eg.request(lb ? p.erow_b : p.erow, lb ? p.ecol_b : p.ecol, lb ? p.ed0_b : p.ed0, e0, e0 + j, El,
+               (lb ? p.wt_base_b : p.wt_base) + tl * 4 + sub, lb);
     // first W2^T slice
     {
       f32x4 s0[BI];
@@ -225,27 +165,19 @@ __device__ __forceinline__ void edge_quarter_items(const EdgeArgs& p, float* sme
 #pragma unroll
       for (int i = 0; i < BI; ++i) *reinterpret_cast<f32x4*>(sB + kThreads * 4 * i + t * 4) = s0[i];
     }
-    if ((unsigned)my_r >= (unsigned)p.n_nodes || (unsigned)my_c >= (unsigned)p.n_nodes) { my_r = -1; my_c = 0; }
-    if (my_r >= 0) {
-      float xr[3], xc[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { xr[k] = p.x[3 * my_r + k]; xc[k] = p.x[3 * my_c + k]; }
-      const float dx = xr[0] - xc[0], dy = xr[1] - xc[1], dz = xr[2] - xc[2];
-      my_d = dx * dx + dy * dy + dz * dz;
-      const bool rl = my_r < p.n_lig, cl = my_c < p.n_lig;
-      my_ty = (rl && cl) ? 1 : ((!rl && !cl) ? 2 : 0);
-    }
-    const float* Pp = p.mlp[0].P + (size_t)(my_r < 0 ? 0 : my_r) * p.ldpq + 4 * half;
-    const float* Qp = p.mlp[0].Q + (size_t)my_c * p.ldpq + 4 * half;
+    eg.resolve(p);
+    eg.commit(p);
+    const float* Pp = p.mlp[0].P + (size_t)(eg.my_r < 0 ? 0 : eg.my_r) * p.ldpq + 4 * half;
+    const float* Qp = p.mlp[0].Q + (size_t)eg.my_c * p.ldpq + 4 * half;
     f32x4 pc = ldv4(Pp), qc = ldv4(Qp), pn = pc, qn4 = qc;
-    f32x16 acc0, acc1;
+    f32x16 acc[2];
     __syncthreads();          // sV + slice 0 visible
     {
       const float b0 = vq[5 * H + feat0], b1 = vq[5 * H + feat1];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) { acc0[r] = b0; acc1[r] = b1; }
+      for (int r = 0; r < 16; ++r) { acc[0][r] = b0; acc[1][r] = b1; }
     }
-    const f32x2 dd = splat2(my_d), dz = splat2(my_d0);
+    const f32x2 dd = splat2(eg.my_d), dz = splat2(eg.my_d0);
 
 #pragma unroll 1
     for (int kt = 0; kt < NK; ++kt) {
@@ -258,7 +190,7 @@ __device__ __forceinline__ void edge_quarter_items(const EdgeArgs& p, float* sme
       }
       const float* bcur = sB + (kt & 1) * L::B_BUF + (4 * half) * H + boff;
       const float* vk = vq + kt * BK + 4 * half;           // this lane's k = kt*BK + 8g + 4*half + i
-      const float* vt = vk + (2 + my_ty) * H;
+      const float* vt = vk + (2 + eg.my_ty) * H;
 #pragma unroll
       for (int g = 0; g < BK / 8; ++g) {
         const int kb = kt * BK + 8 * g;
@@ -266,21 +198,13 @@ __device__ __forceinline__ void edge_quarter_items(const EdgeArgs& p, float* sme
           pn = ldv4(Pp + kb + 8);
           qn4 = ldv4(Qp + kb + 8);
         }
-        // A operand: the main loop's expressions
-        const f32x4 wd4 = *reinterpret_cast<const f32x4*>(vk + 8 * g);
-        const f32x4 wz4 = *reinterpret_cast<const f32x4*>(vk + H + 8 * g);
-        const f32x4 tb4 = *reinterpret_cast<const f32x4*>(vt + 8 * g);
-        f32x2 alo = pk_fma(dz, wz4.xy, pk_fma(dd, wd4.xy, pc.xy + qc.xy)) + tb4.xy;
-        f32x2 ahi = pk_fma(dz, wz4.zw, pk_fma(dd, wd4.zw, pc.zw + qc.zw)) + tb4.zw;
-        alo = silu2(alo);
-        ahi = silu2(ahi);
-        const float a[4] = {alo.x, alo.y, ahi.x, ahi.y};
+        const f32x4 a = first_layer_act4<H>(pc, qc, dd, dz, vk, vt, 8 * g);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const f32x2 bv = *reinterpret_cast<const f32x2*>(bcur + (8 * g + i) * H);
-          acc0 = mfma32(a[i], bv.x, acc0);
-          acc1 = mfma32(a[i], bv.y, acc1);
+          acc[0] = mfma32(a[i], bv.x, acc[0]);
+          acc[1] = mfma32(a[i], bv.y, acc[1]);
         }
         __builtin_amdgcn_s_setprio(0);
         pc = pn; qc = qn4;
@@ -294,16 +218,8 @@ __device__ __forceinline__ void edge_quarter_items(const EdgeArgs& p, float* sme
     }
 
     // ---- epilogue: the main loop's, for accumulator tiles c0 and c0 + 1 ----
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-      const f32x2 m0 = silu2(f32x2{acc0[r], acc0[r + 1]});
-      acc0[r] = m0.x; acc0[r + 1] = m0.y;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-      const f32x2 m1 = silu2(f32x2{acc1[r], acc1[r + 1]});
-      acc1[r] = m1.x; acc1[r + 1] = m1.y;
-    }
+    silu_tile(acc[0]);
+    silu_tile(acc[1]);
     if (p.attention) {
       float part[16];
 #pragma unroll
@@ -320,11 +236,8 @@ __device__ __forceinline__ void edge_quarter_items(const EdgeArgs& p, float* sme
               part2[2 * q4] = h4.xy; part2[2 * q4 + 1] = h4.zw;
             }
           }
-          const f32x2 aw0 = splat2(vq[6 * H + feat0]), aw1 = splat2(vq[6 * H + feat1]);
-#pragma unroll
-          for (int r = 0; r < 8; ++r) part2[r] = pk_fma(f32x2{acc0[2 * r], acc0[2 * r + 1]}, aw0, part2[r]);
-#pragma unroll
-          for (int r = 0; r < 8; ++r) part2[r] = pk_fma(f32x2{acc1[2 * r], acc1[2 * r + 1]}, aw1, part2[r]);
+          att_accumulate(acc[0], vq[6 * H + feat0], part2);
+          att_accumulate(acc[1], vq[6 * H + feat1], part2);
           if (s < 3) {
 #pragma unroll
             for (int q4 = 0; q4 < 4; ++q4) {
@@ -335,72 +248,30 @@ __device__ __forceinline__ void edge_quarter_items(const EdgeArgs& p, float* sme
           } else {
 #pragma unroll
             for (int r = 0; r < 8; ++r) { part[2 * r] = part2[r].x; part[2 * r + 1] = part2[r].y; }
-            const float gate = sigmoidf_fast(reduce16_half_wave(part, j) + att_b);
-            s_gate[16 * half + (j >> 1)] = gate;
+            s_gate[16 * half + (j >> 1)] = sigmoidf_fast(reduce16_half_wave(part, j) + att_b);
           }
         }
         __syncthreads();
       }
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const float4 g4 = *reinterpret_cast<const float4*>(s_gate + 16 * half + 4 * q4);
-        part[4 * q4] = g4.x; part[4 * q4 + 1] = g4.y; part[4 * q4 + 2] = g4.z; part[4 * q4 + 3] = g4.w;
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc0[r] *= part[r];     // mij * att
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc1[r] *= part[r];
+      gates_from_lds(s_gate, half, part);
+      scale_tile(acc[0], part);
+      scale_tile(acc[1], part);
     }
     if constexpr (MSG) {
-      if (!lb && my_wt < p.msg_tiles) {                    // (wt_base == 0: the list starts at slot 0)
+      if (!lb && eg.my_wt < p.msg_tiles) {                 // (wt_base == 0: the list starts at slot 0)
         float* mb = p.msg_out + (size_t)e0 * H + (4 * half) * H;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int row = 8 * (r >> 2) + 4 * half + (r & 3);
           if (e0 + row < E) {
-            mb[(8 * (r >> 2) + (r & 3)) * H + feat0] = acc0[r];
-            mb[(8 * (r >> 2) + (r & 3)) * H + feat1] = acc1[r];
+            mb[(8 * (r >> 2) + (r & 3)) * H + feat0] = acc[0][r];
+            mb[(8 * (r >> 2) + (r & 3)) * H + feat1] = acc[1][r];
           }
         }
       }
     }
-    // segmented row sums (the main loop's walk; two column tiles)
-    f32x2 sum0 = splat2(0.f), sum1 = splat2(0.f);
-    int cur = -1;
-    const int row0 = __builtin_amdgcn_readlane(my_r, 0);
-    bool to_head = row0 >= 0 && row0 == __builtin_amdgcn_readfirstlane(my_prev);
-    auto flush = [&]() {
-      if (cur >= 0) {
-        float* dst = to_head ? (lb ? p.agg_head_b : p.agg_head) + (size_t)my_wt * H
-                             : (lb ? p.agg_b : p.agg) + (size_t)cur * H;
-        // half 0: tile c0, half 1: tile c0 + 1 (its own partial sum + the other half's)
-        const float tot = pair_sum_halves(sum0.x + sum0.y, sum1.x + sum1.y);
-        dst[half ? feat1 : feat0] = tot * inv_norm;
-        to_head = false;
-      }
-      sum0 = splat2(0.f); sum1 = splat2(0.f);
-    };
-#pragma unroll
-    for (int gb = 0; gb < 8; ++gb) {
-      const int hh = gb & 1;
-#pragma unroll
-      for (int ip = 0; ip < 4; ip += 2) {
-        const int k = 4 * (gb >> 1) + ip;
-        const int rn0 = __builtin_amdgcn_readlane(my_r, 4 * gb + ip);
-        const int rn1 = __builtin_amdgcn_readlane(my_r, 4 * gb + ip + 1);
-        if (rn0 != cur) {
-          flush();
-          cur = rn0;
-        }
-        if (half == hh) { sum0.x += acc0[k]; sum1.x += acc1[k]; }
-        if (rn1 != rn0) {
-          flush();
-          cur = rn1;
-        }
-        if (half == hh) { sum0.y += acc0[k + 1]; sum1.y += acc1[k + 1]; }
-      }
-    }
-    flush();
+    // half 0 ends with tile c0, half 1 with tile c0 + 1
+    segmented_row_sums<H, 2>(acc, p, eg, half, feat_of, inv_norm);
   }
 }
 
@@ -439,7 +310,7 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
   float* sB = smem + L::B_OFF;              // [2][BK][H]
   float* sV = smem + L::VEC_OFF;            // per MLP: wd, wd0, tab0..2, b2, w-out
   const int t = threadIdx.x, lane = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);     // wave index as a scalar: LDS-DMA bases stay in SGPRs
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int half = lane >> 5, j = lane & 31;
   float* s_phi = smem + L::SCR_OFF + w * L::SCR_PER;   // [32]
   float* s_tr = s_phi;                                  // [32][3] (phi is consumed before trans is written)
@@ -449,6 +320,8 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
 
   for (int q = 0; q < n_pass; ++q) {
     const EdgeMlpW& mw = p.mlp[qsel + q];
+    // per MLP: wd, wd0, tab0..2, b2, w-out.  Written out in each kernel on purpose: as a call to a shared function the
+    // compiler orders the prologue another way, and every launch waits for its prologue (profiles/edge_parts.md)
     float* v = sV + q * L::VEC_PER;
     for (int i = t; i < H; i += kThreads) {
       v[i] = mw.wd[i];
@@ -461,8 +334,6 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
     }
   }
   const float att_b = (MODE == MODE_GCL && p.attention) ? p.att_b[0] : 0.f;
-  // aggregate / normalization_factor (egnn_new.py:328-329) as one multiply per flushed
-  // segment (<= 1 ulp from the reference's division)
   const float inv_norm = 1.0f / p.norm_factor;
 
   const int swb = (bperm && CT == 8) ? ((j >> 3) & 1) : 0;          // this lane reads its halves swapped
@@ -475,9 +346,8 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
   const int xcd = blockIdx.x & 7;
   const int kx = split ? (blockIdx.x >> 4) : (blockIdx.x >> 3);
   const int gx = split ? (gridDim.x >> 4) : (gridDim.x >> 3);
-  const int tq = ntiles / 8, tr = ntiles % 8;
-  const int csize_all = tq + (xcd < tr ? 1 : 0);
-  const int cbase = (xcd < tr) ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
+  int cbase, csize_all;
+  xcd_range(ntiles, xcd, cbase, csize_all);
   // Quarter items (edge_quarter_items above): the last `nsplit` tiles of the XCD's range run as 4 quarter items each,
   // behind the whole items.  With S = the resident workgroups of an XCD (EdgeArgs::tail_s / 8) and R = the XCD's tiles
   // mod S, the tiles of the last round: R <= S/4 -> all R (one quarter item per workgroup at most, where a whole item
@@ -530,48 +400,15 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
       *reinterpret_cast<stg_t*>(dst + kThreads * UNIT * i) = stg[EMU ? i : i - stage_lo(g)];
   };
 
-  // ---- this lane's edge (current unit) and the prefetched one (next tile) ----------------
-  int my_r = -1, my_c = 0, my_ty = 0;
-  float my_d = 0.f, my_d0 = 0.f, xr[3] = {0.f, 0.f, 0.f}, xc[3] = {0.f, 0.f, 0.f};
-  int nx_r = -1, nx_c = 0;
-  int my_prev = -1, nx_prev = -1;      // row of the edge just before this wave tile (wave-uniform)
-  int my_wt = 0, nx_wt = 0;            // global wave-tile index
-  bool my_lb = false, nx_lb = false;   // the tile belongs to the stage's second list
-  float nx_d0 = 0.f, nxr[3] = {0.f, 0.f, 0.f}, nxc[3] = {0.f, 0.f, 0.f};
-  int vzero;                           // 0 in a vector register the compiler cannot see through
-  asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));
-  // fetch_idx only REQUESTS the next tile's indices; they are looked at one K step later (fetch_x: range check, then
-  // the coordinates), so that no wave waits for a global load at the top of a K step
-  auto fetch_idx = [&](int tile) {
+  // ---- this lane's edge (current unit) and the prefetched one (next tile): requested at the first K step of a unit,
+  // resolved one K step later, so that no wave waits for a global load at the top of a K step
+  EdgeCursor eg;
+  auto request_tile = [&](int tile) {
     const bool lb = MODE == MODE_GCL && tile >= nt_a;     // a tile of the second list (wave-uniform)
     const int tl = lb ? tile - nt_a : tile, El = lb ? E_b : E;
-    const int* er = lb ? p.erow_b : p.erow;
-    const int* ec = lb ? p.ecol_b : p.ecol;
-    const float* ed = lb ? p.ed0_b : p.ed0;
-    const int e0 = tl * BMB + w * BMW, e = e0 + j;
-    nx_r = -1; nx_c = 0; nx_d0 = 0.f; nx_prev = -1; nx_wt = (lb ? p.wt_base_b : p.wt_base) + tl * 4 + w; nx_lb = lb;
-    if (e < El) { nx_r = er[e]; nx_c = ec[e]; nx_d0 = ed[e]; }
-    if (e0 > 0 && e0 < El) nx_prev = er[e0 - 1 + vzero];   // (a per-lane load: nothing waits for it here)
-  };
-  auto fetch_x = [&]() {
-    // entries that do not name two rows of this call (stale workspace words after an overflowed build) are inactive
-    if ((unsigned)nx_r >= (unsigned)p.n_nodes || (unsigned)nx_c >= (unsigned)p.n_nodes) { nx_r = -1; nx_c = 0; }
-    if (nx_r >= 0) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { nxr[k] = p.x[3 * nx_r + k]; nxc[k] = p.x[3 * nx_c + k]; }
-    }
-  };
-  auto commit_edge = [&]() {
-    my_r = nx_r; my_c = nx_c; my_d0 = nx_d0; my_d = 0.f; my_ty = 0;
-    my_prev = nx_prev; my_wt = nx_wt; my_lb = nx_lb;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { xr[k] = nxr[k]; xc[k] = nxc[k]; }
-    if (my_r >= 0) {
-      const float dx = xr[0] - xc[0], dy = xr[1] - xc[1], dz = xr[2] - xc[2];
-      my_d = dx * dx + dy * dy + dz * dz;                  // coord2diff radial, egnn_new.py:298-299
-      const bool rl = my_r < p.n_lig, cl = my_c < p.n_lig;
-      my_ty = (rl && cl) ? 1 : ((!rl && !cl) ? 2 : 0);     // dynamics.py:119-124
-    }
+    const int e0 = tl * BMB + w * BMW;
+    eg.request(lb ? p.erow_b : p.erow, lb ? p.ecol_b : p.ecol, lb ? p.ed0_b : p.ed0, e0, e0 + j, El,
+               (lb ? p.wt_base_b : p.wt_base) + tl * 4 + w, lb);
   };
 
   // B values of one MFMA step: column j of every column tile (plain layout: CT 4-byte reads at stride 32) or
@@ -593,16 +430,16 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
   // prologue: first W2^T slice, first edge, first P/Q chunk
 #pragma unroll
   for (int g = 0; g < NG; ++g) { stage_load(0, 0, g); stage_store(0, g); }
-  fetch_idx(cbase + kx);
-  fetch_x();
-  commit_edge();
+  request_tile(cbase + kx);
+  eg.resolve(p);
+  eg.commit(p);
   __syncthreads();          // sV + slice 0 visible
   int bslice = 0;           // running slice counter (buffer = bslice & 1)
 
   // this lane's k of a step: exact path 8 g + 4 half + i (float4 chunks), emulated path 16 kt + 8 half + i (two float4)
   constexpr int KH = EMU ? 8 : 4;
-  const float* Pp = p.mlp[qsel].P + (size_t)(my_r < 0 ? 0 : my_r) * p.ldpq + KH * half;
-  const float* Qp = p.mlp[qsel].Q + (size_t)my_c * p.ldpq + KH * half;
+  const float* Pp = p.mlp[qsel].P + (size_t)(eg.my_r < 0 ? 0 : eg.my_r) * p.ldpq + KH * half;
+  const float* Qp = p.mlp[qsel].Q + (size_t)eg.my_c * p.ldpq + KH * half;
   f32x4 pc = ldv4(Pp), qc = ldv4(Qp), pn = pc, qn4 = qc;
   f32x4 pc1 = pc, qc1 = qc;                                // emulated path: second half of the 8-float chunk
   if constexpr (EMU != 0) { pc1 = ldv4(Pp + 4); qc1 = ldv4(Qp + 4); }
@@ -636,13 +473,13 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
       if (st == 0) {
         next_li = li + gx;
         has_next = next_li < csize;
-        if (has_next) fetch_idx(cbase + next_li);
+        if (has_next) request_tile(cbase + next_li);
       }
-      if (st == 1 && has_next) fetch_x();
+      if (st == 1 && has_next) eg.resolve(p);
       // the next W2^T slice: a continuous stream across units (the last K step of a workgroup re-reads slice 0 of
       // its MLP: never used; unconditional, so that the compiler counts the loads in flight exactly)
       const int sq = more ? q : qn, sks = more ? kt + 1 : 0;
-      const f32x2 dd = splat2(my_d), dz = splat2(my_d0);
+      const f32x2 dd = splat2(eg.my_d), dz = splat2(eg.my_d0);
       if constexpr (EMU != 0) {
         // ---- emulated path: one 16-k step = 8 activations per lane, split into three bf16x8, 6 (9) MFMAs per column tile.
         // Order of a step: the step's activations, the next P / Q chunk requested, then per pair of column tiles the three
@@ -652,20 +489,9 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
         constexpr int NG1 = (NG + 1) / 2;
         auto act8 = [&](int ks, bf16x8& o_h, bf16x8& o_m, bf16x8& o_l) {       // activations of k step ks from pc / qc
           const float* vk = vq + ks * 16 + 8 * half;       // this lane's k = 16 ks + 8 half + i
-          const float* vt = vk + (2 + my_ty) * H;
-          float av[8];
-#pragma unroll
-          for (int hh = 0; hh < 2; ++hh) {
-            const f32x4 pp = hh ? pc1 : pc, qq = hh ? qc1 : qc;
-            const f32x4 wd4 = *reinterpret_cast<const f32x4*>(vk + 4 * hh);
-            const f32x4 wz4 = *reinterpret_cast<const f32x4*>(vk + H + 4 * hh);
-            const f32x4 tb4 = *reinterpret_cast<const f32x4*>(vt + 4 * hh);
-            f32x2 alo = pk_fma(dz, wz4.xy, pk_fma(dd, wd4.xy, pp.xy + qq.xy)) + tb4.xy;   // (the exact path's arithmetic)
-            f32x2 ahi = pk_fma(dz, wz4.zw, pk_fma(dd, wd4.zw, pp.zw + qq.zw)) + tb4.zw;
-            alo = silu2(alo);
-            ahi = silu2(ahi);
-            av[4 * hh] = alo.x; av[4 * hh + 1] = alo.y; av[4 * hh + 2] = ahi.x; av[4 * hh + 3] = ahi.y;
-          }
+          const float* vt = vk + (2 + eg.my_ty) * H;
+          const f32x4 a03 = first_layer_act4<H>(pc, qc, dd, dz, vk, vt, 0), a47 = first_layer_act4<H>(pc1, qc1, dd, dz, vk, vt, 4);
+          const float av[8] = {a03.x, a03.y, a03.z, a03.w, a47.x, a47.y, a47.z, a47.w};
 #pragma unroll
           for (int i = 0; i < 8; ++i) {                    // exact three-way split: v_cvt_pk_bf16_f32 rounds to nearest even
             const __bf16 h1 = (__bf16)av[i];
@@ -719,7 +545,7 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
       } else {
       const float* bcur = sB + (bslice & 1) * L::B_BUF + (4 * half) * H + (bperm ? j * CT + 4 * swb : j);
       const float* vk = vq + kt * BK + 4 * half;           // this lane's k = kt*BK + 8g + 4*half + i
-      const float* vt = vk + (2 + my_ty) * H;
+      const float* vt = vk + (2 + eg.my_ty) * H;
 #pragma unroll
       for (int g = 0; g < BK / 8; ++g) {
         const int kb = kt * BK + 8 * g;                    // this lane's k = kb + 4*half + i
@@ -729,16 +555,7 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
           pn = ldv4(Pp + kb + 8);
           qn4 = ldv4(Qp + kb + 8);
         }
-        // A operand: SiLU((P + Q) + d wd + d0 wd0 + tab), two values per instruction (explicit fma: the same
-        // arithmetic in every instantiation of the kernel)
-        const f32x4 wd4 = *reinterpret_cast<const f32x4*>(vk + 8 * g);
-        const f32x4 wz4 = *reinterpret_cast<const f32x4*>(vk + H + 8 * g);
-        const f32x4 tb4 = *reinterpret_cast<const f32x4*>(vt + 8 * g);
-        f32x2 alo = pk_fma(dz, wz4.xy, pk_fma(dd, wd4.xy, pc.xy + qc.xy)) + tb4.xy;
-        f32x2 ahi = pk_fma(dz, wz4.zw, pk_fma(dd, wd4.zw, pc.zw + qc.zw)) + tb4.zw;
-        alo = silu2(alo);
-        ahi = silu2(ahi);
-        const float a[4] = {alo.x, alo.y, ahi.x, ahi.y};
+        const f32x4 a = first_layer_act4<H>(pc, qc, dd, dz, vk, vt, 8 * g);
         if (SETPRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -760,7 +577,7 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
     const bool last_unit = tile_ends && !has_next;
     // first P/Q chunk of the NEXT unit: in flight during the epilogue
     if (!last_unit) {
-      const int r_n = tile_ends ? nx_r : my_r, c_n = tile_ends ? nx_c : my_c;
+      const int r_n = tile_ends ? eg.nx_r : eg.my_r, c_n = tile_ends ? eg.nx_c : eg.my_c;
       Pp = p.mlp[qsel + qn].P + (size_t)(r_n < 0 ? 0 : r_n) * p.ldpq + KH * half;
       Qp = p.mlp[qsel + qn].Q + (size_t)c_n * p.ldpq + KH * half;
       pc = ldv4(Pp); qc = ldv4(Qp);
@@ -770,7 +587,7 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
     // ================= wave-private epilogue =================
     if constexpr (STORE) {
       // training forward: z2 (bias included) of the wave tile's valid slots, 128-byte row segments per half-wave
-      const int e0 = (my_wt - p.wt_base) * BMW;
+      const int e0 = (eg.my_wt - p.wt_base) * BMW;
       float* zb = p.z2_out + (MODE == MODE_COORD ? (size_t)(qsel + q) * p.z2_stride : (size_t)0) + (size_t)e0 * H + j;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -782,49 +599,32 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
       }
     }
     if (MODE == MODE_GCL) {
-      // messages m = SiLU(acc)   (egnn_new.py:18-19; the bias is already in the accumulators), register pairs
 #pragma unroll
-      for (int c = 0; c < CT; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const f32x2 m2 = silu2(f32x2{acc[c][r], acc[c][r + 1]});
-          acc[c][r] = m2.x; acc[c][r + 1] = m2.y;
-        }
+      for (int c = 0; c < CT; ++c) silu_tile(acc[c]);
       if (p.attention) {   // att = sigmoid(w_a . m + b_a); a half-wave holds complete rows
         f32x2 part2[8];
 #pragma unroll
         for (int r = 0; r < 8; ++r) part2[r] = splat2(0.f);
 #pragma unroll
-        for (int c = 0; c < CT; ++c) {
-          const f32x2 aw = splat2(vq[6 * H + feat(c)]);
-#pragma unroll
-          for (int r = 0; r < 8; ++r) part2[r] = pk_fma(f32x2{acc[c][2 * r], acc[c][2 * r + 1]}, aw, part2[r]);
-        }
+        for (int c = 0; c < CT; ++c) att_accumulate(acc[c], vq[6 * H + feat(c)], part2);
         float part[16];
 #pragma unroll
         for (int r = 0; r < 8; ++r) { part[2 * r] = part2[r].x; part[2 * r + 1] = part2[r].y; }
         // reduce-scatter over the half-wave: lane j ends with the dot product of accumulator register j >> 1,
         // takes ONE sigmoid, and the 16 gates of the half come back through 64 bytes of LDS (broadcast reads)
-        const float gate = sigmoidf_fast(reduce16_half_wave(part, j) + att_b);
-        s_phi[16 * half + (j >> 1)] = gate;
+        s_phi[16 * half + (j >> 1)] = sigmoidf_fast(reduce16_half_wave(part, j) + att_b);
         wave_lds_fence();
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-          const float4 g4 = *reinterpret_cast<const float4*>(s_phi + 16 * half + 4 * q4);
-          part[4 * q4] = g4.x; part[4 * q4 + 1] = g4.y; part[4 * q4 + 2] = g4.z; part[4 * q4 + 3] = g4.w;
-        }
+        gates_from_lds(s_phi, half, part);
         wave_lds_fence();   // the words are rewritten by the next tile
 #pragma unroll
-        for (int c = 0; c < CT; ++c)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[c][r] *= part[r];       // mij * att, egnn_new.py:40
+        for (int c = 0; c < CT; ++c) scale_tile(acc[c], part);
       }
       if constexpr (MSG) {
         // shell stage of the forward cone: the ghost segment's tiles of the first list keep the gated, un-normalised
         // messages of their valid slots (128-byte row segments per half-wave, like the z2 store above); the tile index
         // is wave-uniform (wt_base == 0: the list starts at slot 0)
-        const int wt = __builtin_amdgcn_readfirstlane(my_wt);
-        if (!my_lb && wt < p.msg_tiles) {
+        const int wt = __builtin_amdgcn_readfirstlane(eg.my_wt);
+        if (!eg.my_lb && wt < p.msg_tiles) {
           const int e0 = wt * BMW;
           // feat(c) = 32 c + j, with the two halves of the column tiles swapped for the lanes that read B swapped
           // (CT == 8 only): two lane bases, every other offset a compile-time constant
@@ -842,66 +642,7 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
           }
         }
       }
-      // Segmented sums over the tile's 32 rows.  Accumulator register rr of half h is row 8*(rr>>2) + 4*h + (rr&3):
-      // the rows alternate between the halves in groups of 4.  Every half adds up ITS rows of the running segment in
-      // edge order; when the segment ends (row ids are wave-uniform scalars: a scalar branch) the two halves' partial
-      // sums are added (half 0's + half 1's) and each half stores the column tiles it received -- a fixed order that
-      // depends on the tile's edges only.
-      // aggregation protocol (edge_mlp.h): the first segment of the tile goes to agg_head[tile]
-      // when its row continues from the previous wave tile, every other segment is the start of
-      // its row and goes to agg[row]; plain stores, each address written by exactly one wave
-      static_assert(CT % 2 == 0, "column tiles are exchanged in pairs");
-      // Even and odd rows of a half run in separate sums (the two words of a register pair) that meet at the flush:
-      // written as sum[c] += acc[c][r] the compiler pairs the adds ACROSS column tiles, whose accumulators are 16
-      // registers apart -- two v_mov per packed add.
-      f32x2 sum2[CT];
-#pragma unroll
-      for (int c = 0; c < CT; ++c) sum2[c] = splat2(0.f);
-      int cur = -1;
-      const int row0 = __builtin_amdgcn_readlane(my_r, 0);
-      bool to_head = row0 >= 0 && row0 == __builtin_amdgcn_readfirstlane(my_prev);
-      auto flush = [&]() {
-        if (cur >= 0) {
-          float* dst = to_head ? (my_lb ? p.agg_head_b : p.agg_head) + (size_t)my_wt * H
-                               : (my_lb ? p.agg_b : p.agg) + (size_t)cur * H;
-#pragma unroll
-          for (int c = 0; c < CT / 2; ++c) {
-            // half 0: tile c, half 1: tile c + CT/2
-            const float tot = pair_sum_halves(sum2[c].x + sum2[c].y, sum2[c + CT / 2].x + sum2[c + CT / 2].y);
-            dst[feat(c + half * (CT / 2))] = tot * inv_norm;
-          }
-          to_head = false;
-        }
-#pragma unroll
-        for (int c = 0; c < CT; ++c) sum2[c] = splat2(0.f);
-      };
-#pragma unroll
-      for (int gb = 0; gb < 8; ++gb) {
-        const int hh = gb & 1;
-#pragma unroll
-        for (int ip = 0; ip < 4; ip += 2) {
-          const int k = 4 * (gb >> 1) + ip;
-          const int rn0 = __builtin_amdgcn_readlane(my_r, 4 * gb + ip);
-          const int rn1 = __builtin_amdgcn_readlane(my_r, 4 * gb + ip + 1);
-          if (rn0 != cur) {                                // scalar compare / branch
-            flush();
-            cur = rn0;
-          }
-          if (half == hh) {
-#pragma unroll
-            for (int c = 0; c < CT; ++c) sum2[c].x += acc[c][k];
-          }
-          if (rn1 != rn0) {
-            flush();
-            cur = rn1;
-          }
-          if (half == hh) {
-#pragma unroll
-            for (int c = 0; c < CT; ++c) sum2[c].y += acc[c][k + 1];
-          }
-        }
-      }
-      flush();
+      segmented_row_sums<H, CT>(acc, p, eg, half, feat, inv_norm);
     } else {
       // scalar head: phi = w3 . SiLU(acc)   (egnn_new.py:80-92; the bias is already in the accumulators)
       f32x2 part2[8];
@@ -924,66 +665,17 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
       if (qsel + q == 0) phi0 = ph; else phi1 = ph;
 
       if (tile_ends) {
-        // trans = u*phi + cross*phi_x   (egnn_new.py:100-109, 296-316); lane = edge
-        float tx = 0.f, ty = 0.f, tz = 0.f;
-        if (my_r >= 0) {
-          const float dx = xr[0] - xc[0], dy = xr[1] - xc[1], dz = xr[2] - xc[2];
-          const float den = sqrtf(my_d + 1e-8f) + p.norm_constant;
-          const float ux = dx / den, uy = dy / den, uz = dz / den;
-          if (split && qsel == 1) {
-            // this workgroup only adds the cross-product term
-          } else if (p.use_tanh) {
-            const float th = tanhf(phi0);
-            tx = ux * th * p.coords_range; ty = uy * th * p.coords_range; tz = uz * th * p.coords_range;
-          } else {
-            tx = ux * phi0; ty = uy * phi0; tz = uz * phi0;
-          }
-          if (p.n_mlp == 2 && !(split && qsel == 0)) {
-            const int b = p.node_batch[my_r];
-            const float m0 = p.mean[3 * b], m1 = p.mean[3 * b + 1], m2 = p.mean[3 * b + 2];
-            const float a0 = xr[0] - m0, a1 = xr[1] - m1, a2 = xr[2] - m2;
-            const float b0 = xc[0] - m0, b1 = xc[1] - m1, b2 = xc[2] - m2;
-            const float c0 = a1 * b2 - a2 * b1, c1 = a2 * b0 - a0 * b2, c2 = a0 * b1 - a1 * b0;
-            const float cden = sqrtf(c0 * c0 + c1 * c1 + c2 * c2) + p.norm_constant;
-            float phx = phi1;
-            if (p.use_tanh) phx = tanhf(phx) * p.coords_range;
-            tx += c0 / cden * phx; ty += c1 / cden * phx; tz += c2 / cden * phx;
-          }
-        }
-        if (half == 0) { s_tr[3 * j] = tx; s_tr[3 * j + 1] = ty; s_tr[3 * j + 2] = tz; }
+        // lane = edge; a split launch's workgroup adds only its own MLP's term
+        float tr[3];
+        edge_translation(p, eg, !(split && qsel == 1), p.n_mlp == 2 && !(split && qsel == 0), phi0, phi1, tr);
+        if (half == 0) { s_tr[3 * j] = tr[0]; s_tr[3 * j + 1] = tr[1]; s_tr[3 * j + 2] = tr[2]; }
         wave_lds_fence();
-        // all 32 values of this lane's component first (independent LDS reads, one wait), then the scalar walk over
-        // the rows: read inside the walk, every step sat out an LDS round trip
         float trv[32];
 #pragma unroll
         for (int e = 0; e < 32; ++e) trv[e] = s_tr[3 * e + (lane < 3 ? lane : 0)];
-        if (lane < 3) {
-          const int pop = split ? qsel : 0;
-          float* xa = p.xagg + pop * p.xagg_stride;
-          float* xh = p.xagg_head + pop * p.xhead_stride;
-          const int row0 = __builtin_amdgcn_readlane(my_r, 0);
-          bool to_head = row0 >= 0 && row0 == __builtin_amdgcn_readfirstlane(my_prev);
-          int cur = -1;
-          float sum = 0.f;
-          auto put = [&]() {
-            if (cur >= 0) {
-              const float v = sum / p.norm_factor;
-              if (to_head) xh[4 * (size_t)my_wt + lane] = v; else xa[(size_t)cur * 3 + lane] = v;
-              to_head = false;
-            }
-          };
-#pragma unroll
-          for (int e = 0; e < 32; ++e) {
-            const int rn = __builtin_amdgcn_readlane(my_r, e);
-            if (rn != cur) {
-              put();
-              cur = rn;
-              sum = 0.f;
-            }
-            sum += trv[e];
-          }
-          put();
-        }
+        const int pop = split ? qsel : 0;
+        segmented_sum3<32>(trv, eg.my_r, eg.my_prev, lane, p.xagg + pop * p.xagg_stride, p.xagg_head + pop * p.xhead_stride,
+                           eg.my_wt, p.norm_factor);
         wave_lds_fence();   // scratch is reused by the next tile
       }
     }
@@ -991,7 +683,7 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave_kernel(EdgeArgs p) {
     // advance to the next unit
     if (tile_ends) {
       if (last_unit) break;
-      commit_edge();
+      eg.commit(p);
       li = next_li;
       q = 0;
     } else {

@@ -1,5 +1,6 @@
 // 16-edge-granule variant of the fused edge-MLP kernels (same math, arguments and aggregation protocol as edge_wave.h /
-// edge_mlp.h -- see there for the algorithm and the reference citations, egnn_new.py:31-52,96-122).
+// edge_mlp.h -- see there for the algorithm and the reference citations, egnn_new.py:31-52,96-122; the first-layer
+// activation, the edge prefetch and the translation's row sums are the shared functions of edge_parts.h).
 //
 // Why: a wave of edge_wave.h owns 32 edges x all H features = 1024 v_mfma_f32_32x32x2_f32 per K loop, 27 us of matrix
 // time; a launch whose tiles do not fill the SIMDs a whole number of times pays up to one such unit for the remainder
@@ -23,7 +24,7 @@
 //     protocol of edge_mlp.h with 16-edge tiles (head slots are indexed by 16-edge tile: the completion kernels take the
 //     tile shift as an argument).
 //   * epilogue, MODE_COORD: scalar head by the same all-reduce, trans per edge in the lanes of the first quarter, a
-//     16-step segmented walk for the three components (as edge_wave.h).  One (tile, MLP) item per workgroup pass.
+//     16-step segmented walk for the three components (segmented_sum3, edge_parts.h).  One (tile, MLP) item per workgroup pass.
 //
 // Workgroup = 4 waves = 64 edges, persistent over items (grid-stride).  The results differ from the 32-edge kernel in
 // rounding only (another k grouping inside the fp32 MFMA chains, another summation tree of the row sums): <= 2e-5
@@ -98,6 +99,8 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave16_kernel(EdgeArgs p) {
 
   for (int q = 0; q < n_mlp; ++q) {
     const EdgeMlpW& mw = p.mlp[q];
+    // per MLP: wd, wd0, tab0..2, b2, w-out.  Written out in each kernel on purpose: as a call to a shared function the
+    // compiler orders the prologue another way, and every launch waits for its prologue (profiles/edge_parts.md)
     float* v = sV + q * L::VEC_PER;
     for (int i = t; i < H; i += kThreads) {
       v[i] = mw.wd[i];
@@ -132,50 +135,27 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave16_kernel(EdgeArgs p) {
     for (int i = 0; i < BH; ++i) *reinterpret_cast<f32x4*>(dst + ((size_t)(g * BH + i) * kThreads + t) * 4) = stg[i];
   };
 
-  // ---- this lane's edge (current item) and the prefetched one ----
-  int my_r = -1, my_c = 0, my_ty = 0, my_prev = -1;
-  float my_d = 0.f, my_d0 = 0.f, xr[3] = {0.f, 0.f, 0.f}, xc[3] = {0.f, 0.f, 0.f};
-  int nx_r = -1, nx_c = 0, nx_prev = -1;
-  float nx_d0 = 0.f, nxr[3] = {0.f, 0.f, 0.f}, nxc[3] = {0.f, 0.f, 0.f};
-  int vzero;
-  asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));
-  auto fetch_idx = [&](int tile) {
-    const int e0 = tile * 64 + w * 16, e = e0 + n;
-    nx_r = -1; nx_c = 0; nx_d0 = 0.f; nx_prev = -1;
-    if (e < E) { nx_r = p.erow[e]; nx_c = p.ecol[e]; nx_d0 = p.ed0[e]; }
-    if (e0 > 0 && e0 < E) nx_prev = p.erow[e0 - 1 + vzero];
-  };
-  auto fetch_x = [&]() {
-    if ((unsigned)nx_r >= (unsigned)p.n_nodes || (unsigned)nx_c >= (unsigned)p.n_nodes) { nx_r = -1; nx_c = 0; }
-    if (nx_r >= 0) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { nxr[k] = p.x[3 * nx_r + k]; nxc[k] = p.x[3 * nx_c + k]; }
-    }
-  };
-  auto commit_edge = [&]() {
-    my_r = nx_r; my_c = nx_c; my_d0 = nx_d0; my_d = 0.f; my_ty = 0; my_prev = nx_prev;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { xr[k] = nxr[k]; xc[k] = nxc[k]; }
-    if (my_r >= 0) {
-      const float dx = xr[0] - xc[0], dy = xr[1] - xc[1], dz = xr[2] - xc[2];
-      my_d = dx * dx + dy * dy + dz * dz;
-      const bool rl = my_r < p.n_lig, cl = my_c < p.n_lig;
-      my_ty = (rl && cl) ? 1 : ((!rl && !cl) ? 2 : 0);
-    }
+  // ---- this lane's edge (current item) and the prefetched one: lane (n, kq) is edge n of the wave's 16; the head
+  // slot comes from the tile index (wt16 below) and there is one list, so the cursor's wt / lb stay unset (0, false)
+  // and nothing in this file reads them ----
+  EdgeCursor eg;
+  auto request_tile = [&](int tile) {
+    const int e0 = tile * 64 + w * 16;
+    eg.request(p.erow, p.ecol, p.ed0, e0, e0 + n, E, 0, false);
   };
 
   int item = blockIdx.x;
   int tile = item / n_mlp, q = item - tile * n_mlp;
   stage_load(q, 0, 0); stage_store(0, 0);
   stage_load(q, 0, 1); stage_store(0, 1);
-  fetch_idx(tile);
-  fetch_x();
-  commit_edge();
+  request_tile(tile);
+  eg.resolve(p);
+  eg.commit(p);
   __syncthreads();
   int bslice = 0;
   // first P / Q chunk of an item: requested before the previous item's epilogue (here: before the first item)
-  f32x4 pc_next = ldv4(p.mlp[q].P + (size_t)(my_r < 0 ? 0 : my_r) * p.ldpq + 4 * kq);
-  f32x4 qc_next = ldv4(p.mlp[q].Q + (size_t)my_c * p.ldpq + 4 * kq);
+  f32x4 pc_next = ldv4(p.mlp[q].P + (size_t)(eg.my_r < 0 ? 0 : eg.my_r) * p.ldpq + 4 * kq);
+  f32x4 qc_next = ldv4(p.mlp[q].Q + (size_t)eg.my_c * p.ldpq + 4 * kq);
 
 #pragma unroll 1
   for (;;) {
@@ -184,8 +164,8 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave16_kernel(EdgeArgs p) {
     const int tile_n = has_next ? next_item / n_mlp : 0, q_n = has_next ? next_item - tile_n * n_mlp : q;
     const bool new_edges = has_next && tile_n != tile;
     const float* vq = sV + q * L::VEC_PER;
-    const float* Pp = p.mlp[q].P + (size_t)(my_r < 0 ? 0 : my_r) * p.ldpq + 4 * kq;
-    const float* Qp = p.mlp[q].Q + (size_t)my_c * p.ldpq + 4 * kq;
+    const float* Pp = p.mlp[q].P + (size_t)(eg.my_r < 0 ? 0 : eg.my_r) * p.ldpq + 4 * kq;
+    const float* Qp = p.mlp[q].Q + (size_t)eg.my_c * p.ldpq + 4 * kq;
     f32x4 pc = pc_next, qc = qc_next, pn = pc, qn4 = qc;
 
     f32x4 acc[CT];
@@ -194,31 +174,24 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave16_kernel(EdgeArgs p) {
       const float bv = vq[5 * H + feat(a)];
       acc[a] = f32x4{bv, bv, bv, bv};
     }
-    const f32x2 dd = splat2(my_d), dz = splat2(my_d0);
+    const f32x2 dd = splat2(eg.my_d), dz = splat2(eg.my_d0);
 
 #pragma unroll 1
     for (int kt = 0; kt < NK; ++kt) {
       const bool more = kt + 1 < NK;
-      if (kt == 0 && new_edges) fetch_idx(tile_n);
-      if (kt == 1 && new_edges) fetch_x();
+      if (kt == 0 && new_edges) request_tile(tile_n);
+      if (kt == 1 && new_edges) eg.resolve(p);
       const int sq = more ? q : q_n, sks = more ? kt + 1 : 0;
       const float* bcur = sB + (bslice & 1) * BK * H + (4 * kq) * H + n * CT;
       const float* vk = vq + kt * BK + 4 * kq;
-      const float* vt = vk + (2 + my_ty) * H;
+      const float* vt = vk + (2 + eg.my_ty) * H;
 #pragma unroll
       for (int g = 0; g < BK / 16; ++g) {
         const int kb = kt * BK + 16 * g;
         if (g > 0) stage_store((bslice + 1) & 1, g - 1);
         stage_load(sq, sks, g);
         if (g + 1 < BK / 16 || more) { pn = ldv4(Pp + kb + 16); qn4 = ldv4(Qp + kb + 16); }
-        const f32x4 wd4 = *reinterpret_cast<const f32x4*>(vk + 16 * g);
-        const f32x4 wz4 = *reinterpret_cast<const f32x4*>(vk + H + 16 * g);
-        const f32x4 tb4 = *reinterpret_cast<const f32x4*>(vt + 16 * g);
-        f32x2 alo = pk_fma(dz, wz4.xy, pk_fma(dd, wd4.xy, pc.xy + qc.xy)) + tb4.xy;
-        f32x2 ahi = pk_fma(dz, wz4.zw, pk_fma(dd, wd4.zw, pc.zw + qc.zw)) + tb4.zw;
-        alo = silu2(alo);
-        ahi = silu2(ahi);
-        const float av[4] = {alo.x, alo.y, ahi.x, ahi.y};
+        const f32x4 av = first_layer_act4<H>(pc, qc, dd, dz, vk, vt, 16 * g);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -242,7 +215,7 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave16_kernel(EdgeArgs p) {
     }
 
     if (has_next) {                                          // the next item's first P / Q chunk flies during the epilogue
-      const int r_n = new_edges ? nx_r : my_r, c_n = new_edges ? nx_c : my_c;
+      const int r_n = new_edges ? eg.nx_r : eg.my_r, c_n = new_edges ? eg.nx_c : eg.my_c;
       pc_next = ldv4(p.mlp[q_n].P + (size_t)(r_n < 0 ? 0 : r_n) * p.ldpq + 4 * kq);
       qc_next = ldv4(p.mlp[q_n].Q + (size_t)c_n * p.ldpq + 4 * kq);
     }
@@ -255,7 +228,7 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave16_kernel(EdgeArgs p) {
         acc[a] = f32x4{m01.x, m01.y, m23.x, m23.y};
       }
       // edges of this lane's registers: active?
-      if (kq == 0) s_i[n] = my_r;
+      if (kq == 0) s_i[n] = eg.my_r;
       wave_lds_fence();
       const int4 rows4 = *reinterpret_cast<const int4*>(s_i + 4 * kq);
       wave_lds_fence();
@@ -280,14 +253,14 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave16_kernel(EdgeArgs p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[a][r] = act[r] ? acc[a][r] : 0.f;      // entries that name no edge add nothing
       // segments of the tile: runs of equal row ids
-      const int prev_row = dpp_row_shr1_i(my_r, -2);
-      const bool first = n == 0 || my_r != prev_row;
+      const int prev_row = dpp_row_shr1_i(eg.my_r, -2);
+      const bool first = n == 0 || eg.my_r != prev_row;
       const unsigned long long bal = __builtin_amdgcn_ballot_w64(first && kq == 0);
       const unsigned m16 = (unsigned)bal & 0xFFFFu;
       const int seg = __builtin_popcount(m16 & ((2u << n) - 1u)) - 1;          // segment of edge n
       if (kq == 0) {
         s_i[n] = seg;
-        if (first) s_i[16 + seg] = my_r;
+        if (first) s_i[16 + seg] = eg.my_r;
       }
       wave_lds_fence();
       const int4 sg4 = *reinterpret_cast<const int4*>(s_i + 4 * kq);           // segments of edges 4 kq + m
@@ -296,8 +269,8 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave16_kernel(EdgeArgs p) {
       const int nseg = __builtin_popcount(m16);
       const float ind[4] = {sg4.x == n ? 1.f : 0.f, sg4.y == n ? 1.f : 0.f, sg4.z == n ? 1.f : 0.f, sg4.w == n ? 1.f : 0.f};
       const int srow[4] = {sr4.x, sr4.y, sr4.z, sr4.w};
-      const int row0 = __builtin_amdgcn_readlane(my_r, 0);
-      const bool head0 = row0 >= 0 && row0 == __builtin_amdgcn_readfirstlane(my_prev);
+      const int row0 = __builtin_amdgcn_readlane(eg.my_r, 0);
+      const bool head0 = row0 >= 0 && row0 == __builtin_amdgcn_readfirstlane(eg.my_prev);
       float* dst[4];
       bool st[4];
 #pragma unroll
@@ -339,17 +312,17 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave16_kernel(EdgeArgs p) {
       const float ph = s_f[n];
       wave_lds_fence();
       float tx = 0.f, ty = 0.f, tz = 0.f;
-      if (my_r >= 0 && kq == 0) {
-        const float dx = xr[0] - xc[0], dy = xr[1] - xc[1], dzz = xr[2] - xc[2];
+      if (eg.my_r >= 0 && kq == 0) {
+        const float dx = eg.xr[0] - eg.xc[0], dy = eg.xr[1] - eg.xc[1], dzz = eg.xr[2] - eg.xc[2];
         if (q == 0) {
-          const float den = sqrtf(my_d + 1e-8f) + p.norm_constant;
+          const float den = sqrtf(eg.my_d + 1e-8f) + p.norm_constant;
           const float T = p.use_tanh ? tanhf(ph) * p.coords_range : ph;
           tx = dx / den * T; ty = dy / den * T; tz = dzz / den * T;
         } else {
-          const int b = p.node_batch[my_r];
+          const int b = p.node_batch[eg.my_r];
           const float m0 = p.mean[3 * b], m1 = p.mean[3 * b + 1], m2 = p.mean[3 * b + 2];
-          const float a0 = xr[0] - m0, a1 = xr[1] - m1, a2 = xr[2] - m2;
-          const float b0 = xc[0] - m0, b1 = xc[1] - m1, b2 = xc[2] - m2;
+          const float a0 = eg.xr[0] - m0, a1 = eg.xr[1] - m1, a2 = eg.xr[2] - m2;
+          const float b0 = eg.xc[0] - m0, b1 = eg.xc[1] - m1, b2 = eg.xc[2] - m2;
           const float c0 = a1 * b2 - a2 * b1, c1 = a2 * b0 - a0 * b2, c2 = a0 * b1 - a1 * b0;
           const float cden = sqrtf(c0 * c0 + c1 * c1 + c2 * c2) + p.norm_constant;
           const float T = p.use_tanh ? tanhf(ph) * p.coords_range : ph;
@@ -361,33 +334,13 @@ __global__ __launch_bounds__(kThreads, 2) void edge_wave16_kernel(EdgeArgs p) {
       float trv[16];
 #pragma unroll
       for (int e = 0; e < 16; ++e) trv[e] = s_f[16 + 3 * e + (lane < 3 ? lane : 0)];
-      if (lane < 3) {
-        float* xa = p.xagg + q * p.xagg_stride;
-        float* xh = p.xagg_head + q * p.xhead_stride;
-        const int row0 = __builtin_amdgcn_readlane(my_r, 0);
-        bool to_head = row0 >= 0 && row0 == __builtin_amdgcn_readfirstlane(my_prev);
-        int cur = -1;
-        float sum = 0.f;
-        auto put = [&]() {
-          if (cur >= 0) {
-            const float v = sum / p.norm_factor;
-            if (to_head) xh[4 * (size_t)wt16 + lane] = v; else xa[(size_t)cur * 3 + lane] = v;
-            to_head = false;
-          }
-        };
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int rn = __builtin_amdgcn_readlane(my_r, e);
-          if (rn != cur) { put(); cur = rn; sum = 0.f; }
-          sum += trv[e];
-        }
-        put();
-      }
+      segmented_sum3<16>(trv, eg.my_r, eg.my_prev, lane, p.xagg + q * p.xagg_stride, p.xagg_head + q * p.xhead_stride, wt16,
+                         p.norm_factor);
       wave_lds_fence();
     }
 
     if (!has_next) break;
-    if (new_edges) commit_edge();
+    if (new_edges) eg.commit(p);
     item = next_item; tile = tile_n; q = q_n;
   }
 }

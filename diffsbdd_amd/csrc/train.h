@@ -158,16 +158,9 @@ __global__ __launch_bounds__(kThreads, 1) void edge_bwd_a_kernel(TrainEdgeArgs p
       for (int g = 0; g < BK / 8; ++g) {
         const int kb = kt * BK + 8 * g;
         if (g + 1 < BK / 8 || kt + 1 < NK) { pn = ldv4(Pp + kb + 8); qn = ldv4(Qp + kb + 8); }
-        const f32x4 wd4 = *reinterpret_cast<const f32x4*>(vk + 8 * g);
-        const f32x4 wz4 = *reinterpret_cast<const f32x4*>(vk + H + 8 * g);
-        const f32x4 tb4 = *reinterpret_cast<const f32x4*>(vt + 8 * g);
-        f32x2 alo = pk_fma(dz2v, wz4.xy, pk_fma(dd2, wd4.xy, pc.xy + qc.xy)) + tb4.xy;
-        f32x2 ahi = pk_fma(dz2v, wz4.zw, pk_fma(dd2, wd4.zw, pc.zw + qc.zw)) + tb4.zw;
-        alo = silu2(alo);
-        ahi = silu2(ahi);
-        const float a[4] = {alo.x, alo.y, ahi.x, ahi.y};
+        const f32x4 a = first_layer_act4<H>(pc, qc, dd2, dz2v, vk, vt, 8 * g);
         if (e < p.E) {
-          const f32x4 av = active ? f32x4{a[0], a[1], a[2], a[3]} : f32x4{0.f, 0.f, 0.f, 0.f};
+          const f32x4 av = active ? a : f32x4{0.f, 0.f, 0.f, 0.f};
           *reinterpret_cast<f32x4*>(p.a1_out + (size_t)e * H + kb + 4 * half) = av;
         }
 #pragma unroll

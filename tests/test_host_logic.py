@@ -684,7 +684,7 @@ def test_committed_pmc_traffic_was_measured_on_the_committed_kernel_sources():
     """`roofline.traffic` of the benchmark line is read from a committed PMC measurement (counters cannot be collected from
     inside the process); `bench.py` reports it only when the file's `kernel_source_sha16` equals the hash of the edge
     kernel's sources in this tree.  This test keeps the committed pair consistent: editing `csrc/edge_wave.h`,
-    `edge_mlp.h` or `common.h` without re-running `tools/pmc_traffic.sh` fails HERE instead of silently turning the
+    `edge_parts.h`, `edge_mlp.h` or `common.h` without re-running `tools/pmc_traffic.sh` fails HERE instead of silently turning the
     driver's `traffic` into null."""
     import bench
     from diffsbdd_amd.build import kernel_source_hash
