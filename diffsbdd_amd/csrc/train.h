@@ -1,7 +1,7 @@
-// Backward pass of the fused edge stages ("hand-written backward for the fused edge kernels") and the
-// node-level weight-gradient GEMM, so that the reference's training step (lightning_modules.py:337-363 ->
-// conditional_model.py:202-330 / en_diffusion.py:336-469 -> dynamics.py:87-167 -> egnn_new.py:31-58,96-122) runs on
-// hand-written gfx950 kernels.
+// Backward pass of the fused edge stages ("hand-written backward for the fused edge kernels"), so that
+// the reference's training step (lightning_modules.py:337-363 -> conditional_model.py:202-330 /
+// en_diffusion.py:336-469 -> dynamics.py:87-167 -> egnn_new.py:31-58,96-122) runs on hand-written gfx950 kernels.  The
+// parts the edge kernels share are in train_parts.h, the weight-gradient GEMM and its ordered reduction in wgrad.h.
 //
 // Forward of an edge MLP (edge_mlp.h), per edge e = (i, j):
 //     z1 = P[i] + Q[j] + d wd + d0 wd0 + tab[type]      a1 = SiLU(z1)
@@ -15,7 +15,7 @@
 //       the epilogue turns the accumulators into dz2 (GCL: attention + SiLU backward from the gathered d_agg rows;
 //       COORD: scalar head, tanh and the geometry of u / cross backward) -> dz2 [E][H] and a1 [E][H] to HBM, bias /
 //       head gradients as per-(wave, half) partial vectors, the coordinate gradients of the geometry per edge.
-//   wgrad (wgrad_kernel): dW2 = dz2^T a1, a split-K "TN" GEMM over the edges with an ordered reduction (no atomics).
+//   wgrad (wgrad_kernel, wgrad.h): dW2 = dz2^T a1, a split-K "TN" GEMM over the edges with an ordered reduction (no atomics).
 //   kernel B (edge_bwd_b_kernel): da1 = dz2 W2 (A operand = the lane's dz2 row, straight from global memory), the epilogue
 //       recomputes z1 in accumulator layout, dz1 = da1 SiLU'(z1) -> dz1 [E][H], the gradients of wd / wd0 / tab as
 //       partial vectors, the gradient w.r.t. |d|^2 and d0 per edge.
@@ -26,7 +26,9 @@
 #pragma once
 #include "common.h"
 #include "edge_mlp.h"
-#include "edge_wave.h"
+#include "edge_parts.h"
+#include "train_parts.h"
+#include "wgrad.h"
 
 namespace dsbdd {
 
@@ -51,13 +53,6 @@ struct TrainEdgeArgs {
   float* gxr; float* gxc; float* gm;   // COORD kernel A: [E][3] gradient pieces for x[row], x[col], the sample mean
   float* gd; float* gd0; // kernel B: [E] gradient w.r.t. the current and the input squared distance
 };
-
-constexpr int kPartA = 3;   // kernel A: d_b2, d_head (att_w / w3), [0] = d_att_b
-constexpr int kPartB = 5;   // kernel B: d_wd, d_wd0, d_tab[0..2]
-constexpr int kPartAll = kPartA + kPartB;   // one [8][H] slot per workgroup, B's rows first: the layout of dsbdd_train_mlp_grad::d_vec,
-                                            // so ONE ordered reduction behind kernel B serves both kernels (round 6)
-
-__device__ __forceinline__ float dsilu_from(float z, float sg) { return sg * (1.0f + z * (1.0f - sg)); }
 
 // Stream of [32][H] slices of a row-major [H][H] matrix through a two-slot LDS buffer.
 template <int H>
@@ -120,20 +115,15 @@ __global__ __launch_bounds__(kThreads, 1) void edge_bwd_a_kernel(TrainEdgeArgs p
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int e_base = tile * 128 + w * 32;
     const int e = e_base + j;
-    bool active = e < p.E;
-    int r = 0, cidx = 0;
-    float d0 = 0.f;
-    if (active) {
-      r = p.erow[e]; cidx = p.ecol[e]; d0 = p.ed0[e];
-      if ((unsigned)r >= (unsigned)p.n_nodes || (unsigned)cidx >= (unsigned)p.n_nodes) { active = false; r = 0; cidx = 0; d0 = 0.f; }
-    }
+    int r, cidx;
+    float d0;
+    const bool active = bwd_lane_entry(p.erow, p.ecol, p.ed0, p.E, e, p.n_nodes, r, cidx, d0);
     float xr[3], xc[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) { xr[k] = p.x[3 * r + k]; xc[k] = p.x[3 * cidx + k]; }
     const float ddx = xr[0] - xc[0], ddy = xr[1] - xc[1], ddz = xr[2] - xc[2];
     const float d = active ? ddx * ddx + ddy * ddy + ddz * ddz : 0.f;
-    const bool rl = r < p.n_lig, cl = cidx < p.n_lig;
-    const int ty = (rl && cl) ? 1 : ((!rl && !cl) ? 2 : 0);
+    const int ty = bwd_edge_type(r, cidx, p.n_lig);
 
     f32x16 acc[CT];
 #pragma unroll
@@ -286,7 +276,8 @@ __global__ __launch_bounds__(kThreads, 1) void edge_bwd_a_kernel(TrainEdgeArgs p
       wave_lds_fence();
       const float ph = s_phi[j];
       wave_lds_fence();
-      // lane = edge: d_phi and the geometry gradients (egnn_new.py:100-109, 296-316)
+      // lane = edge: d_phi and the geometry gradients (egnn_new.py:100-109, 296-316).  SECOND COPY: the MODE_COORD branch of
+      // edge_bwd_e_kernel below -- change both (why two: train_parts.h, profiles/train_parts.md)
       float g0 = 0.f, g1 = 0.f, g2 = 0.f;
       if (active) { g0 = p.d_xagg[3 * r] * inv_norm; g1 = p.d_xagg[3 * r + 1] * inv_norm; g2 = p.d_xagg[3 * r + 2] * inv_norm; }
       float T = ph, dT = 1.f;
@@ -318,14 +309,7 @@ __global__ __launch_bounds__(kThreads, 1) void edge_bwd_a_kernel(TrainEdgeArgs p
           am[0] = -(ar[0] + ac[0]); am[1] = -(ar[1] + ac[1]); am[2] = -(ar[2] + ac[2]);
         }
       }
-      if (half == 0 && e < p.E) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          p.gxr[3 * (size_t)e + k] = ar[k];
-          p.gxc[3 * (size_t)e + k] = ac[k];
-          if (p.gm) p.gm[3 * (size_t)e + k] = am[k];
-        }
-      }
+      if (half == 0 && e < p.E) store_coord_pieces(p.gxr, p.gxc, p.gm, e, ar, ac, am);
       if (half == 0) s_aux[j] = dphi;
       wave_lds_fence();
       float dph[16];
@@ -367,64 +351,35 @@ __global__ __launch_bounds__(kThreads, 1) void edge_bwd_a_kernel(TrainEdgeArgs p
     sp[H + 32 * c + j] = pv1[c];
     sp[2 * H + 32 * c + j] = (c == 0 && j == 0) ? ps : 0.f;
   }
-  __syncthreads();
-  for (int i = t; i < kPartA * H; i += kThreads) {
-    float v = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v += sB[(size_t)q * kPartA * H + i];
-    p.part[(size_t)blockIdx.x * kPartAll * H + (size_t)kPartB * H + i] = v;      // rows 5 .. 7 of the workgroup's [8][H] slot
-  }
+  fold_wave_partials<kPartA>(sB, H, t, p.part + ((size_t)blockIdx.x * kPartAll + kPartB) * H);   // rows 5 .. 7 of the slot
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// kernel E (round 6): the message stage's kernel A WITHOUT its H x H layer.  The forward pass of the network path keeps
-// z2 = W2 a1 + b2 of every edge (edge_wave_kernel<.., STORE>, 4 E H bytes per message stage -- the device has 288 GB), so
-// what is left of kernel A is element-wise per edge: a1 = SiLU(z1) from the row-gathered projections (for the weight
-// gradient), m = SiLU(z2), the attention gate and its backward, dz2.  One WAVE per edge, lane l holds columns
-// V l .. V l + V - 1 (V = H / 64: 16-byte accesses at H = 256, every row a contiguous 4 H bytes), 16 waves per workgroup,
-// the grid of kernel B (one [8][H] partial-vector slot per workgroup: rows 5 .. 7 here, as kernel A).  Row sums are wave
-// butterflies in a fixed order: bitwise reproducible, and within rounding of kernel A's (which sums the same products in
-// accumulator-tile order).
-constexpr int kThreadsE = 1024;
-template <int V>
-__device__ __forceinline__ void ld_cols(const float* row, int lane, float (&v)[V]) {
-  if constexpr (V == 4) { const float4 q = *reinterpret_cast<const float4*>(row + 4 * lane); v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
-  else if constexpr (V == 2) { const float2 q = *reinterpret_cast<const float2*>(row + 2 * lane); v[0] = q.x; v[1] = q.y; }
-  else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) v[k] = row[V * lane + k];
-  }
-}
-template <int V>
-__device__ __forceinline__ void st_cols(float* row, int lane, const float (&v)[V]) {
-  if constexpr (V == 4) *reinterpret_cast<float4*>(row + 4 * lane) = float4{v[0], v[1], v[2], v[3]};
-  else if constexpr (V == 2) *reinterpret_cast<float2*>(row + 2 * lane) = float2{v[0], v[1]};
-  else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) row[V * lane + k] = v[k];
-  }
-}
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-template <int H>
+// kernel E (round 6): kernel A WITHOUT its H x H layer.  The forward pass of the network path keeps z2 = W2 a1 + b2 of
+// every edge (edge_wave_kernel<.., STORE>, 4 E H bytes per stage -- the device has 288 GB), so what is left of kernel A is
+// element-wise per edge: a1 = SiLU(z1) from the row-gathered projections (for the weight gradient), m = SiLU(z2), then
+//   MODE_GCL:   the attention gate and its backward, dz2;
+//   MODE_COORD: phi = w3 . m, the geometry gradients of kernel A's MODE_COORD epilogue (every lane evaluates the edge's
+//               scalars; lane 0 stores them), dz2 = d_phi w3 SiLU'(z2).
+// One WAVE per edge, lane l holds columns V l .. V l + V - 1 (V = H / 64: 16-byte accesses at H = 256, every row a
+// contiguous 4 H bytes), 16 waves per workgroup, the grid of kernel B (one [8][H] partial-vector slot per workgroup:
+// rows 5 .. 7 here, as kernel A).  Row sums are wave butterflies in a fixed order: bitwise reproducible, and within
+// rounding of kernel A's (which sums the same products in accumulator-tile order).
+template <int H, int MODE>
 __global__ __launch_bounds__(kThreadsE) void edge_bwd_e_kernel(TrainEdgeArgs p, const float* __restrict__ z2) {
   constexpr int V = H / 64, NW = kThreadsE / 64;
   __shared__ __attribute__((aligned(16))) float sP[NW][2 * H + 4];
   const int t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const bool attention = p.head != nullptr;
-  float wd[V], wd0[V], tb[3][V], aw[V];
+  const bool attention = MODE == MODE_GCL && p.head != nullptr;
+  float wd[V], wd0[V], tb[3][V], hw[V];      // hw: the head's weights -- att_w (zeros without attention) / w3
   ld_cols<V>(p.wd, lane, wd);
   ld_cols<V>(p.wd0, lane, wd0);
 #pragma unroll
   for (int y = 0; y < 3; ++y) ld_cols<V>(p.table + y * H, lane, tb[y]);
 #pragma unroll
-  for (int k = 0; k < V; ++k) aw[k] = 0.f;
-  if (attention) ld_cols<V>(p.head, lane, aw);
+  for (int k = 0; k < V; ++k) hw[k] = 0.f;
+  if (MODE == MODE_COORD || attention) ld_cols<V>(p.head, lane, hw);
   const float att_b = attention ? p.head_b[0] : 0.f;
   const float inv_norm = 1.0f / p.norm_factor;
   float pb2[V], pv1[V], ps = 0.f;
@@ -433,184 +388,96 @@ __global__ __launch_bounds__(kThreadsE) void edge_bwd_e_kernel(TrainEdgeArgs p, 
 
 #pragma unroll 1
   for (int e = blockIdx.x * NW + w; e < p.E; e += gridDim.x * NW) {
-    int r = __builtin_amdgcn_readfirstlane(p.erow[e]), c = __builtin_amdgcn_readfirstlane(p.ecol[e]);
+    const int r = __builtin_amdgcn_readfirstlane(p.erow[e]), c = __builtin_amdgcn_readfirstlane(p.ecol[e]);
     const float d0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.ed0[e])));
-    const bool active = (unsigned)r < (unsigned)p.n_nodes && (unsigned)c < (unsigned)p.n_nodes;
     float zv[V], a1[V], dz[V];
-    if (!active) {          // (wave-uniform) rows of inactive list entries are zeros: the weight-gradient GEMM sums every row
+    if (!bwd_entry_active(r, c, p.n_nodes)) {          // (wave-uniform) rows of inactive list entries are zeros: the weight-gradient GEMM sums every row
 #pragma unroll
       for (int k = 0; k < V; ++k) zv[k] = 0.f;
       st_cols<V>(p.a1_out + (size_t)e * H, lane, zv);
       st_cols<V>(p.dz_out + (size_t)e * H, lane, zv);
+      if (MODE == MODE_COORD && lane < 3) {
+        p.gxr[3 * (size_t)e + lane] = 0.f; p.gxc[3 * (size_t)e + lane] = 0.f;
+        if (p.gm) p.gm[3 * (size_t)e + lane] = 0.f;
+      }
       continue;
     }
     float pv[V], qv[V], dout[V];
     ld_cols<V>(z2 + (size_t)e * H, lane, zv);
     ld_cols<V>(p.P + (size_t)r * p.ldpq, lane, pv);
     ld_cols<V>(p.Q + (size_t)c * p.ldpq, lane, qv);
-    ld_cols<V>(p.d_agg + (size_t)r * H, lane, dout);
-    const float ddx = p.x[3 * r] - p.x[3 * c], ddy = p.x[3 * r + 1] - p.x[3 * c + 1], ddz = p.x[3 * r + 2] - p.x[3 * c + 2];
-    const float d = ddx * ddx + ddy * ddy + ddz * ddz;
-    const bool rl = r < p.n_lig, cl = c < p.n_lig;
-    const int ty = (rl && cl) ? 1 : ((!rl && !cl) ? 2 : 0);
-    // a1 = SiLU(z1), the first layer as kernel A evaluates it
-#pragma unroll
-    for (int k = 0; k < V; ++k) a1[k] = silu(fmaf(d0, wd0[k], fmaf(d, wd[k], pv[k] + qv[k])) + tb[ty][k]);
-    st_cols<V>(p.a1_out + (size_t)e * H, lane, a1);
-    float m[V], sg[V], dot = 0.f, sdot = 0.f;
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      dout[k] *= inv_norm;
-      sg[k] = sigmoidf_fast(zv[k]);
-      m[k] = zv[k] * sg[k];
-      dot = fmaf(m[k], aw[k], dot);
-      sdot = fmaf(dout[k], m[k], sdot);
-    }
-    float att = 1.f, tt = 0.f;
-    if (attention) {
-      const float gate = sigmoidf_fast(wave_sum_f(dot) + att_b);
-      att = gate;
-      tt = wave_sum_f(sdot) * gate * (1.0f - gate);
-      ps += tt;
-    }
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      const float dm = fmaf(tt, aw[k], dout[k] * att);
-      dz[k] = dm * dsilu_from(zv[k], sg[k]);
-      pb2[k] += dz[k];
-      pv1[k] = fmaf(tt, m[k], pv1[k]);
-    }
-    st_cols<V>(p.dz_out + (size_t)e * H, lane, dz);
-  }
-  // partial vectors of the workgroup: the 16 waves' sums in wave order -> rows 5 .. 7 of its slot
-  st_cols<V>(sP[w], lane, pb2);
-  st_cols<V>(sP[w] + H, lane, pv1);
-  if (lane == 0) sP[w][2 * H] = ps;
-  __syncthreads();
-  for (int i = t; i < kPartA * H; i += kThreadsE) {
-    float v = 0.f;
-    if (i < 2 * H) {
-#pragma unroll
-      for (int q = 0; q < NW; ++q) v += sP[q][i];
-    } else if (i == 2 * H) {
-#pragma unroll
-      for (int q = 0; q < NW; ++q) v += sP[q][2 * H];
-    }
-    p.part[(size_t)blockIdx.x * kPartAll * H + (size_t)kPartB * H + i] = v;
-  }
-}
-
-// kernel E of the coordinate stage: phi = w3 . SiLU(z2) from the kept z2, the geometry gradients of kernel A's
-// MODE_COORD epilogue (every lane evaluates the edge's scalars; lane 0 stores them), dz2 = d_phi w3 SiLU'(z2).
-template <int H>
-__global__ __launch_bounds__(kThreadsE) void edge_bwd_ec_kernel(TrainEdgeArgs p, const float* __restrict__ z2) {
-  constexpr int V = H / 64, NW = kThreadsE / 64;
-  __shared__ __attribute__((aligned(16))) float sP[NW][2 * H + 4];
-  const int t = threadIdx.x, lane = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  float wd[V], wd0[V], tb[3][V], w3[V];
-  ld_cols<V>(p.wd, lane, wd);
-  ld_cols<V>(p.wd0, lane, wd0);
-#pragma unroll
-  for (int y = 0; y < 3; ++y) ld_cols<V>(p.table + y * H, lane, tb[y]);
-  ld_cols<V>(p.head, lane, w3);
-  const float inv_norm = 1.0f / p.norm_factor;
-  float pb2[V], pv1[V];
-#pragma unroll
-  for (int k = 0; k < V; ++k) { pb2[k] = 0.f; pv1[k] = 0.f; }
-
-#pragma unroll 1
-  for (int e = blockIdx.x * NW + w; e < p.E; e += gridDim.x * NW) {
-    const int r = __builtin_amdgcn_readfirstlane(p.erow[e]), c = __builtin_amdgcn_readfirstlane(p.ecol[e]);
-    const float d0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.ed0[e])));
-    const bool active = (unsigned)r < (unsigned)p.n_nodes && (unsigned)c < (unsigned)p.n_nodes;
-    float zv[V], a1[V], dz[V];
-    if (!active) {
-#pragma unroll
-      for (int k = 0; k < V; ++k) zv[k] = 0.f;
-      st_cols<V>(p.a1_out + (size_t)e * H, lane, zv);
-      st_cols<V>(p.dz_out + (size_t)e * H, lane, zv);
-      if (lane < 3) {
-        p.gxr[3 * (size_t)e + lane] = 0.f; p.gxc[3 * (size_t)e + lane] = 0.f;
-        if (p.gm) p.gm[3 * (size_t)e + lane] = 0.f;
-      }
-      continue;
-    }
-    float pv[V], qv[V];
-    ld_cols<V>(z2 + (size_t)e * H, lane, zv);
-    ld_cols<V>(p.P + (size_t)r * p.ldpq, lane, pv);
-    ld_cols<V>(p.Q + (size_t)c * p.ldpq, lane, qv);
+    if constexpr (MODE == MODE_GCL) ld_cols<V>(p.d_agg + (size_t)r * H, lane, dout);
     const float xr[3] = {p.x[3 * r], p.x[3 * r + 1], p.x[3 * r + 2]}, xc[3] = {p.x[3 * c], p.x[3 * c + 1], p.x[3 * c + 2]};
     const float ddx = xr[0] - xc[0], ddy = xr[1] - xc[1], ddz = xr[2] - xc[2];
     const float d = ddx * ddx + ddy * ddy + ddz * ddz;
-    const bool rl = r < p.n_lig, cl = c < p.n_lig;
-    const int ty = (rl && cl) ? 1 : ((!rl && !cl) ? 2 : 0);
-#pragma unroll
-    for (int k = 0; k < V; ++k) a1[k] = silu(fmaf(d0, wd0[k], fmaf(d, wd[k], pv[k] + qv[k])) + tb[ty][k]);
+    first_layer_cols<V>(pv, qv, d, d0, bwd_edge_type(r, c, p.n_lig), wd, wd0, tb, a1);
     st_cols<V>(p.a1_out + (size_t)e * H, lane, a1);
-    float m[V], sg[V], dot = 0.f;
+    float m[V], sg[V], dm[V], dot = 0.f;     // m = SiLU(z2), dot = m . hw; dm: the gradient w.r.t. m
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       sg[k] = sigmoidf_fast(zv[k]);
       m[k] = zv[k] * sg[k];
-      dot = fmaf(m[k], w3[k], dot);
+      dot = fmaf(m[k], hw[k], dot);
     }
-    const float ph = wave_sum_f(dot);
-    // d_phi and the geometry gradients (egnn_new.py:100-109, 296-316), as kernel A's MODE_COORD epilogue
-    const float g0 = p.d_xagg[3 * r] * inv_norm, g1 = p.d_xagg[3 * r + 1] * inv_norm, g2 = p.d_xagg[3 * r + 2] * inv_norm;
-    float T = ph, dT = 1.f;
-    if (p.use_tanh) { const float th = tanhf(ph); T = th * p.coords_range; dT = (1.0f - th * th) * p.coords_range; }
-    float dphi = 0.f, ar[3] = {0.f, 0.f, 0.f}, ac[3] = {0.f, 0.f, 0.f}, am[3] = {0.f, 0.f, 0.f};
-    if (p.which == 0) {
-      const float nrm = sqrtf(d + 1e-8f), den = nrm + p.norm_constant;
-      const float ux = ddx / den, uy = ddy / den, uz = ddz / den;
-      dphi = (g0 * ux + g1 * uy + g2 * uz) * dT;
-      const float du0 = g0 * T, du1 = g1 * T, du2 = g2 * T;
-      const float sdot = (du0 * ddx + du1 * ddy + du2 * ddz) / (nrm * den * den);
-      ar[0] = du0 / den - ddx * sdot; ar[1] = du1 / den - ddy * sdot; ar[2] = du2 / den - ddz * sdot;
-      ac[0] = -ar[0]; ac[1] = -ar[1]; ac[2] = -ar[2];
-    } else {
-      const int b = p.node_batch[r];
-      const float m0 = p.mean[3 * b], m1 = p.mean[3 * b + 1], m2 = p.mean[3 * b + 2];
-      const float a0 = xr[0] - m0, a1_ = xr[1] - m1, a2 = xr[2] - m2;
-      const float b0 = xc[0] - m0, b1 = xc[1] - m1, b2 = xc[2] - m2;
-      const float c0 = a1_ * b2 - a2 * b1, c1 = a2 * b0 - a0 * b2, c2 = a0 * b1 - a1_ * b0;
-      const float cn = sqrtf(c0 * c0 + c1 * c1 + c2 * c2), cden = cn + p.norm_constant;
-      dphi = (g0 * c0 + g1 * c1 + g2 * c2) / cden * dT;
-      const float dc0 = g0 * T, dc1 = g1 * T, dc2 = g2 * T;
-      const float sdot = cn > 0.f ? (dc0 * c0 + dc1 * c1 + dc2 * c2) / (cn * cden * cden) : 0.f;
-      const float e0 = dc0 / cden - c0 * sdot, e1 = dc1 / cden - c1 * sdot, e2 = dc2 / cden - c2 * sdot;   // d cr
-      ar[0] = b1 * e2 - b2 * e1; ar[1] = b2 * e0 - b0 * e2; ar[2] = b0 * e1 - b1 * e0;
-      ac[0] = e1 * a2 - e2 * a1_; ac[1] = e2 * a0 - e0 * a2; ac[2] = e0 * a1_ - e1 * a0;
-      am[0] = -(ar[0] + ac[0]); am[1] = -(ar[1] + ac[1]); am[2] = -(ar[2] + ac[2]);
-    }
-    if (lane == 0) {
+    float hs;                                // the gradient w.r.t. the head's scalar (gate logit / phi)
+    if constexpr (MODE == MODE_GCL) {
+      float sdot = 0.f, att = 1.f;
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        p.gxr[3 * (size_t)e + k] = ar[k];
-        p.gxc[3 * (size_t)e + k] = ac[k];
-        if (p.gm) p.gm[3 * (size_t)e + k] = am[k];
+      for (int k = 0; k < V; ++k) { dout[k] *= inv_norm; sdot = fmaf(dout[k], m[k], sdot); }
+      hs = 0.f;
+      if (attention) {
+        const float gate = sigmoidf_fast(wave_sum_f(dot) + att_b);
+        att = gate;
+        hs = wave_sum_f(sdot) * gate * (1.0f - gate);
+        ps += hs;
       }
+#pragma unroll
+      for (int k = 0; k < V; ++k) dm[k] = fmaf(hs, hw[k], dout[k] * att);
+    } else {
+      const float ph = wave_sum_f(dot);
+      // d_phi and the geometry gradients (egnn_new.py:100-109, 296-316).  SECOND COPY: kernel A's MODE_COORD epilogue above --
+      // change both (why two: train_parts.h, profiles/train_parts.md)
+      const float g0 = p.d_xagg[3 * r] * inv_norm, g1 = p.d_xagg[3 * r + 1] * inv_norm, g2 = p.d_xagg[3 * r + 2] * inv_norm;
+      float T = ph, dT = 1.f;
+      if (p.use_tanh) { const float th = tanhf(ph); T = th * p.coords_range; dT = (1.0f - th * th) * p.coords_range; }
+      float ar[3] = {0.f, 0.f, 0.f}, ac[3] = {0.f, 0.f, 0.f}, am[3] = {0.f, 0.f, 0.f};
+      if (p.which == 0) {
+        const float nrm = sqrtf(d + 1e-8f), den = nrm + p.norm_constant;
+        const float ux = ddx / den, uy = ddy / den, uz = ddz / den;
+        hs = (g0 * ux + g1 * uy + g2 * uz) * dT;
+        const float du0 = g0 * T, du1 = g1 * T, du2 = g2 * T;
+        const float sdot = (du0 * ddx + du1 * ddy + du2 * ddz) / (nrm * den * den);
+        ar[0] = du0 / den - ddx * sdot; ar[1] = du1 / den - ddy * sdot; ar[2] = du2 / den - ddz * sdot;
+        ac[0] = -ar[0]; ac[1] = -ar[1]; ac[2] = -ar[2];
+      } else {
+        const int b = p.node_batch[r];
+        const float m0 = p.mean[3 * b], m1 = p.mean[3 * b + 1], m2 = p.mean[3 * b + 2];
+        const float a0 = xr[0] - m0, a1_ = xr[1] - m1, a2 = xr[2] - m2;
+        const float b0 = xc[0] - m0, b1 = xc[1] - m1, b2 = xc[2] - m2;
+        const float c0 = a1_ * b2 - a2 * b1, c1 = a2 * b0 - a0 * b2, c2 = a0 * b1 - a1_ * b0;
+        const float cn = sqrtf(c0 * c0 + c1 * c1 + c2 * c2), cden = cn + p.norm_constant;
+        hs = (g0 * c0 + g1 * c1 + g2 * c2) / cden * dT;
+        const float dc0 = g0 * T, dc1 = g1 * T, dc2 = g2 * T;
+        const float sdot = cn > 0.f ? (dc0 * c0 + dc1 * c1 + dc2 * c2) / (cn * cden * cden) : 0.f;
+        const float e0 = dc0 / cden - c0 * sdot, e1 = dc1 / cden - c1 * sdot, e2 = dc2 / cden - c2 * sdot;   // d cr
+        ar[0] = b1 * e2 - b2 * e1; ar[1] = b2 * e0 - b0 * e2; ar[2] = b0 * e1 - b1 * e0;
+        ac[0] = e1 * a2 - e2 * a1_; ac[1] = e2 * a0 - e0 * a2; ac[2] = e0 * a1_ - e1 * a0;
+        am[0] = -(ar[0] + ac[0]); am[1] = -(ar[1] + ac[1]); am[2] = -(ar[2] + ac[2]);
+      }
+      if (lane == 0) store_coord_pieces(p.gxr, p.gxc, p.gm, e, ar, ac, am);
+#pragma unroll
+      for (int k = 0; k < V; ++k) dm[k] = hs * hw[k];
     }
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      dz[k] = dphi * w3[k] * dsilu_from(zv[k], sg[k]);
+      dz[k] = dm[k] * dsilu_from(zv[k], sg[k]);
       pb2[k] += dz[k];
-      pv1[k] = fmaf(dphi, m[k], pv1[k]);
+      pv1[k] = fmaf(hs, m[k], pv1[k]);
     }
     st_cols<V>(p.dz_out + (size_t)e * H, lane, dz);
   }
-  st_cols<V>(sP[w], lane, pb2);
-  st_cols<V>(sP[w] + H, lane, pv1);
-  __syncthreads();
-  for (int i = t; i < kPartA * H; i += kThreadsE) {
-    float v = 0.f;
-    if (i < 2 * H) {
-#pragma unroll
-      for (int q = 0; q < NW; ++q) v += sP[q][i];
-    }
-    p.part[(size_t)blockIdx.x * kPartAll * H + (size_t)kPartB * H + i] = v;
-  }
+  // partial vectors of the workgroup: the 16 waves' sums in wave order -> rows 5 .. 7 of its slot ([2][0] = d_att_b)
+  fold16_wave_partials<H, MODE == MODE_GCL>(sP, w, lane, t, pb2, pv1, ps, p.part + ((size_t)blockIdx.x * kPartAll + kPartB) * H);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -655,20 +522,14 @@ __global__ __launch_bounds__(kThreads, 1) void edge_bwd_b_kernel(TrainEdgeArgs p
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int e_base = tile * 128 + w * 32;
     const int e = e_base + j;
-    bool active = e < p.E;
-    int r = 0, cidx = 0;
-    float d0 = 0.f;
-    if (active) {
-      r = p.erow[e]; cidx = p.ecol[e]; d0 = p.ed0[e];
-      if ((unsigned)r >= (unsigned)p.n_nodes || (unsigned)cidx >= (unsigned)p.n_nodes) { active = false; r = 0; cidx = 0; d0 = 0.f; }
-    }
-    float d = 0.f;
+    int r, cidx;
+    float d0, d = 0.f;
+    const bool active = bwd_lane_entry(p.erow, p.ecol, p.ed0, p.E, e, p.n_nodes, r, cidx, d0);
     if (active) {
       const float ddx = p.x[3 * r] - p.x[3 * cidx], ddy = p.x[3 * r + 1] - p.x[3 * cidx + 1], ddz = p.x[3 * r + 2] - p.x[3 * cidx + 2];
       d = ddx * ddx + ddy * ddy + ddz * ddz;
     }
-    const bool rl = r < p.n_lig, cl = cidx < p.n_lig;
-    const int ty = (rl && cl) ? 1 : ((!rl && !cl) ? 2 : 0);
+    const int ty = bwd_edge_type(r, cidx, p.n_lig);
     if (half == 0) { s_row[j] = active ? r : -1; s_col[j] = cidx; s_d[j] = d; s_d0[j] = d0; s_ty[j] = ty; }
 
     f32x16 acc[CT];
@@ -770,13 +631,7 @@ __global__ __launch_bounds__(kThreads, 1) void edge_bwd_b_kernel(TrainEdgeArgs p
     sp[3 * H + 32 * c + j] = pt1[c];
     sp[4 * H + 32 * c + j] = pt2[c];
   }
-  __syncthreads();
-  for (int i = t; i < kPartB * H; i += kThreads) {
-    float v = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v += sB[(size_t)q * kPartB * H + i];
-    p.part[(size_t)blockIdx.x * kPartAll * H + i] = v;                           // rows 0 .. 4 of the workgroup's [8][H] slot
-  }
+  fold_wave_partials<kPartB>(sB, H, t, p.part + (size_t)blockIdx.x * kPartAll * H);       // rows 0 .. 4 of the slot
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -879,133 +734,6 @@ __global__ __launch_bounds__(kThreads) void sample_edge_sum3_kernel(const float*
     __syncthreads();
   }
   if (t < 3) out[3 * b + t] = red[t][0];
-}
-
-// out[g][i] = sum over the parts p in [g gs, min((g + 1) gs, n_part)) of part[p * stride + i], i < width; fixed order.
-// acc: out[g][i] += that sum instead -- the complete sum first, the old value added last with one rounding (the
-// accumulating store of a parameter gradient, dsbdd_train_net_backward_acc)
-__global__ void partial_reduce_kernel(const float* part, int n_part, size_t stride, int width, int gs, float* out,
-                                      size_t out_stride, int acc) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= width) return;
-  const int g = blockIdx.y;
-  const int p0 = g * gs, p1 = min(p0 + gs, n_part);
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  int pi = p0;
-  for (; pi + 4 <= p1; pi += 4) {
-    a0 += part[(size_t)pi * stride + i];
-    a1 += part[(size_t)(pi + 1) * stride + i];
-    a2 += part[(size_t)(pi + 2) * stride + i];
-    a3 += part[(size_t)(pi + 3) * stride + i];
-  }
-  for (; pi < p1; ++pi) a0 += part[(size_t)pi * stride + i];
-  const float v = (a0 + a1) + (a2 + a3);
-  float* o = out + (size_t)g * out_stride + i;
-  *o = acc ? __fadd_rn(*o, v) : v;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Weight gradient:  Cp[z][m][n] = sum over k in chunk z of A[k][m] B[k][n]   (A [K][lda], B [K][ldb]); the chunks are
-// added by partial_reduce_kernel.  Workgroup tile 128 x 128, wave tile 64 x 64 (2 x 2 MFMA tiles of 32 x 32).  The operands
-// go through LDS in slabs of 16 k rows (16-byte coalesced loads one slab ahead in registers, two LDS buffers, one barrier per
-// slab); a wave reads its A / B words with ds_read_b32 (lane = column, the two half-waves one k row apart: the row stride of
-// 160 words puts them on disjoint banks).  First version (operands straight from global memory, one dword load per lane
-// and MFMA): 43 - 48 TFLOP/s on the edge-level gradients (profiles/r4m_wgrad_sweep.md).
-struct WgradArgs { const float* A; int lda; const float* B; int ldb; int K; int M; int N; float* Cp; int kc; };
-
-constexpr int kWgBK = 16, kWgLd = 160;
-
-__device__ __forceinline__ void wgrad_slab_load(const float* X, int ld, int K1, int k, int c0, int C, bool vec, int t,
-                                                f32x4 (&r)[2]) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int q = t + kThreads * i, row = q >> 5, col = c0 + 4 * (q & 31);
-    const int kk = k + row;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (kk < K1) {
-      const float* src = X + (size_t)kk * ld + col;
-      if (vec && col + 3 < C) v = ldv4(src);
-      else {
-        if (col < C) v[0] = src[0];
-        if (col + 1 < C) v[1] = src[1];
-        if (col + 2 < C) v[2] = src[2];
-        if (col + 3 < C) v[3] = src[3];
-      }
-    }
-    r[i] = v;
-  }
-}
-
-__device__ __forceinline__ void wgrad_slab_store(float* buf, int t, const f32x4 (&r)[2]) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int q = t + kThreads * i;
-    *reinterpret_cast<f32x4*>(buf + (q >> 5) * kWgLd + 4 * (q & 31)) = r[i];
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void wgrad_kernel(WgradArgs p) {
-  __shared__ __attribute__((aligned(16))) float sA[2][kWgBK * kWgLd];
-  __shared__ __attribute__((aligned(16))) float sB[2][kWgBK * kWgLd];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int wm = w >> 1, wn = w & 1, j = lane & 31, kh = lane >> 5;
-  const int m0 = blockIdx.x * 128, n0 = blockIdx.y * 128;
-  const int k0 = blockIdx.z * p.kc, k1 = min(p.K, k0 + p.kc);
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[a][b][q] = 0.f;
-  if (k0 < k1) {
-    const bool va = (p.lda & 3) == 0 && (reinterpret_cast<uintptr_t>(p.A) & 15) == 0;
-    const bool vb = (p.ldb & 3) == 0 && (reinterpret_cast<uintptr_t>(p.B) & 15) == 0;
-    f32x4 ra[2], rb[2];
-    wgrad_slab_load(p.A, p.lda, k1, k0, m0, p.M, va, t, ra);
-    wgrad_slab_load(p.B, p.ldb, k1, k0, n0, p.N, vb, t, rb);
-    wgrad_slab_store(sA[0], t, ra);
-    wgrad_slab_store(sB[0], t, rb);
-    __syncthreads();
-    int cur = 0;
-    const int oa = kh * kWgLd + wm * 64 + j, ob = kh * kWgLd + wn * 64 + j;
-#pragma unroll 1
-    for (int k = k0; k < k1; k += kWgBK) {
-      const bool more = k + kWgBK < k1;
-      if (more) {
-        wgrad_slab_load(p.A, p.lda, k1, k + kWgBK, m0, p.M, va, t, ra);
-        wgrad_slab_load(p.B, p.ldb, k1, k + kWgBK, n0, p.N, vb, t, rb);
-      }
-      const float* a_ = sA[cur] + oa;
-      const float* b_ = sB[cur] + ob;
-#pragma unroll
-      for (int s = 0; s < kWgBK / 2; ++s) {
-        const float a0 = a_[2 * s * kWgLd], a1 = a_[2 * s * kWgLd + 32];
-        const float b0 = b_[2 * s * kWgLd], b1 = b_[2 * s * kWgLd + 32];
-        acc[0][0] = mfma32(a0, b0, acc[0][0]);
-        acc[0][1] = mfma32(a0, b1, acc[0][1]);
-        acc[1][0] = mfma32(a1, b0, acc[1][0]);
-        acc[1][1] = mfma32(a1, b1, acc[1][1]);
-      }
-      if (more) {
-        wgrad_slab_store(sA[cur ^ 1], t, ra);
-        wgrad_slab_store(sB[cur ^ 1], t, rb);
-      }
-      __syncthreads();
-      cur ^= 1;
-    }
-  }
-  float* C = p.Cp + (size_t)blockIdx.z * p.M * p.N;
-  const int mb = m0 + wm * 64, nb = n0 + wn * 64;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int m = mb + 32 * a + mfma_row(q, lane), n = nb + 32 * b + j;
-        if (m < p.M && n < p.N) C[(size_t)m * p.N + n] = acc[a][b][q];
-      }
 }
 
 }  // namespace dsbdd

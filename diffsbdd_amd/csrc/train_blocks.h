@@ -1,6 +1,6 @@
-// Training-step building blocks (host side of csrc/train.h; included by engine.hip in front of train_net.h): weight
-// gradients, the edge-stage scratch, side streams, and the forward / backward of one message or coordinate stage.  The
-// dsbdd_train_* entry points over them are in train_api.h.
+// Training-step building blocks (host side of csrc/train.h and csrc/wgrad.h; included by engine.hip in front of
+// train_net.h): weight gradients, the edge-stage scratch, side streams, and the forward / backward of one message or
+// coordinate stage.  The dsbdd_train_* entry points over them are in train_api.h.
 #pragma once
 
 // out[i] = sum_p part[p * stride + i] in a fixed order (two levels above 64 parts); tmp: ceil(n_part / 32) * width floats.
@@ -111,8 +111,8 @@ static hipError_t launch_bwd_b(int H, hipStream_t s, const TrainEdgeArgs& a, int
 static hipError_t launch_bwd_e(int H, hipStream_t s, int mode, const TrainEdgeArgs& a, const float* z2, int grid) {
   return with_hidden(H, [&](auto h) {
     constexpr int HH = decltype(h)::value;
-    if (mode == MODE_COORD) hipLaunchKernelGGL((edge_bwd_ec_kernel<HH>), dim3(grid), dim3(kThreadsE), 0, s, a, z2);
-    else hipLaunchKernelGGL((edge_bwd_e_kernel<HH>), dim3(grid), dim3(kThreadsE), 0, s, a, z2);
+    if (mode == MODE_GCL) hipLaunchKernelGGL((edge_bwd_e_kernel<HH, MODE_GCL>), dim3(grid), dim3(kThreadsE), 0, s, a, z2);
+    else hipLaunchKernelGGL((edge_bwd_e_kernel<HH, MODE_COORD>), dim3(grid), dim3(kThreadsE), 0, s, a, z2);
     return hipGetLastError();
   });
 }

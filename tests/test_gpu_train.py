@@ -166,12 +166,12 @@ def test_edge_first_layer_function(H, emb):
         assert rel_err(e.grad, ed_.grad) < 1e-6
 
 
-def _graph_problem(arch, n_lig, n_poc, seed):
+def _graph_problem(arch, n_lig, n_poc, seed, spread=3.0):
     from diffsbdd_amd.train_hip import TrainGraph
     cfg, _ = W.arch_cfg(arch)
     sd = W.random_state_dict(cfg, seed=3)
     m = make_dynamics(cfg, sd)
-    xl, xp, t, ml, mp = problem(cfg, n_lig, n_poc, seed)
+    xl, xp, t, ml, mp = problem(cfg, n_lig, n_poc, seed, spread=spread)
     x = torch.cat((xl[:, :3], xp[:, :3]), 0).to(dev()).contiguous()
     g = TrainGraph(m, ml.to(dev()), mp.to(dev()), x)
     return cfg, m, g, x
@@ -235,12 +235,18 @@ def test_edge_gcl_function_vs_torch_fp64(arch, n_lig, n_poc, attention):
     ("small_joint", [6, 3], [30, 41]),
     ("small_variant", [8, 5], [33, 29]),
     ("crossdock_fullatom_cond", [23, 18], [286, 250]),
+    ("moad_fullatom_joint", [5, 7, 6], [40, 35, 38]),
 ])
 def test_edge_coord_function_vs_torch_fp64(arch, n_lig, n_poc):
     """EdgeCoord: x_out and the gradients w.r.t. pq, x, the sample mean, ed0 and every parameter of the two coordinate
-    MLPs against float64 torch autograd of egnn_new.py:96-122 + coord2diff / coord2cross."""
+    MLPs against float64 torch autograd of egnn_new.py:96-122 + coord2diff / coord2cross.  moad_fullatom_joint: H = 192,
+    the width whose kernel E takes the scalar branch of ld_cols / st_cols (three columns per lane), both coordinate MLPs
+    on every row (update_pocket_coords), a list of more than two 128-edge tiles with a partly filled last one."""
     from diffsbdd_amd.train_hip import EdgeCoord, SampleMean
-    cfg, m, g, x = _graph_problem(arch, n_lig, n_poc, seed=7)
+    joint192 = arch == "moad_fullatom_joint"
+    cfg, m, g, x = _graph_problem(arch, n_lig, n_poc, seed=7, spread=0.6 if joint192 else 3.0)
+    if joint192:
+        assert cfg["hidden_nf"] == 192 and g.E > 256 and g.E % 128 != 0, (cfg["hidden_nf"], g.E)
     hp = m._hp
     H = cfg["hidden_nf"]
     n_mlp = 1 if hp["reflection_equivariant"] else 2
@@ -463,17 +469,26 @@ def test_side_streams_of_the_backward_keep_the_bits(arch, n_lig, n_poc):
 
 @pytest.mark.parametrize("arch,n_lig,n_poc", [("crossdock_fullatom_cond", [23] * 6, [286] * 6),
                                               ("crossdock_ca_cond", [23, 20, 25, 11], [36, 40, 30, 33]),
-                                              ("small_variant", [5, 7, 6], [40, 35, 38])])
+                                              ("small_variant", [5, 7, 6], [40, 35, 38]),
+                                              ("moad_fullatom_joint", [5, 7, 6], [40, 35, 38])])
 def test_kept_z2_backward_agrees_with_the_recompute_backward(arch, n_lig, n_poc):
     """Round 6: the forward pass of the network path keeps z2 = W2 a1 + b2 of every edge MLP and the backward pass runs the
-    element-wise kernels E / EC (csrc/train.h) where rounds 4 - 5 recomputed the H x H layer in kernel A
+    element-wise kernel E in its two modes (csrc/train.h) where rounds 4 - 5 recomputed the H x H layer in kernel A
     (DSBDD_TRAIN_STORE_Z2=0, read when the handle is created).  Same mathematics, different summation order of the row
     sums: every parameter and input gradient agrees to rounding (1e-5 of the gradient's scale; the oracle comparisons
-    above hold the 1e-4 bound for the default), and each path repeats itself bit for bit."""
+    above hold the 1e-4 bound for the default), and each path repeats itself bit for bit.  moad_fullatom_joint: H = 192
+    (three columns per lane in kernel E: the scalar branch of ld_cols / st_cols), both coordinate MLPs on every row, more
+    than two 128-edge tiles with a partly filled last one."""
     import copy
     cfg, _ = W.arch_cfg(arch)
     sd = W.random_state_dict(cfg, seed=1)
-    xl, xp, t, ml, mp = problem(cfg, n_lig, n_poc, seed=9)
+    joint192 = arch == "moad_fullatom_joint"
+    xl, xp, t, ml, mp = problem(cfg, n_lig, n_poc, seed=9, spread=0.6 if joint192 else 3.0)
+    if joint192:
+        from diffsbdd_amd.train_hip import TrainGraph
+        x = torch.cat((xl[:, :3], xp[:, :3]), 0).to(dev()).contiguous()
+        E = TrainGraph(make_dynamics(cfg, copy.deepcopy(sd)), ml.to(dev()), mp.to(dev()), x).E
+        assert cfg["hidden_nf"] == 192 and E > 256 and E % 128 != 0, (cfg["hidden_nf"], E)
     gen = torch.Generator().manual_seed(7)
     wl, wp = torch.randn(xl.shape, generator=gen).to(dev()), torch.randn(xp.shape, generator=gen).to(dev())
 
