@@ -17,6 +17,7 @@ ABI_VERSION = 6
 # error / status codes (include/diffsbdd_hip.h)
 OK, ERR_ARG, ERR_STATE, ERR_CAPACITY, ERR_LAUNCH = 0, -1, -2, -3, -4
 STATUS_NAN, STATUS_EDGE_OVERFLOW = 1, 2
+MOL_MAX_ATOMS, MOL_STATS, FP_WORDS = 128, 8, 64     # csrc/mol_metrics.h
 
 # weight-slot enums
 G_NAMES = ["ATOM_ENC_W0T", "ATOM_ENC_B0", "ATOM_ENC_W1T", "ATOM_ENC_B1",
@@ -126,6 +127,8 @@ SIGNATURES = {
                                     _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "dsbdd_bond_orders": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _P, C.c_float, C.c_float,
                                     C.c_float, _I32, _P]),
+    "dsbdd_mol_graph_stats": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "dsbdd_fp_diversity": (C.c_int, [_P, _P, _P, _I64, _P, _P]),
     "dsbdd_pack_ligands": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _P, _P, _P, _I64, _I64, _I32, _P, _P, _P, _P, _P]),
     # training-step building blocks (struct arguments are passed by pointer: ctypes.byref / arrays)
     "dsbdd_train_scratch_bytes": (C.c_size_t, [_I32, _I64, _I64]),

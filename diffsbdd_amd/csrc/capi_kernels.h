@@ -1,5 +1,5 @@
 // Thin C-ABI wrappers of the stand-alone kernels (included by engine.hip): DDPM steps (ddpm.h), keyed noise, node GEMM,
-// bond orders (molecule.h), ligand packing (ligand_pack.h), the radius graph (graph.h).
+// bond orders (molecule.h), molecule graph statistics and fingerprint distances (mol_metrics.h), ligand packing (ligand_pack.h), the radius graph (graph.h).
 #pragma once
 
 extern "C" {
@@ -175,6 +175,39 @@ int dsbdd_bond_orders(void* stream, const float* x, const int32_t* atom_type, co
   BondArgs a{x, atom_type, mol_off, bonds1, bonds2, bonds3, margin1, margin2, margin3, n_types, n_max,
              reinterpret_cast<signed char*>(order)};
   hipLaunchKernelGGL(bond_orders_kernel, dim3((unsigned)batch), dim3(64), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_mol_graph_stats(void* stream, const int8_t* order, const int32_t* atom_type, const int32_t* mol_off, int64_t batch,
+                          int32_t n_types, const int32_t* max_valence, int32_t n_max, int32_t orders_in_key,
+                          int32_t* valence, int32_t* label, int32_t* stats, uint64_t* keys, uint32_t* fingerprint,
+                          int32_t* type_counts) {
+  StreamDevice stream_device_(stream);
+  if (!order || !atom_type || !mol_off || !max_valence || !valence || !label || !stats || !keys || !fingerprint ||
+      !type_counts)
+    return fail(DSBDD_ERR_ARG, "null argument");
+  if (batch < 0 || batch > 0x7fffffff || n_types < 1) return fail(DSBDD_ERR_ARG, "bad batch or n_types");
+  if (n_max < 1 || n_max > kMolMaxAtoms)
+    return fail(DSBDD_ERR_ARG, "n_max must be in [1, " + std::to_string(kMolMaxAtoms) + "]");
+  if (batch == 0) return DSBDD_OK;
+  MolGraphArgs a{reinterpret_cast<const signed char*>(order), atom_type, mol_off, max_valence, n_types, n_max,
+                 orders_in_key != 0, valence, label, stats, reinterpret_cast<mm_u64*>(keys), fingerprint, type_counts};
+  hipLaunchKernelGGL(mol_graph_kernel, dim3((unsigned)batch), dim3(64), mol_graph_lds_bytes(n_max),
+                     static_cast<hipStream_t>(stream), a);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_fp_diversity(void* stream, const uint32_t* fingerprint, const int32_t* group_off, int64_t n_groups, double* sum,
+                       int64_t* pairs) {
+  StreamDevice stream_device_(stream);
+  if (!fingerprint || !group_off || !sum || !pairs) return fail(DSBDD_ERR_ARG, "null argument");
+  if (n_groups < 0 || n_groups > 0x7fffffff) return fail(DSBDD_ERR_ARG, "bad n_groups");
+  if (reinterpret_cast<uintptr_t>(fingerprint) & 15) return fail(DSBDD_ERR_ARG, "fingerprints must be 16-byte aligned");
+  if (n_groups == 0) return DSBDD_OK;
+  hipLaunchKernelGGL(fp_diversity_kernel, dim3((unsigned)n_groups), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<const uint4*>(fingerprint), group_off, sum, reinterpret_cast<long long*>(pairs));
   HIP_TRY(hipGetLastError());
   return DSBDD_OK;
 }

@@ -35,6 +35,7 @@
 #include "lig_head.h"
 #include "ligand_pack.h"
 #include "molecule.h"
+#include "mol_metrics.h"
 #include "node_chain.h"
 #include "node_linear.h"
 #include "train.h"

@@ -643,6 +643,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="noise is keyed by (seed, global sample index)")
     ap.add_argument("--trusted-checkpoint", action="store_true",
                     help="allow a full unpickle of the checkpoint file")
+    ap.add_argument("--metrics", action="store_true",
+                    help="write metrics.json next to the output (metrics.MoleculeSetMetrics of the written molecules)")
     a = ap.parse_args(argv)
     bs = a.batch_size or a.n_samples
     assert a.n_samples % bs == 0
@@ -659,6 +661,11 @@ def main(argv=None):
     from .molecules import PROCESS_MOLECULE_COVERAGE
     print("[generate] " + PROCESS_MOLECULE_COVERAGE, file=sys.stderr)
     print(f"wrote {len(molecules)} molecules to {a.outfile}")
+    if a.metrics:
+        from . import metrics
+        summary = metrics.summarize([[m for m in molecules if m is not None]], gen.dataset_info, [os.path.basename(a.pdbfile)], gen.device)
+        metrics.write_summary(os.path.join(os.path.dirname(os.path.abspath(a.outfile)), "metrics.json"), summary,
+                              prefix="[generate] ")
 
 
 if __name__ == "__main__":

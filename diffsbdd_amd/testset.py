@@ -312,6 +312,8 @@ def main(argv=None):
     ap.add_argument("--n_nodes_min", type=int, default=0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--trusted-checkpoint", action="store_true")
+    ap.add_argument("--metrics", action="store_true",
+                    help="write metrics.json (metrics.MoleculeSetMetrics of the raw molecules, one group per pocket)")
     a = ap.parse_args(argv)
     from .molecules import PROCESS_MOLECULE_COVERAGE
     print("[testset] " + PROCESS_MOLECULE_COVERAGE, file=sys.stderr)
@@ -351,6 +353,11 @@ def main(argv=None):
     if rank == 0:
         with open(os.path.join(a.outdir, "process_molecule.txt"), "w") as f:
             f.write(PROCESS_MOLECULE_COVERAGE + "\n")
+    if a.metrics:                               # of the molecules as written under raw/ (this rank's pockets)
+        from . import metrics
+        summary = metrics.summarize([[m for m in j.raw if m is not None] for j in mine], gen.dataset_info, [j.name for j in mine], gen.device)
+        metrics.write_summary(os.path.join(a.outdir, "metrics.json" if world == 1 else f"metrics.rank{rank}.json"), summary,
+                              prefix="[testset] ")
     if rank == 0 and times:
         secs = [t[1] for t in times]
         mean = sum(secs) / len(secs)

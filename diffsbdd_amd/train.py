@@ -19,6 +19,12 @@ Out of scope (refused with a message): `virtual_nodes` (AppendVirtualNodes draws
 `augment_noise > 0` / `augment_rotation` (the reference raises NotImplementedError for them), `gpus > 1` (data-parallel
 ranks; the same effective batch is reached with `accumulate_grad_batches`).
 Accepted and ignored with one warning: `wandb_params`, `visualize_*`, the RDKit-based `eval_params` / `eval_epochs`.
+
+Sampled-molecule evaluation (the reference's `validation_epoch_end`, lightning_modules.py:382-398) is asked for with a key
+of its own, `sample_eval: {every_n_epochs, n_samples, batch_size, timesteps}`: on the due epochs `evaluate_samples()`
+samples ligands for the validation pockets and logs `sample/*` records of `metrics.MoleculeSetMetrics` (see
+`metrics.METRICS_COVERAGE` for what they are).  It draws from keys of its own, (seed, epoch, batch), and touches neither
+the weights nor the training randomness: a run with the block and one without it end with the same weights, bit for bit.
 """
 from __future__ import annotations
 
@@ -38,6 +44,7 @@ from .optim import ClippedAdamW, ReferenceClipper, QUEUE_KEY
 
 DRAWS_PER_STEP = 16          # noise draws reserved per micro-batch (a training forward makes one or two)
 _EVAL_DRAW_BASE = 1 << 40    # validation draws live apart from the training ones
+_SAMPLE_EVAL_KEYS = ("every_n_epochs", "n_samples", "batch_size", "timesteps")
 _IGNORED = ("wandb_params", "visualize_sample_epoch", "visualize_chain_epoch", "eval_params", "eval_epochs",
             "enable_progress_bar", "num_sanity_val_steps", "num_workers")
 
@@ -113,6 +120,13 @@ def check_config(cfg):
     k = cfg.get("accumulate_grad_batches", 1)
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
         raise ValueError(f"accumulate_grad_batches must be an integer >= 1, got {k!r}")
+    if cfg.get("sample_eval") is not None:
+        se = cfg["sample_eval"]
+        if not isinstance(se, dict) or set(se) - set(_SAMPLE_EVAL_KEYS):
+            raise ValueError(f"sample_eval takes the keys {_SAMPLE_EVAL_KEYS}, got {se!r}")
+        for key, v in se.items():
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1):
+                raise ValueError(f"sample_eval.{key} must be an integer >= 1, got {v!r}")
     ignored = [k for k in cfg if k in _IGNORED or k.startswith("visualize_")]
     if ignored:
         warnings.warn("training config: accepted and ignored: " + ", ".join(sorted(ignored)) +
@@ -201,6 +215,8 @@ class Trainer:
         self._t_gen = torch.Generator()
         self.ddpm.t_int_source = self._draw_t
         self._t_key = 0
+        self.sample_eval = cfg.get("sample_eval")
+        self._set_metrics = None           # MoleculeSetMetrics with the training split's keys and type counts, built once
 
     # -- randomness: everything derives from (seed, epoch, micro_step) -----------------------------------------------------
     def _draw_t(self, batch):
@@ -280,6 +296,61 @@ class Trainer:
         self.ddpm.train()
         return float(total / n)
 
+    # -- sampled molecules (lightning_modules.py:412-549) ------------------------------------------------------------------------
+    def _sample_key(self, batch):
+        """The key of one evaluation batch's draws: a function of (seed, epoch, batch), apart from the training keys."""
+        return ((self.seed * 1000003 + self.epoch) * 100003 + int(batch) + _EVAL_DRAW_BASE) % (2 ** 63)
+
+    @torch.no_grad()
+    def evaluate_samples(self):
+        """Samples `sample_eval.n_samples` ligands -- for the validation pockets, item (i * batch_size + j) % len(val) as
+        `sample_and_analyze_given_pocket`, with sizes from `size_distribution.sample_conditional`; the joint model draws
+        whole complexes with `ddpm.sample` -- and evaluates them with one group per pocket against the training split.
+        -> the `sample/*` record.  Leaves the model in training mode and the training keys untouched."""
+        from .metrics import MoleculeSetMetrics, reference_from_dataset
+        se = self.sample_eval or {}
+        val, dev = self.val_set, self.device
+        n_samples = int(se.get("n_samples") or len(val))
+        bs = min(int(se.get("batch_size") or self.cfg["batch_size"]), n_samples)
+        timesteps = se.get("timesteps")
+        if self._set_metrics is None:
+            keys = counts = None
+            if self.train_set is not None and len(self.train_set):
+                keys, counts = reference_from_dataset(self.train_set, self.gen.dataset_info, device=dev)
+            self._set_metrics = MoleculeSetMetrics(self.gen.dataset_info, keys, counts)
+        joint = self.cfg["mode"] == "joint"
+        self.ddpm.eval()
+        xs, types, masks, groups, done = [], [], [], [], 0
+        try:
+            for i in range((n_samples + bs - 1) // bs):
+                n = min(bs, n_samples - done)
+                key = self._sample_key(i)
+                with torch.random.fork_rng(devices=[dev] if dev.type == "cuda" else []):
+                    torch.manual_seed(key)
+                    self.ddpm.seed(key)
+                    if joint:
+                        n_lig, n_pocket = self.ddpm.size_distribution.sample(n)
+                        xh_lig, _, lig_mask, _ = self.ddpm.sample(n, n_lig, n_pocket, timesteps=timesteps, device=dev)
+                        groups += [0] * n
+                    else:
+                        idx = [(i * bs + j) % len(val) for j in range(n)]
+                        _, pocket = self.ligand_and_pocket(val.collate(idx))
+                        n_lig = self.ddpm.size_distribution.sample_conditional(n1=None, n2=pocket["size"])
+                        xh_lig, _, lig_mask, _ = self.ddpm.sample_given_pocket(pocket, n_lig, timesteps=timesteps)
+                        groups += idx
+                xs.append(xh_lig[:, :self.x_dims])
+                types.append(xh_lig[:, self.x_dims:].argmax(1))
+                masks.append(lig_mask + done)
+                done += n
+        finally:
+            self.ddpm.train()
+        res = self._set_metrics.evaluate(torch.cat(xs), torch.cat(types), torch.cat(masks), groups=groups, batch=done)
+        record = {"epoch": self.epoch, "step": self.global_step}
+        for k in ("validity", "connectivity", "uniqueness", "novelty", "diversity", "kl_div_atom_types", "n", "n_valid",
+                  "n_connected", "n_unique"):
+            record["sample/" + k] = res[k]
+        return record
+
     # -- metrics -----------------------------------------------------------------------------------------------------------
     def _log(self, record):
         os.makedirs(self.run_dir, exist_ok=True)
@@ -326,6 +397,8 @@ class Trainer:
             if self.val_set is not None and len(self.val_set):
                 val = self.validate()
                 self._log({"epoch": self.epoch, "step": self.global_step, "loss/val": val})
+                if self.sample_eval is not None and (self.epoch + 1) % int(self.sample_eval.get("every_n_epochs") or 1) == 0:
+                    self._log(self.evaluate_samples())
             self.epoch += 1
             self.batch_in_epoch = 0
             self.save_checkpoint(val)

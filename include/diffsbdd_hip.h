@@ -722,6 +722,31 @@ int dsbdd_bond_orders(void* stream, const float* x, const int32_t* atom_type,
                       float margin1, float margin2, float margin3, int32_t n_max,
                       int8_t* order);
 
+/* Graph statistics of every molecule of such a batch (csrc/mol_metrics.h; the per-molecule part of the reference's
+ * analysis/metrics.py:52-125): one wave per molecule, integers only, no atomics -- every output is a function of the
+ * molecule alone.  order = what dsbdd_bond_orders wrote with the same n_max; n_max in [1, DSBDD_MOL_MAX_ATOMS], anything
+ * larger is refused (a molecule longer than n_max is read as its first n_max atoms, as by dsbdd_bond_orders).
+ * max_valence [n_types]: highest sum of bond orders per type, -1 = not checked.  orders_in_key = 0 treats every bond as a
+ * single one in the keys (skeleton key).  Outputs: valence [N], label [N] (smallest atom index, within the molecule, of the
+ * atom's fragment), stats [batch][DSBDD_MOL_STATS] = n_atoms, n_bonds, atoms over their valence, fragments, size and label
+ * of the largest fragment (ties: smallest atom index; -1 for an empty molecule), 0, 0; keys [batch][2] = colour-refinement
+ * keys of the largest fragment and of the whole sample (invariant under atom renumbering; equal keys mean
+ * refinement-equivalent, not proven isomorphic); fingerprint [batch][64] = 2048 bits of the largest fragment (radius-2
+ * environments); type_counts [batch][n_types].  batch = 0 launches nothing. */
+#define DSBDD_MOL_MAX_ATOMS 128
+#define DSBDD_MOL_STATS 8
+int dsbdd_mol_graph_stats(void* stream, const int8_t* order, const int32_t* atom_type, const int32_t* mol_off,
+                          int64_t batch, int32_t n_types, const int32_t* max_valence, int32_t n_max,
+                          int32_t orders_in_key, int32_t* valence, int32_t* label, int32_t* stats, uint64_t* keys,
+                          uint32_t* fingerprint, int32_t* type_counts);
+
+/* Tanimoto distances inside groups of such fingerprints (the reference's calculate_diversity): fingerprint [M][64] (16-byte
+ * aligned), group_off [n_groups+1] ascending row offsets.  sum [g] = sum over pairs i < j of the group of
+ * 1 - |a & b| / |a | b| (0 for an empty union), float64 in a fixed order; pairs [g] = the number of pairs.  One workgroup
+ * per group. */
+int dsbdd_fp_diversity(void* stream, const uint32_t* fingerprint, const int32_t* group_off, int64_t n_groups, double* sum,
+                       int64_t* pairs);
+
 /* ---- ligands as input: the packed batch of the design front ends -------------*/
 /* One launch that writes the ligand batch of substructure inpainting and of
  * diversification (inpaint.py:114-141, optimize.py:39-62 of the reference build
