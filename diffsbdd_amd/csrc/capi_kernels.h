@@ -1,5 +1,5 @@
 // Thin C-ABI wrappers of the stand-alone kernels (included by engine.hip): DDPM steps (ddpm.h), keyed noise, node GEMM,
-// bond orders (molecule.h), molecule graph statistics and fingerprint distances (mol_metrics.h), ligand packing (ligand_pack.h), the radius graph (graph.h).
+// bond orders (molecule.h), molecule graph statistics and fingerprint distances (mol_metrics.h), ligand packing (ligand_pack.h), the radius graph (radius_graph.h).
 #pragma once
 
 extern "C" {

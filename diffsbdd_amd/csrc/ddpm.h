@@ -6,7 +6,7 @@
 // PyTorch kernels + 2-4 host syncs of the reference step become one launch.
 #pragma once
 #include "common.h"
-#include "graph.h"
+#include "graph_parts.h"   // lower_bound_i64, SampleRows
 
 namespace dsbdd {
 
@@ -104,10 +104,9 @@ __global__ __launch_bounds__(kThreads) void cond_update_kernel(
     int n_lig, const int64_t* mask_poc, int n_poc, int dl, int dp, float alpha_ts, float c_eps,
     float sigma, int remove_com) {
   __shared__ float red[kThreads];
-  const int b = blockIdx.x;
-  const int l0 = lower_bound_i64(mask_lig, n_lig, b), l1 = lower_bound_i64(mask_lig, n_lig, b + 1);
-  const int p0 = lower_bound_i64(mask_poc, n_poc, b), p1 = lower_bound_i64(mask_poc, n_poc, b + 1);
-  cond_update_body(z_lig, xh_poc, eps, NoiseTensor{noise}, l0, l1, p0, p1, dl, dp, alpha_ts, c_eps, sigma, remove_com, red);
+  const SampleRows r = sample_rows(mask_lig, n_lig, mask_poc, n_poc, blockIdx.x);
+  cond_update_body(z_lig, xh_poc, eps, NoiseTensor{noise}, r.l0, r.l1, r.p0, r.p1, dl, dp, alpha_ts, c_eps, sigma, remove_com,
+                   red);
 }
 
 // Joint model: both node sets are denoised, then the COM over ligand+pocket is
@@ -117,10 +116,9 @@ __global__ __launch_bounds__(kThreads) void joint_update_kernel(
     const float* noise_p, const int64_t* mask_lig, int n_lig, const int64_t* mask_poc, int n_poc,
     int dl, int dp, float alpha_ts, float c_eps, float sigma, int center_noise) {
   __shared__ float red[kThreads];
-  const int b = blockIdx.x, t = threadIdx.x;
-  const int l0 = lower_bound_i64(mask_lig, n_lig, b), l1 = lower_bound_i64(mask_lig, n_lig, b + 1);
-  const int p0 = lower_bound_i64(mask_poc, n_poc, b), p1 = lower_bound_i64(mask_poc, n_poc, b + 1);
-  const int nl = l1 - l0, np = p1 - p0;
+  const int t = threadIdx.x;
+  const SampleRows r = sample_rows(mask_lig, n_lig, mask_poc, n_poc, blockIdx.x);
+  const int l0 = r.l0, l1 = r.l1, p0 = r.p0, p1 = r.p1, nl = l1 - l0, np = p1 - p0;
   const float cnt = (nl + np) > 0 ? (float)(nl + np) : 1.f;
   float mn[3] = {0.f, 0.f, 0.f};
   if (center_noise) {   // x part of the noise COM-free over ligand + pocket (en_diffusion.py:932-942)
@@ -159,13 +157,6 @@ __global__ __launch_bounds__(kThreads) void joint_update_kernel(
 // tree over the sample's own rows), so the result for a sample is a pure function of that
 // sample's data -- bitwise reproducible and independent of the batch composition.  They replace
 // chains of ~20-100 small torch kernels (index_add_ with float atomics among them).
-
-struct SampleRows { int l0, l1, p0, p1; };
-__device__ __forceinline__ SampleRows sample_rows(const int64_t* mask_lig, int n_lig, const int64_t* mask_poc,
-                                                  int n_poc, int b) {
-  return SampleRows{lower_bound_i64(mask_lig, n_lig, b), lower_bound_i64(mask_lig, n_lig, b + 1),
-                    lower_bound_i64(mask_poc, n_poc, b), lower_bound_i64(mask_poc, n_poc, b + 1)};
-}
 
 // sum over rows [r0, r1) of columns 0..2 of a [rows][ld] matrix (optionally only rows with sel != 0)
 __device__ __forceinline__ void rows_sum3(const float* a, int ld, int r0, int r1, const float* sel, float* red,

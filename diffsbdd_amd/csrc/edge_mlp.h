@@ -31,7 +31,7 @@
 // each written by exactly one wave with a plain store.  agg_complete_kernel (below) and
 // coord_update_kernel then form  agg[row] + agg_head[T0 + 1] + ... + agg_head[T1]  in tile
 // order, T0 / T1 = tiles of the row's first / last edge (from row_ptr and deg).  Together with
-// the 32-aligned (sample, node set) segments of the edge list (graph.h) every per-row sum is a
+// the 32-aligned (sample, node set) segments of the edge list (radius_graph.h) every per-row sum is a
 // pure function of that sample's data: results are bitwise reproducible and independent of the
 // batch composition / sharding.
 //
@@ -65,6 +65,16 @@ struct EdgeMlpW {
   const float* W2SK;
 };
 
+// dst[k][j * CT + c] = src[k][c * 32 + j] for an [H][H] matrix, CT = H / 32 (EdgeMlpW::W2TP; the other copies are packed
+// by pack16_w2t_kernel, pack_w2e_kernel and pack_w2sk_kernel beside the kernels that read them).
+__global__ void permute_w2t_kernel(const float* src, float* dst, int H) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= H * H) return;
+  const int k = i / H, o = i % H, ct = H / 32;
+  const int j = o / ct, c = o % ct;
+  dst[i] = src[k * H + c * 32 + j];
+}
+
 struct EdgeArgs {
   const int* erow; const int* ecol; const float* ed0;  // [E]
   const int* e_count;     // device scalar: number of edges to process
@@ -89,7 +99,7 @@ struct EdgeArgs {
   size_t xhead_stride;
   float norm_factor;
   int wt_base;            // global index of this launch's first wave tile (the list pointers may start inside the list)
-  int* tile_ctr;          // work-queue counters, all zero between launches (graph.h: kTileCtrInts)
+  int* tile_ctr;          // work-queue counters, all zero between launches (graph_parts.h: kTileCtrInts)
   // -DDSBDD_TIMESTAMPS builds only: [64 workgroups][16 marks] of wall_clock64() (100 MHz) for this launch
   unsigned long long* ts;
   // edge_wave_kernel, MODE_COORD with two MLPs: alternate workgroups take the coordinate /

@@ -46,7 +46,6 @@
 #include "common.h"
 #include "edge_mlp.h"
 #include "edge_parts.h"
-#include "graph.h"
 
 namespace dsbdd {
 

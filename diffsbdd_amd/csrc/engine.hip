@@ -31,7 +31,10 @@
 #include "edge_wave.h"
 #include "edge_wave16.h"
 #include "edge_splitk.h"
-#include "graph.h"
+#include "graph_parts.h"
+#include "radius_graph.h"
+#include "level_list.h"
+#include "geometry.h"
 #include "lig_head.h"
 #include "ligand_pack.h"
 #include "molecule.h"

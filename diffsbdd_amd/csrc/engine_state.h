@@ -77,7 +77,7 @@ static void w2_pack(hipStream_t s, const float* src, void* dst, int H) {
   hipLaunchKernelGGL(K, dim3((H * H + 255) / 256), dim3(256), 0, s, src, static_cast<T*>(dst), H);
 }
 static const W2Kind kW2Kinds[W2_KINDS] = {
-    {4, w2_pack<float, permute_w2t_kernel>},        // lane-grouped copy of the 32-edge kernels (edge_wave.h)
+    {4, w2_pack<float, permute_w2t_kernel>},        // lane-grouped copy of the 32-edge kernels (edge_wave.h; packed in edge_mlp.h)
     {4, w2_pack<float, pack16_w2t_kernel>},         // lane-grouped copy of the 16-edge kernels (edge_wave16.h)
     {6, w2_pack<unsigned short, pack_w2e_kernel>},  // three bf16 planes of the emulated path (edge_wave.h)
     {4, w2_pack<float, pack_w2sk_kernel>}};         // per-wave rotated copy of the split-K kernels (edge_splitk.h)
@@ -103,7 +103,7 @@ struct Workspace {
   int *erow3, *ecol3, *row_ptr3, *deg3, *scan_tmp3, *seg_base3, *node_batch3, *lig_off3, *poc_off3, *twin;
   float *ed02, *ed03, *xframe, *aggB, *agg_headB;
   int* frame_rows;                      // pocket row (0-based in the pocket array) of every frame row
-  // level-ordered list (graph.h, "Level-ordered edge list"): pocket-conditioned calls that return the ligand part only
+  // level-ordered list (level_list.h): pocket-conditioned calls that return the ligand part only
   int *lvl, *seg_rows, *seg_edges, *node_base, *edge_base, *lvl_cnt, *lvl_end, *lvl_list, *row_ptrL, *erowL, *ecolL;
   float* ed0L;
   unsigned long long* lvl_stats;
@@ -174,7 +174,7 @@ struct dsbdd_engine : Workspace {
   int tail = 1;                         // DSBDD_OPT_TAIL: the last round of the exact H = 256 message launches on quarter items (edge_wave.h);
                                         // 0 off, 1 on (default), n > 1: n in place of the resident workgroups in the rule (test hook); DSBDD_TAIL
   int64_t cap_shell = 0;                // slots of one shell list: a level's rows, one padded segment per sample
-  // Memory of the shell stages: the shell lists (graph.h, LevelArgs::sh_*) and the messages of the ghost segment,
+  // Memory of the shell stages: the shell lists (level_list.h, LevelArgs::sh_*) and the messages of the ghost segment,
   // [ghost_slots][H].  The bound workspace keeps its recorded layout and the message buffer's size is the frame's, not
   // known at bind time, so the engine owns this block: laid out by shell_memory (graph_cache.h) before the first call
   // that runs a shell stage -- eagerly, never inside a capture --, kept until the capacities or the frame outgrow it.
@@ -209,10 +209,6 @@ struct dsbdd_engine : Workspace {
   int n_cu = 256;
   int chain = 1;             // DSBDD_NODE_CHAIN=0: the three-launch node phase (node_linear.h) everywhere
   int64_t chain_min_rows = 0;      // (test hook; the choice of kernel must not depend on the batch size: bitwise batch invariance)
-  int fork_front = 0;  // DSBDD_FORK=1: encoders / embedding on a side stream at the head of a call (measured slower, see forward.h)
-  hipStream_t side_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  int level_rows = 0;  // DSBDD_LEVEL_ROWS=1: all-row stages of a pruned call walk the level list (measured slower, see rows_of)
   int fold_scan = 1;   // DSBDD_FOLD_SCAN: 1 (default) = the level ordering's exclusive scans are computed by level_place_kernel
                        // itself (no single-workgroup level_scan_kernel launch) and the block-0 sample mean rides in levels_kernel;
                        // 0 = the separate launches.  (The same fold for the radius graph's own scan -- segment totals by
@@ -261,9 +257,6 @@ struct dsbdd_engine : Workspace {
     for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     drop_graphs();
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
-    if (side_stream) (void)hipStreamDestroy(side_stream);
-    if (ev_fork) (void)hipEventDestroy(ev_fork);
-    if (ev_join) (void)hipEventDestroy(ev_join);
     if (shell_mem) (void)hipFree(shell_mem);
   }
 };
@@ -337,8 +330,6 @@ static void read_env_switches(dsbdd_engine* e) {
       {"DSBDD_NODE_GROUP", &e->node_group}, {"DSBDD_PRUNE", &e->prune}, {"DSBDD_LIG_HEAD", &e->lig_head},
       {"DSBDD_NODE_CHAIN", &e->chain}};
   for (const auto& sw : off_on_zero) if (env_int(sw.first, &v) && v == 0) *sw.second = 0;
-  const std::pair<const char*, int*> on_nonzero[] = {{"DSBDD_LEVEL_ROWS", &e->level_rows}, {"DSBDD_FORK", &e->fork_front}};
-  for (const auto& sw : on_nonzero) if (env_int(sw.first, &v)) *sw.second = v != 0;
   if (env_int("DSBDD_FOLD_SCAN", &v)) e->fold_scan = v > 0 ? 1 : 0;
   if (env_int("DSBDD_GRANULE16", &v, true)) e->granule16 = (unsigned)v;
   if (env_int("DSBDD_SPLITK", &v, true)) e->splitk = (unsigned)v;

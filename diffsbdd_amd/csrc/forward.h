@@ -58,7 +58,7 @@ struct Forward : ForwardArgs {
   // ligand endpoint; the pocket-pocket part comes from the static list built by set_pocket_frame.
   const bool split0 = frame_applies(e, *this);
   // Ligand output only (eps_pocket == nullptr) in pocket-conditioning mode: the stages evaluate the rows the
-  // ligand output depends on, prefixes of the level-ordered list (graph.h, "Level-ordered edge list")
+  // ligand output depends on, prefixes of the level-ordered list (level_list.h)
   const bool prune = e->prune && subset && !ext && !eps_pocket && !e->trace_h && !e->trace_x && nlig > 0;
   const int G_stages = c.n_layers * c.inv_sublayers;
   // Forward cone (identical pockets, one t for the batch): after message stage g only the nodes within g + 1 hops of
@@ -85,8 +85,6 @@ struct Forward : ForwardArgs {
   static constexpr int LV = kLevels - 1;                // "everything"
   // ghost rows are evaluated while a later stage still reads canonical values: the ascending part of the radii
   const int g_ghost_last = ghost_last();
-  const bool fork = e->fork_front && !ext;     // (DSBDD_FORK, see assemble_and_encode)
-  hipStream_t sa = s;                          // the stream of the encoder / embedding chain
   int64_t edge_bound = e->cap_edges;           // edge_list(): the external list's length
   bool mean_in_levels = false;                 // edge_list(): block 0's sample mean was computed by levels_kernel
   // the list the stages after block 0's split run on
@@ -129,7 +127,7 @@ struct Forward : ForwardArgs {
   // stage's shell -- still hold canonical h (and P|Q), and so do their neighbours of level >= g + 1; pocket-pocket distances
   // do not depend on the ligand.  The message of an edge (shell row, column of level >= g + 1) is therefore the one the
   // ghost rows compute for the twin edge in the same launch, and every sample would compute it again.  Such a stage runs
-  // list A = [ghost segment | rows of level <= g] of the main list and list B = the stage's shell list (graph.h: the shell
+  // list A = [ghost segment | rows of level <= g] of the main list and list B = the stage's shell list (level_list.h: the shell
   // rows' edges from columns of level <= g) in one persistent grid, the ghost tiles keep their messages, and
   // agg_complete_shell_kernel adds them to the shell rows' own sums in a fixed order.  Only for exact levels (g + 1 < LV)
   // and the default exact kernel at hidden_nf 256; the kernel variants of the 16-edge / split-K masks and the emulated
@@ -144,13 +142,10 @@ struct Forward : ForwardArgs {
     return n;
   }
   // rows of the nodes of level <= r (r >= kLevels - 1: everything), with or without the ghost rows in front
-  // (round 4 experiment, DSBDD_LEVEL_ROWS=1: the all-row stages of a pruned call walk the level list as well -- a
-  //  permutation of the rows -- so that the active nodes and the ligand rows are PREFIXES of every stage's row list and the
-  //  coordinate projections ride in the node-phase launch of every stage, not only of the radius-limited ones: 3 launches
-  //  fewer per call on the C-alpha and mixed-pocket plans [4,4,4,3,2,1].  Measured 0.5 % SLOWER on both
-  //  (profiles/r4f_ab.md: the grouped node GEMM launch beats the chain's projection passes); off by default)
+  // (the all-row stages keep the natural row order: walking the level list there as well, so that the coordinate
+  //  projections ride in every stage's node-phase launch, was measured 0.5 % slower, profiles/r4f_ab.md)
   void rows_of(int r, bool ghost, NodeLinearArgs& a) const {
-    if (!prune || (r >= LV && !ghost && !e->level_rows)) return;
+    if (!prune || (r >= LV && !ghost)) return;
     if (r > LV) r = LV;
     a.row_idx = ghost ? e->lvl_list : e->lvl_list + n_ghost;
     a.m_count = ghost ? e->lvl_cnt + r : e->lvl_cnt + kLevels + r;
@@ -192,6 +187,23 @@ struct Forward : ForwardArgs {
     }
   }
 
+  // The two-layer MLPs of the two node sets (ligand, pocket): the first n in ONE launch when both fit mlp2_kernel;
+  // otherwise each one that has an output as two node_linear launches through its part of enc_tmp.
+  int mlp2_pair(const Mlp2Problem (&p)[2], int n) {
+    if (mlp2_fits(p[0]) && mlp2_fits(p[1])) {
+      HIP_TRY(launch_mlp2(s, p, n));
+      return DSBDD_OK;
+    }
+    for (int k = 0; k < 2; ++k) {
+      const Mlp2Problem& q = p[k];
+      if (!q.out) continue;
+      float* tmp = e->enc_tmp + (k ? (size_t)n_lig * LE : 0);
+      HIP_TRY(nl(s, q.in, q.ld_in, q.K0, nullptr, 0, 0, q.W0T, q.ldw0, q.b0, nullptr, 0, tmp, LE, q.rows, q.M1, 1));
+      HIP_TRY(nl(s, tmp, LE, q.M1, nullptr, 0, 0, q.W1T, q.ldw1, q.b1, nullptr, 0, q.out, q.ld_out, q.rows, q.n_out, 0));
+    }
+    return DSBDD_OK;
+  }
+
   int assemble_and_encode() {
     // ---- masks -> offsets, split inputs ---------------------------------------
     {
@@ -202,51 +214,24 @@ struct Forward : ForwardArgs {
                          t, (int)t_count, e->x, e->x_in, e->h0, J, JP);
       HIP_TRY(hipGetLastError());
     }
-    // ---- two independent chains at the head of a call: A = encoders -> embedding (-> ghost-row features), needs only the
-    // assembled inputs; B = radius graph -> scan -> fill -> hop levels -> level-ordered list, needs only the coordinates.
-    // Both are strings of short latency-bound kernels (A: 46 us, B: 78 us per call at the benchmark size).  Round 4
-    // experiment, DSBDD_FORK=1: A on an engine-owned side stream, forked and joined by events -- inside a captured graph the
-    // two become parallel branches.  Parity-green (146 GPU tests) and measured SLOWER: 37.56 vs 38.00 ligands/s (full-atom),
-    // 52.7 vs 55.0 (C-alpha), i.e. +40 us per call: a fork / join inside a replayed graph costs more than the 46 us of
-    // serial kernels it hides (profiles/r4g_fork_ab.md; the same finding as round 2's second-stream experiment).  Off.
-    if (fork) {
-      if (!e->side_stream) HIP_TRY(hipStreamCreateWithFlags(&e->side_stream, hipStreamNonBlocking));
-      if (!e->ev_fork) HIP_TRY(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-      if (!e->ev_join) HIP_TRY(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-      HIP_TRY(hipEventRecord(e->ev_fork, s));
-      HIP_TRY(hipStreamWaitEvent(e->side_stream, e->ev_fork, 0));
-      sa = e->side_stream;
-    }
+    // (The encoder / embedding chain below needs only the assembled inputs and the edge list only the coordinates, but
+    //  they stay on one stream: as parallel branches of the captured graph they cost 40 us per call more than the 46 us
+    //  of serial kernels the fork hides, profiles/r4g_fork_ab.md.)
     // ---- encoders (dynamics.py:96-97) -> h0[:, 0:J] ----------------------------
-    {
-      Mlp2Problem enc[2] = {
-          {xh_lig + 3, dl, a, W[DSBDD_G_ATOM_ENC_W0T], pad4(2 * a), W[DSBDD_G_ATOM_ENC_B0], 2 * a,
-           W[DSBDD_G_ATOM_ENC_W1T], pad4(J), W[DSBDD_G_ATOM_ENC_B1], J, e->h0, JP, (int)n_lig},
-          residue_encoder(e, *this)};
-      if (mlp2_fits(enc[0]) && mlp2_fits(enc[1])) {
-        // both node sets, both layers: one launch.  With a pocket frame the pocket's encoding is a constant of the chain:
-        // frame_upkeep computed it before this call (eagerly, so that replayed graphs find it too)
-        HIP_TRY(launch_mlp2(sa, enc, (split0 && e->h0_pocket_valid) ? 1 : 2));
-      } else {
-        HIP_TRY(nl(sa, xh_lig + 3, dl, a, nullptr, 0, 0, W[DSBDD_G_ATOM_ENC_W0T], pad4(2 * a), W[DSBDD_G_ATOM_ENC_B0],
-                   nullptr, 0, e->enc_tmp, LE, n_lig, 2 * a, 1));
-        HIP_TRY(nl(sa, e->enc_tmp, LE, 2 * a, nullptr, 0, 0, W[DSBDD_G_ATOM_ENC_W1T], pad4(J),
-                   W[DSBDD_G_ATOM_ENC_B1], nullptr, 0, e->h0, JP, n_lig, J, 0));
-        float* tmp_p = e->enc_tmp + (size_t)n_lig * LE;
-        HIP_TRY(nl(sa, xh_pocket + 3, dp, r, nullptr, 0, 0, W[DSBDD_G_RES_ENC_W0T], pad4(2 * r), W[DSBDD_G_RES_ENC_B0],
-                   nullptr, 0, tmp_p, LE, n_pocket, 2 * r, 1));
-        HIP_TRY(nl(sa, tmp_p, LE, 2 * r, nullptr, 0, 0, W[DSBDD_G_RES_ENC_W1T], pad4(J), W[DSBDD_G_RES_ENC_B1],
-                   nullptr, 0, e->h0 + (size_t)n_lig * JP, JP, n_pocket, J, 0));
-      }
-    }
+    const Mlp2Problem enc[2] = {
+        {xh_lig + 3, dl, a, W[DSBDD_G_ATOM_ENC_W0T], pad4(2 * a), W[DSBDD_G_ATOM_ENC_B0], 2 * a,
+         W[DSBDD_G_ATOM_ENC_W1T], pad4(J), W[DSBDD_G_ATOM_ENC_B1], J, e->h0, JP, (int)n_lig},
+        residue_encoder(e, *this)};
+    // With a pocket frame the pocket's encoding is a constant of the chain: frame_upkeep computed it before this call
+    // (eagerly, so that replayed graphs find it too)
+    RC_TRY(mlp2_pair(enc, (split0 && e->h0_pocket_valid) ? 1 : 2));
     // ---- embedding (egnn_new.py:233) ---------------------------------------------
-    HIP_TRY(nl(sa, e->h0, JP, JP, nullptr, 0, 0, W[DSBDD_G_EMB_WT], H, W[DSBDD_G_EMB_B], nullptr, 0, e->h, H, N, H, 0));
+    HIP_TRY(nl(s, e->h0, JP, JP, nullptr, 0, 0, W[DSBDD_G_EMB_WT], H, W[DSBDD_G_EMB_B], nullptr, 0, e->h, H, N, H, 0));
     if (split0) {   // the ghost rows start from the embedded features of the pockets they stand for
-      hipLaunchKernelGGL(gather_rows_kernel, dim3((e->frame_n3 + 3) / 4), dim3(kThreads), 0, sa, e->h + (size_t)N * H,
+      hipLaunchKernelGGL(gather_rows_kernel, dim3((e->frame_n3 + 3) / 4), dim3(kThreads), 0, s, e->h + (size_t)N * H,
                          (const float*)(e->h + (size_t)nlig * H), (const int*)e->frame_rows, (int)e->frame_n3, H);
       HIP_TRY(hipGetLastError());
     }
-    if (fork) HIP_TRY(hipEventRecord(e->ev_join, sa));
     return DSBDD_OK;
   }
 
@@ -319,8 +304,6 @@ struct Forward : ForwardArgs {
                          (const int*)e->act_ptr, e->act_list, N);
       HIP_TRY(hipGetLastError());
     }
-    // (the embedding and the ghost rows' features were enqueued with the encoders, on the side stream: join)
-    if (fork) HIP_TRY(hipStreamWaitEvent(s, e->ev_join, 0));
     return DSBDD_OK;
   }
 
@@ -595,18 +578,15 @@ struct Forward : ForwardArgs {
     // few updated rows (the ligand's): one workgroup per sample updates them and reduces the next block's mean;
     // all rows updated (joint model): the wide per-component kernel, the mean stays a launch of its own
     const bool next_mean = subset && n_mlp == 2 && blk + 1 < c.n_layers;
+    const CoordSums sums{e->xagg, e->xagg_head, n_q, ea.xagg_stride, ea.xhead_stride, L_ptr, e->deg, c_max, c_shift};
     if (!subset) {
       if (n_upd > 0) {
-        hipLaunchKernelGGL(coord_update_kernel, dim3((3 * n_upd + 255) / 256), dim3(256), 0, s, e->x,
-                           (const float*)e->xagg, (const float*)e->xagg_head, n_q, ea.xagg_stride, ea.xhead_stride,
-                           L_ptr, (const int*)e->deg, 3 * n_upd, c_max, c_shift);
+        hipLaunchKernelGGL(coord_update_kernel, dim3((3 * n_upd + 255) / 256), dim3(256), 0, s, e->x, sums, 3 * n_upd);
         HIP_TRY(hipGetLastError());
       }
     } else if (n_upd > 0 || next_mean) {
-      hipLaunchKernelGGL(coord_update_mean_kernel, dim3(B), dim3(kThreads), 0, s, e->x, (const float*)e->xagg,
-                         (const float*)e->xagg_head, n_q, ea.xagg_stride, ea.xhead_stride, L_ptr,
-                         (const int*)e->deg, n_upd, (const int*)e->lig_off, (const int*)e->poc_off, nlig,
-                         next_mean ? e->mean : (float*)nullptr, c_max, c_shift);
+      hipLaunchKernelGGL(coord_update_mean_kernel, dim3(B), dim3(kThreads), 0, s, e->x, sums, n_upd,
+                         (const int*)e->lig_off, (const int*)e->poc_off, nlig, next_mean ? e->mean : (float*)nullptr);
       HIP_TRY(hipGetLastError());
     }
     return DSBDD_OK;
@@ -626,29 +606,13 @@ struct Forward : ForwardArgs {
     }
     HIP_TRY(nl(s, e->h, H, H, nullptr, 0, 0, W[DSBDD_G_EMBOUT_WT], JP, W[DSBDD_G_EMBOUT_B], nullptr, 0, e->hout, JP,
                eps_pocket ? N : n_lig, JP, 0));
-    {
-      Mlp2Problem dec[2] = {
-          {e->hout, JP, J, W[DSBDD_G_ATOM_DEC_W0T], pad4(2 * a), W[DSBDD_G_ATOM_DEC_B0], 2 * a,
-           W[DSBDD_G_ATOM_DEC_W1T], pad4(a), W[DSBDD_G_ATOM_DEC_B1], a, eps_lig + 3, dl, (int)n_lig},
-          {e->hout + (size_t)n_lig * JP, JP, J, W[DSBDD_G_RES_DEC_W0T], pad4(2 * r), W[DSBDD_G_RES_DEC_B0], 2 * r,
-           W[DSBDD_G_RES_DEC_W1T], pad4(r), W[DSBDD_G_RES_DEC_B1], r, eps_pocket ? eps_pocket + 3 : nullptr, dp,
-           (int)n_pocket}};
-      if (mlp2_fits(dec[0]) && mlp2_fits(dec[1])) {
-        HIP_TRY(launch_mlp2(s, dec, eps_pocket ? 2 : 1));
-      } else {
-        HIP_TRY(nl(s, e->hout, JP, J, nullptr, 0, 0, W[DSBDD_G_ATOM_DEC_W0T], pad4(2 * a), W[DSBDD_G_ATOM_DEC_B0], nullptr, 0,
-                   e->enc_tmp, LE, n_lig, 2 * a, 1));
-        HIP_TRY(nl(s, e->enc_tmp, LE, 2 * a, nullptr, 0, 0, W[DSBDD_G_ATOM_DEC_W1T], pad4(a), W[DSBDD_G_ATOM_DEC_B1], nullptr, 0,
-                   eps_lig + 3, dl, n_lig, a, 0));
-        if (eps_pocket) {
-          float* tmp_p = e->enc_tmp + (size_t)n_lig * LE;
-          HIP_TRY(nl(s, e->hout + (size_t)n_lig * JP, JP, J, nullptr, 0, 0, W[DSBDD_G_RES_DEC_W0T], pad4(2 * r),
-                     W[DSBDD_G_RES_DEC_B0], nullptr, 0, tmp_p, LE, n_pocket, 2 * r, 1));
-          HIP_TRY(nl(s, tmp_p, LE, 2 * r, nullptr, 0, 0, W[DSBDD_G_RES_DEC_W1T], pad4(r), W[DSBDD_G_RES_DEC_B1], nullptr, 0,
-                     eps_pocket + 3, dp, n_pocket, r, 0));
-        }
-      }
-    }
+    const Mlp2Problem dec[2] = {
+        {e->hout, JP, J, W[DSBDD_G_ATOM_DEC_W0T], pad4(2 * a), W[DSBDD_G_ATOM_DEC_B0], 2 * a,
+         W[DSBDD_G_ATOM_DEC_W1T], pad4(a), W[DSBDD_G_ATOM_DEC_B1], a, eps_lig + 3, dl, (int)n_lig},
+        {e->hout + (size_t)n_lig * JP, JP, J, W[DSBDD_G_RES_DEC_W0T], pad4(2 * r), W[DSBDD_G_RES_DEC_B0], 2 * r,
+         W[DSBDD_G_RES_DEC_W1T], pad4(r), W[DSBDD_G_RES_DEC_B1], r, eps_pocket ? eps_pocket + 3 : nullptr, dp,
+         (int)n_pocket}};
+    RC_TRY(mlp2_pair(dec, eps_pocket ? 2 : 1));
     // ---- velocity, NaN guard, joint-mode COM removal (dynamics.py:136,155-164) --
     hipLaunchKernelGGL(finalize_kernel, dim3(B), dim3(kThreads), 0, s, (const float*)e->x, (const float*)e->x_in,
                        (const int*)e->lig_off, (const int*)e->poc_off, nlig, c.update_pocket_coords, eps_lig, dl,

@@ -164,7 +164,7 @@ static int build_edges_impl(hipStream_t s, const float* x, int n_lig, int N, int
   if (blocks < 1) blocks = 1;
   const Cutoffs cut = cutoffs_of(c);
   // with scan_tmp / seg_base: every (sample, node set) segment of the edge list starts at a wave-tile
-  // boundary (graph.h scan_kernel); without: a compact list (the public dsbdd_build_edges)
+  // boundary (radius_graph.h scan_kernel); without: a compact list (the public dsbdd_build_edges)
   const int aligned = scan_tmp && seg_base;
   SegAlign sg{node_batch, lig_off, poc_off, n_lig, B, scan_tmp, aligned ? seg_base : nullptr};
   EdgeList2 l2{};

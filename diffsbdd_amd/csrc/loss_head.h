@@ -21,6 +21,7 @@
 #pragma once
 #include "common.h"
 #include "ddpm.h"
+#include "graph_parts.h"   // lower_bound_i64
 
 namespace dsbdd {
 
@@ -40,11 +41,6 @@ struct LossCfg {
 
 constexpr int kLossThreads = 256;
 
-__device__ __forceinline__ int lower_bound_i64(const long long* a, int n, long long v) {
-  int lo = 0, hi = n;
-  while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < v) lo = mid + 1; else hi = mid; }
-  return lo;
-}
 // (block_sum of ddpm.h: fixed-order sum of one value per thread, every thread gets the total)
 static_assert(kLossThreads == kThreads, "block_sum reduces kThreads values");
 __device__ __forceinline__ float sigmoid_ref(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -58,7 +54,7 @@ __device__ __forceinline__ float gamma_at(const float* table, int T, float t) {
 }
 
 // engine.edge_capacity in one launch: out[0] = the masks are sorted ascending with ids in [0, batch), out[1] = sum over the
-// samples of the complete graph's edges with every (sample, node set) segment rounded up to 32 (csrc/graph.h).  One
+// samples of the complete graph's edges with every (sample, node set) segment rounded up to 32 (csrc/radius_graph.h).  One
 // workgroup; ~ 25 torch launches (two bincounts, the comparisons, their reductions) before every training forward otherwise.
 __global__ __launch_bounds__(kLossThreads) void edge_capacity_kernel(const long long* ml, int n_l, const long long* mp, int n_p,
                                                                       int batch, long long* out) {

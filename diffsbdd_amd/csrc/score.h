@@ -21,6 +21,7 @@
 #pragma once
 #include "common.h"
 #include "ddpm.h"
+#include "graph_parts.h"   // lower_bound_i64
 #include "loss_head.h"
 
 namespace dsbdd {

@@ -27,6 +27,7 @@
 #include "common.h"
 #include "edge_mlp.h"
 #include "edge_parts.h"
+#include "graph_parts.h"   // block_sum3, SampleRows
 #include "train_parts.h"
 #include "wgrad.h"
 
@@ -721,18 +722,13 @@ __global__ __launch_bounds__(kThreads) void sample_edge_sum3_kernel(const float*
                                                                     const int* poc_off, int n_lig, int e_lim, float* out) {
   __shared__ float red[3][kThreads];
   const int b = blockIdx.x, t = threadIdx.x;
+  const SampleRows r = sample_rows(lig_off, poc_off, n_lig, b);
   float a0 = 0.f, a1 = 0.f, a2 = 0.f;
   for (int seg = 0; seg < 2; ++seg) {
-    const int n0 = seg ? n_lig + poc_off[b] : lig_off[b], n1 = seg ? n_lig + poc_off[b + 1] : lig_off[b + 1];
-    const int e0 = row_ptr[n0], e1 = min(row_ptr[n1], e_lim);
+    const int e0 = row_ptr[seg ? r.p0 : r.l0], e1 = min(row_ptr[seg ? r.p1 : r.l1], e_lim);
     for (int e = e0 + t; e < e1; e += kThreads) { a0 += v[3 * (size_t)e]; a1 += v[3 * (size_t)e + 1]; a2 += v[3 * (size_t)e + 2]; }
   }
-  red[0][t] = a0; red[1][t] = a1; red[2][t] = a2;
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if (t < s) { red[0][t] += red[0][t + s]; red[1][t] += red[1][t + s]; red[2][t] += red[2][t + s]; }
-    __syncthreads();
-  }
+  block_sum3(a0, a1, a2, red);
   if (t < 3) out[3 * b + t] = red[t][0];
 }
 

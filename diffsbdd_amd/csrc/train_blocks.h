@@ -304,8 +304,9 @@ static int coord_forward_impl(void* stream, int32_t H, const dsbdd_train_graph* 
   // CU: twice as many, half as long work items), one coordinate sum per MLP, added by coord_update_kernel
   ea.pass_split = n_mlp == 2 ? 1 : 0;
   HIP_TRY(launch_edge_plain(H, s, MODE_COORD, ea, g->n_edges));
-  return launch_1d(coord_update_kernel, (size_t)(3 * n_upd), s, x_out, ts.xagg, ts.xagg_head, ea.pass_split ? 2 : 1, ea.xagg_stride,
-                   ea.xhead_stride, g->row_ptr, g->deg, (int)(3 * n_upd), (int)((g->n_edges + 31) / 32 + 1), 5);
+  const CoordSums sums{ts.xagg, ts.xagg_head, ea.pass_split ? 2 : 1, ea.xagg_stride, ea.xhead_stride, g->row_ptr, g->deg,
+                       (int)((g->n_edges + 31) / 32 + 1), 5};
+  return launch_1d(coord_update_kernel, (size_t)(3 * n_upd), s, x_out, sums, (int)(3 * n_upd));
 }
 
 static int coord_backward_impl(void* stream, int32_t H, const dsbdd_train_graph* g, const dsbdd_train_mlp* m, int32_t n_mlp,

@@ -125,7 +125,7 @@ def edge_capacity(mask_lig, mask_pocket, batch, check_sorted=True):
     """Upper bound on the length of the engine's edge list: the complete graph
     inside every sample (dynamics.py:170-172, self loops included), with the edges
     of each (sample, node set) segment rounded up to a multiple of 32 (the engine
-    starts every segment at a wave-tile boundary, csrc/graph.h).  One host sync;
+    starts every segment at a wave-tile boundary, csrc/radius_graph.h).  One host sync;
     sampling chains compute it once.  The same sync validates the masks: the
     kernels locate a sample's rows by binary search, so the masks must be sorted
     ascending with ids in [0, batch) (the reference's scatter ops would accept any
@@ -368,8 +368,8 @@ class HipEngine:
         return torch.from_numpy(row[keep].astype("int64")), torch.from_numpy(col[keep].astype("int64"))
 
     def last_levels(self, n_nodes):
-        """Level structures of the last ligand-output-only call in pocket-conditioning mode (csrc/graph.h,
-        "Level-ordered edge list"), as numpy arrays (debug / tests; syncs): dict with level[N], order[N] (nodes by
+        """Level structures of the last ligand-output-only call in pocket-conditioning mode (csrc/level_list.h),
+        as numpy arrays (debug / tests; syncs): dict with level[N], order[N] (nodes by
         (level, id)), count[5] (nodes with level <= r), end[5] (list position where the rows of level <= r end),
         row_ptr[N], deg[N], the re-ordered list row / col / d0 (padding entries have row = -1), and the number of
         ghost nodes / list slots of a canonical pocket in front of them (forward cone)."""

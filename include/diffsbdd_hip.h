@@ -177,7 +177,7 @@ int dsbdd_engine_set_trace(dsbdd_engine* e, float* trace_h, float* trace_x);
  *   status    int32 device word, OR-ed with DSBDD_STATUS_* (caller zeroes it)
  * eps_pocket == NULL in pocket-conditioning mode (what ConditionalDDPM's chains need, conditional_model.py:268-272)
  * lets the engine skip every row the ligand output does not depend on: message stage g of G evaluates the nodes
- * within G - g hops of a ligand atom (csrc/graph.h "Level-ordered edge list"; dsbdd_engine_last_plan reports the
+ * within G - g hops of a ligand atom (csrc/level_list.h; dsbdd_engine_last_plan reports the
  * radii).  eps_lig is the same up to fp32 summation order (different wave-tile boundaries). */
 int dsbdd_dynamics_forward(dsbdd_engine* e, void* stream, const float* xh_lig,
                            const float* xh_pocket, const float* t, int64_t t_count,
@@ -207,7 +207,7 @@ int dsbdd_engine_graph_stats(const dsbdd_engine* e, int64_t* replays, int64_t* c
  * level up to which stage g computed its rows (4 = every row), ghost[g] = 1 when the stage also evaluated the
  * canonical pocket (identical pockets, csrc/forward.h "Forward cone"), timed_level = radius of the launches that
  * dsbdd_engine_profile brackets.  All 4 / 0 unless the call was a ligand-output-only call in pocket-conditioning
- * mode (eps_pocket == NULL), see csrc/graph.h "Level-ordered edge list". */
+ * mode (eps_pocket == NULL), see csrc/level_list.h. */
 int dsbdd_engine_last_plan(const dsbdd_engine* e, int32_t* radius, int32_t* ghost, int32_t capacity,
                            int32_t* n_stages, int32_t* timed_level);
 
@@ -270,7 +270,7 @@ int dsbdd_engine_get_option(const dsbdd_engine* e, int which);
 enum {
   DSBDD_BUF_EDGE_ROW = 0, DSBDD_BUF_EDGE_COL, DSBDD_BUF_EDGE_D0, DSBDD_BUF_ROW_PTR,
   DSBDD_BUF_H, DSBDD_BUF_X, DSBDD_BUF_NODE_BATCH, DSBDD_BUF_DEG,
-  /* level-ordered list of the last ligand-output-only call in pocket-conditioning mode (csrc/graph.h):
+  /* level-ordered list of the last ligand-output-only call in pocket-conditioning mode (csrc/level_list.h):
    * level[N], nodes by (level, id) [N], cumulative node counts [5], edge prefix ends [5], and the list */
   DSBDD_BUF_LEVEL, DSBDD_BUF_LEVEL_LIST, DSBDD_BUF_LEVEL_COUNT, DSBDD_BUF_LEVEL_END,
   DSBDD_BUF_LROW_PTR, DSBDD_BUF_LEDGE_ROW, DSBDD_BUF_LEDGE_COL, DSBDD_BUF_LEDGE_D0,
@@ -280,7 +280,7 @@ enum {
 };
 int dsbdd_engine_buffer(const dsbdd_engine* e, int which, void** ptr_out);
 
-/* Read-out of the shell lists of the last forward-cone call (csrc/graph.h, LevelArgs::sh_*; DSBDD_OPT_SHELL): copies
+/* Read-out of the shell lists of the last forward-cone call (csrc/level_list.h, LevelArgs::sh_*; DSBDD_OPT_SHELL): copies
  * `count` elements to host memory (synchronises the device).  List s = 0, 1 holds the rows of level s + 2 with their edges
  * from columns of level <= s + 1.  STATS: uint64[8] sums over the calls that built the lists, [3 s] edges of list s,
  * [3 s + 1] its slots (32-aligned sample segments), [3 s + 2] the rows' other edges = references to the canonical pocket's

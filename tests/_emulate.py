@@ -38,7 +38,7 @@ def edge_mlp_first(P, Q, row, col, d, d0, typ, wd, wd0, tab):
 
 
 def build_edges(x, mask_l, mask_p, cfg):
-    """graph.h edges_kernel semantics: exact distance, sqrt(d2) <= cutoff."""
+    """radius_graph.h edges_kernel semantics: exact distance, sqrt(d2) <= cutoff."""
     nl = len(mask_l)
     m = torch.cat([mask_l, mask_p])
     d = x[:, None, :] - x[None, :, :]
@@ -235,7 +235,7 @@ def emulate_tile_gemm(Atile, Btile, BM, BN_half_tiles, wave_rows, lda):
 
 
 # ---------------------------------------------------------------------------
-# aligned edge layout + atomic-free aggregation protocol (csrc/graph.h scan_kernel /
+# aligned edge layout + atomic-free aggregation protocol (csrc/radius_graph.h scan_kernel /
 # edges_kernel<true>, csrc/edge_mlp.h): a host model of the index arithmetic
 # ---------------------------------------------------------------------------
 EDGE_ALIGN = 32

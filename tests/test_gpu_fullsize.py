@@ -248,7 +248,7 @@ def test_pocket_frame_block0_split_and_shared_pockets():
 
 
 def _hop_levels(row, col, n_lig, n_nodes, n_levels=5):
-    """Reference for csrc/graph.h levels_kernel: graph distance to the nearest ligand node, capped."""
+    """Reference for csrc/level_list.h levels_kernel: graph distance to the nearest ligand node, capped."""
     lvl = np.full(n_nodes, n_levels - 1, dtype=np.int64)
     lvl[:n_lig] = 0
     for k in range(1, n_levels - 1):
@@ -273,7 +273,7 @@ def _hop_levels(row, col, n_lig, n_nodes, n_levels=5):
 def test_ligand_only_call_evaluates_live_rows(arch, B, frame, monkeypatch):
     """A pocket-conditioned call that returns the ligand part only (what ConditionalDDPM's chains ask for,
     conditional_model.py:268-272) evaluates, per message stage, the rows the ligand output depends on -- prefixes
-    of the level-ordered edge list (csrc/graph.h).  (i) the level structures against a numpy BFS over the
+    of the level-ordered edge list (csrc/level_list.h).  (i) the level structures against a numpy BFS over the
     natural-order list, (ii) ligand eps against the all-rows call (different summation tiles: 2e-5) and the
     oracle (1e-4), (iii) eager / captured / replayed calls and a batch vs its second half: bit-identical."""
     from diffsbdd_amd.engine import edge_capacity

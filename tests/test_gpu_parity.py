@@ -395,7 +395,7 @@ def test_fused_keyed_step_is_bitwise_the_separate_launches():
 
 def test_folded_scans_are_bitwise_the_scan_kernels(monkeypatch):
     """Round 5: the exclusive scans between the two passes of the radius graph and of the level ordering are computed by
-    the fill / place kernels themselves (integer wave sums over segment totals; csrc/graph.h "folded scan") instead of
+    the fill / place kernels themselves (integer wave sums over segment totals; csrc/level_list.h, level_place_kernel) instead of
     two single-workgroup launches.  DSBDD_FOLD_SCAN=0 selects the old launches: the edge lists, the level structures and
     every output must be IDENTICAL -- ragged batch with a sample without ligand atoms and one without pocket atoms,
     calls that return the pocket part (natural-order list) and ligand-only calls (level-ordered list), and a chain with

@@ -58,7 +58,7 @@ def test_packed_weights_and_orchestration_reproduce_golden(name):
 
 @pytest.mark.parametrize("name", ["dyn_small_cond", "dyn_small_joint", "dyn_small_variant"])
 def test_emulated_edge_builder_semantics(name):
-    """graph.h semantics (exact distance, sqrt(d2) <= cutoff, order) vs the
+    """radius_graph.h semantics (exact distance, sqrt(d2) <= cutoff, order) vs the
     reference list, up to the cdist ambiguity band."""
     c = Case(name)
     cfg = make_config(**_hp(c.cfg))
@@ -277,7 +277,7 @@ def test_loss_forward_needs_a_gpu_in_both_modes():
 
 
 def test_aligned_edge_layout_and_atomic_free_aggregation_protocol():
-    """Host model of csrc/graph.h (segment-aligned row offsets) and csrc/edge_mlp.h (tile partial sums
+    """Host model of csrc/radius_graph.h (segment-aligned row offsets) and csrc/edge_mlp.h (tile partial sums
     + ordered head sums): every row's edges are found at [row_ptr, row_ptr + deg), segments start at
     multiples of 32, the protocol reproduces the plain per-row sum exactly on integer-valued data, and a
     sample's rows get bit-identical sums whatever else is in the batch (the tile cut of a row depends only

@@ -42,7 +42,6 @@
 #pragma once
 #include "../diffsbdd_amd/csrc/common.h"
 #include "../diffsbdd_amd/csrc/edge_mlp.h"
-#include "../diffsbdd_amd/csrc/graph.h"
 
 namespace dsbdd {
 

@@ -23,7 +23,7 @@
 #include "../diffsbdd_amd/csrc/edge_mlp.h"
 #include "../diffsbdd_amd/csrc/edge_wave.h"
 #include "../diffsbdd_amd/csrc/edge_wave16.h"
-#include "../diffsbdd_amd/csrc/graph.h"
+#include "../diffsbdd_amd/csrc/geometry.h"   // coord_update_kernel
 
 using namespace dsbdd;
 
@@ -250,14 +250,14 @@ int main(int argc, char** argv) {
     const int g32 = grid32(MODE_COORD, cnt), g16 = grid16(MODE_COORD, cnt, 2), g16b = grid16(MODE_COORD, cnt, 3);
     const float u32 = time_us([&] { hipLaunchKernelGGL((edge_wave_kernel<H, MODE_COORD, true>), dim3(g32), dim3(kThreads), 0, 0, a32); }, reps);
     CK(hipMemset(d_xo[0], 0, (size_t)N * 12));
-    hipLaunchKernelGGL(coord_update_kernel, dim3((3 * nr + 255) / 256), dim3(256), 0, 0, d_xo[0], (const float*)d_xagg, (const float*)d_xhead, 2,
-                       a32.xagg_stride, a32.xhead_stride, (const int*)d_rowptr, (const int*)d_deg, 3 * nr, (int)slots16 - 1, 5);
+    hipLaunchKernelGGL(coord_update_kernel, dim3((3 * nr + 255) / 256), dim3(256), 0, 0, d_xo[0],
+                       CoordSums{d_xagg, d_xhead, 2, a32.xagg_stride, a32.xhead_stride, d_rowptr, d_deg, (int)slots16 - 1, 5}, 3 * nr);
     CK(hipDeviceSynchronize());
     const float u16 = time_us([&] { hipLaunchKernelGGL((edge_wave16_kernel<H, MODE_COORD>), dim3(g16), dim3(kThreads), 0, 0, a16); }, reps);
     const float u16b = time_us([&] { hipLaunchKernelGGL((edge_wave16_kernel<H, MODE_COORD>), dim3(g16b), dim3(kThreads), 0, 0, a16); }, reps);
     CK(hipMemset(d_xo[1], 0, (size_t)N * 12));
-    hipLaunchKernelGGL(coord_update_kernel, dim3((3 * nr + 255) / 256), dim3(256), 0, 0, d_xo[1], (const float*)d_xagg, (const float*)d_xhead, 2,
-                       a16.xagg_stride, a16.xhead_stride, (const int*)d_rowptr, (const int*)d_deg, 3 * nr, (int)slots16 - 1, 4);
+    hipLaunchKernelGGL(coord_update_kernel, dim3((3 * nr + 255) / 256), dim3(256), 0, 0, d_xo[1],
+                       CoordSums{d_xagg, d_xhead, 2, a16.xagg_stride, a16.xhead_stride, d_rowptr, d_deg, (int)slots16 - 1, 4}, 3 * nr);
     CK(hipDeviceSynchronize());
     printf("| COORD, 2 MLPs | %d | %.1f (%d) | %.3f | %.1f (%d) | %.3f | %.1f | %.2e |\n", cnt, u32, g32, fl / u32 / 1e6 / 157.3, u16, g16,
            fl / u16 / 1e6 / 157.3, u16b, maxdiff(d_xo[0], d_xo[1], (size_t)nr * 3));

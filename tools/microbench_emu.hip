@@ -25,7 +25,7 @@
 #include "../diffsbdd_amd/csrc/common.h"
 #include "../diffsbdd_amd/csrc/edge_mlp.h"
 #include "edge_wave_diag.h"   // the round-5 state of csrc/edge_wave.h with its A/B and diagnostic build switches
-#include "../diffsbdd_amd/csrc/graph.h"
+#include "../diffsbdd_amd/csrc/graph_parts.h"   // kTileCtrInts
 
 using namespace dsbdd;
 
