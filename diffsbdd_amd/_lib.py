@@ -184,6 +184,7 @@ SIGNATURES = {
     "dsbdd_optim_bind": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t]),
     "dsbdd_optim_set_params": (C.c_int, [_P, _P, C.POINTER(_P)]),
     "dsbdd_optim_step": (C.c_int, [_P, _P, C.POINTER(_P), C.POINTER(_I32), C.c_double]),
+    "dsbdd_optim_step_ranks": (C.c_int, [_P, _P, _P, _I64, _I32, _P, C.POINTER(_P), C.POINTER(_I32), C.c_double]),
     "dsbdd_optim_state_read": (C.c_int, [_P, _P, C.POINTER(C.c_double), _I32]),
     "dsbdd_optim_state_write": (C.c_int, [_P, _P, C.POINTER(C.c_double), _I32, C.c_double, C.c_double]),
     "dsbdd_lj_potential": (C.c_int, [_P, _P, _I32, _I32, _P, _I64, _I64, _P, C.c_double, _I32, _P, _P, _P]),

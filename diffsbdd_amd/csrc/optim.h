@@ -8,6 +8,8 @@
 //   launch 2  optim_update_kernel  EVERY workgroup reduces the same partials in the same order and derives the same
 //                                  clip coefficient; then p, m, v, vmax of its chunks are updated with the gradient
 //                                  scaled as it is read; workgroup 0 writes the queue of parity p ^ 1 and the counters
+// Data-parallel ranks (dsbdd_optim_step_ranks): launch 1 is optim_reduce_norm_kernel instead, which folds the ranks' gradient
+// buckets in rank order as it reads them and leaves the same partials; launch 2 is unchanged.
 // The queue is double-buffered by step parity: within one launch no workgroup reads what another one writes.
 // No floating-point atomics: every sum has a fixed order, the result is bitwise reproducible.
 // Gradient pointers change every step (fresh allocations of the backward pass) and travel BY VALUE in the kernel
@@ -106,6 +108,69 @@ __global__ __launch_bounds__(kOptimThreads) void optim_norm_kernel(OptimLaunch L
         for (int i = (n4 << 2) + threadIdx.x; i < n; i += kOptimThreads) acc += (double)g[i] * g[i];
       } else {
         for (int i = threadIdx.x; i < n; i += kOptimThreads) acc += (double)g[i] * g[i];
+      }
+    }
+    const double s = block_sum_f64(acc, lds);
+    if (threadIdx.x == 0) L.partial[c] = s;
+  }
+}
+
+// Data-parallel ranks: the flat gradient buckets of n_ranks ranks (layout of the m / v / vmax buffers, OptimChunk::flat),
+// `stride` floats apart, folded in rank order into `out` (which may be one of them).
+struct OptimRanks {
+  const float* gathered;
+  long long stride;
+  int n_ranks;
+  float* out;
+};
+
+// Launch 1 of a data-parallel step: s = ((g[0] + g[1]) + g[2]) + ... per element in float32 (one rounding per add, rank
+// order), s -> out, and the per-chunk sums of s^2 with the thread <- element assignment, the per-thread order and the
+// block_sum_f64 of optim_norm_kernel's 16-byte path: partial[c] has the bits optim_norm_kernel leaves on the reduced
+// bucket.  Every element is read (all ranks) and written by one thread only, so `out` may alias a rank's bucket.
+// A tensor without a gradient is neither read nor written (its region may hold NaN).
+__global__ __launch_bounds__(kOptimThreads) void optim_reduce_norm_kernel(OptimLaunch L, OptimStepArgs A, OptimRanks R) {
+  __shared__ double lds[kOptimThreads / 64];
+  if (L.clip && L.first && blockIdx.x == 0 && threadIdx.x == 0)
+    L.scratch[0] = queue_threshold(L.queue + L.parity * kQueueStride);
+  // float4 accesses need every rank's copy of a chunk 16-byte aligned: flat is a multiple of 4 elements
+  const bool vec = ((reinterpret_cast<uintptr_t>(R.gathered) | reinterpret_cast<uintptr_t>(R.out)) & 15) == 0 &&
+                   (R.n_ranks == 1 || (R.stride & 3) == 0);
+  for (int c = L.chunk_lo + blockIdx.x; c < L.chunk_hi; c += gridDim.x) {
+    const OptimChunk ch = L.chunks[c];
+    double acc = 0.0;
+    if (A.grad[ch.tensor - L.tensor_lo]) {
+      const float* g = R.gathered + ch.flat;
+      float* o = R.out + ch.flat;
+      const int n = ch.count;
+      const int n4 = n >> 2;
+      if (vec) {
+        for (int i = threadIdx.x; i < n4; i += kOptimThreads) {
+          float4 q = reinterpret_cast<const float4*>(g)[i];
+          for (int r = 1; r < R.n_ranks; ++r) {
+            const float4 a = reinterpret_cast<const float4*>(g + r * R.stride)[i];
+            q.x = q.x + a.x; q.y = q.y + a.y; q.z = q.z + a.z; q.w = q.w + a.w;
+          }
+          reinterpret_cast<float4*>(o)[i] = q;
+          acc += (double)q.x * q.x; acc += (double)q.y * q.y; acc += (double)q.z * q.z; acc += (double)q.w * q.w;
+        }
+      } else {
+        for (int i = threadIdx.x; i < n4; i += kOptimThreads) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const int e = 4 * i + k;
+            float q = g[e];
+            for (int r = 1; r < R.n_ranks; ++r) q = q + g[r * R.stride + e];
+            o[e] = q;
+            acc += (double)q * q;
+          }
+        }
+      }
+      for (int e = (n4 << 2) + threadIdx.x; e < n; e += kOptimThreads) {
+        float q = g[e];
+        for (int r = 1; r < R.n_ranks; ++r) q = q + g[r * R.stride + e];
+        o[e] = q;
+        acc += (double)q * q;
       }
     }
     const double s = block_sum_f64(acc, lds);

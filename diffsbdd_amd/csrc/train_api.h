@@ -479,7 +479,10 @@ int dsbdd_optim_set_params(dsbdd_optim* o, void* stream, float* const* params) {
   return DSBDD_OK;
 }
 
-int dsbdd_optim_step(dsbdd_optim* o, void* stream, const float* const* grads, const int32_t* steps, double lr) {
+// R == nullptr: launch 1 is optim_norm_kernel on the caller's gradients (skipped without clipping); else
+// optim_reduce_norm_kernel folds the ranks' buckets into R->out first (always launched: the reduce is needed either way)
+static int optim_step_impl(dsbdd_optim* o, void* stream, const float* const* grads, const int32_t* steps, double lr,
+                           const OptimRanks* R) {
   StreamDevice stream_device_(stream);
   if (!o || !grads || !steps) return fail(DSBDD_ERR_ARG, "null argument");
   if (!o->bound || !o->has_params) return fail(DSBDD_ERR_STATE, "optimiser state or parameters not bound");
@@ -494,7 +497,7 @@ int dsbdd_optim_step(dsbdd_optim* o, void* stream, const float* const* grads, co
   // the scalars torch derives in Python doubles and hands to float32 kernels
   L.decay = (float)(1.0 - lr * c.weight_decay); L.w1 = (float)(1.0 - c.beta1); L.beta2 = (float)c.beta2;
   L.w2 = (float)(1.0 - c.beta2); L.eps = (float)c.eps;
-  for (int pass = c.clip_grad ? 0 : 1; pass < 2; ++pass) {
+  for (int pass = (c.clip_grad || R) ? 0 : 1; pass < 2; ++pass) {
     for (int lo = 0; lo < n; lo += kOptimTensors) {
       const int hi = lo + kOptimTensors < n ? lo + kOptimTensors : n;
       OptimStepArgs A{};
@@ -511,13 +514,31 @@ int dsbdd_optim_step(dsbdd_optim* o, void* stream, const float* const* grads, co
       int grid = L.chunk_hi - L.chunk_lo;
       if (grid > 2 * o->n_cu) grid = 2 * o->n_cu;
       if (grid < 1) grid = 1;
-      if (pass == 0) hipLaunchKernelGGL(optim_norm_kernel, dim3(grid), dim3(kOptimThreads), 0, s, L, A);
+      if (pass == 0 && R) hipLaunchKernelGGL(optim_reduce_norm_kernel, dim3(grid), dim3(kOptimThreads), 0, s, L, A, *R);
+      else if (pass == 0) hipLaunchKernelGGL(optim_norm_kernel, dim3(grid), dim3(kOptimThreads), 0, s, L, A);
       else hipLaunchKernelGGL(optim_update_kernel, dim3(grid), dim3(kOptimThreads), 0, s, L, A);
       HIP_TRY(hipGetLastError());
     }
   }
   if (c.clip_grad) ++o->n_steps;
   return DSBDD_OK;
+}
+
+int dsbdd_optim_step(dsbdd_optim* o, void* stream, const float* const* grads, const int32_t* steps, double lr) {
+  return optim_step_impl(o, stream, grads, steps, lr, nullptr);
+}
+
+int dsbdd_optim_step_ranks(dsbdd_optim* o, void* stream, const float* gathered, int64_t rank_stride, int32_t n_ranks,
+                           float* out_flat, const float* const* grads, const int32_t* steps, double lr) {
+  if (!o || !gathered || !out_flat || !grads) return fail(DSBDD_ERR_ARG, "null argument");
+  if (n_ranks < 1 || n_ranks > 4096) return fail(DSBDD_ERR_ARG, "n_ranks must be 1 to 4096");
+  if (n_ranks > 1 && rank_stride < o->flat_elems) return fail(DSBDD_ERR_ARG, "rank_stride is shorter than one bucket");
+  if ((reinterpret_cast<uintptr_t>(gathered) | reinterpret_cast<uintptr_t>(out_flat)) & 3) return fail(DSBDD_ERR_ARG, "misaligned bucket");
+  for (size_t i = 0; i < o->numel.size(); ++i)
+    if (grads[i] && grads[i] != out_flat + o->offset[i])
+      return fail(DSBDD_ERR_ARG, "gradient " + std::to_string(i) + " is not its region of out_flat (dsbdd_optim_state_offset)");
+  const OptimRanks R{gathered, (long long)rank_stride, (int)n_ranks, out_flat};
+  return optim_step_impl(o, stream, grads, steps, lr, &R);
 }
 
 int dsbdd_optim_state_read(dsbdd_optim* o, void* stream, double* out, int32_t capacity) {

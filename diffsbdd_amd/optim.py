@@ -14,6 +14,11 @@ The state is torch's: `state[p]` holds `step`, `exp_avg`, `exp_avg_sq`, `max_exp
 buffers the kernels stream over), created when `p` first has a gradient, so `state_dict()` / `load_state_dict()`
 exchange with `torch.optim.AdamW(amsgrad=True)`; the queue travels as the extra key `clip_queue`.
 
+Data-parallel ranks: `step_ranks(gathered, n_ranks)` is `step()` on the sum of the ranks' gradient buckets, folded per
+element in rank order (float32, one rounding per add) by the first launch itself (`optim_reduce_norm_kernel` takes the
+place of the norm launch: no extra launch, no extra pass over the gradient), bit for bit what torch's ordered adds into
+the bucket followed by `step()` give.  It needs `n_ranks` gathered buckets on the device beside the optimiser's own.
+
 `ReferenceClipper` is the host-side restatement of the reference's clipping (with its three host read-backs per
 step): the `optimizer="torch"` leg of the trainer, parity tests and tools/train_step_bench.py use it.
 """
@@ -84,10 +89,16 @@ def attach_queue(state_dict, items, n_clips=0):
 class GradientBucket:
     """ONE flat float32 device tensor that holds every parameter's gradient at the offsets of the optimiser's state
     (`dsbdd_optim_state_offset`): the destination of the accumulating backward (train_net.accumulating), and the unit a
-    data-parallel all-reduce would work on.  `view(p)` is the region of parameter `p`, shaped like `p`."""
+    data-parallel exchange works on (`ClippedAdamW.step_ranks`).  `view(p)` is the region of parameter `p`, shaped like
+    `p`.  `flat`: the caller's storage for it (e.g. this rank's slot of a gather buffer) instead of a new tensor."""
 
-    def __init__(self, params, offsets, elems, device):
-        self.flat = torch.zeros(elems, dtype=torch.float32, device=device)
+    def __init__(self, params, offsets, elems, device, flat=None):
+        if flat is None:
+            flat = torch.zeros(elems, dtype=torch.float32, device=device)
+        elif (flat.dtype != torch.float32 or flat.device != torch.device(device) or flat.dim() != 1 or flat.numel() != elems or
+              not flat.is_contiguous() or flat.data_ptr() % 16):
+            raise ValueError("a gradient bucket is a contiguous, 16-byte aligned float32 tensor of %d elements on %s" % (elems, device))
+        self.flat = flat
         self._views = {id(p): self.flat[o:o + p.numel()].view(p.shape) for p, o in zip(params, offsets)}
         self._params = list(params)          # (keeps the ids above alive)
 
@@ -160,12 +171,14 @@ class ClippedAdamW(torch.optim.Optimizer):
         self.state[self._params[i]] = {"step": torch.tensor(float(self._steps[i])), "exp_avg": m, "exp_avg_sq": v,
                                        "max_exp_avg_sq": vmax}
 
-    def gradient_bucket(self):
+    def gradient_bucket(self, flat=None):
         """The optimiser's `GradientBucket`, created on first use and then kept: `step()` reads `p.grad` pointers as ever,
-        which are views of it after an accumulating backward."""
+        which are views of it after an accumulating backward.  `flat`: storage for a bucket that does not exist yet."""
         if self._bucket is None:
             self._bucket = GradientBucket(self._params, self._offsets, int(self.lib.dsbdd_optim_state_elems(self._h)),
-                                          self.device)
+                                          self.device, flat=flat)
+        elif flat is not None:
+            raise ValueError("the gradient bucket exists already: its storage is chosen at its first use")
         return self._bucket
 
     def zero_grad(self, set_to_none=True):
@@ -197,13 +210,53 @@ class ClippedAdamW(torch.optim.Optimizer):
             if self._steps[i] == 1 and p not in self.state:
                 self._make_state(i)
         stream = self._stream()
+        self._follow_params(ptrs, stream)
+        _lib.check(self.lib.dsbdd_optim_step(self._h, stream, self._grad_arr, self._step_arr,
+                                             float(self.param_groups[0]["lr"])), "dsbdd_optim_step")
+        return loss
+
+    def _follow_params(self, ptrs, stream):
         if ptrs != self._ptrs:                                      # the device table follows the parameters' storage
             arr = (C.c_void_p * len(ptrs))(*ptrs)
             _lib.check(self.lib.dsbdd_optim_set_params(self._h, stream, arr), "dsbdd_optim_set_params")
             self._ptrs = ptrs
-        _lib.check(self.lib.dsbdd_optim_step(self._h, stream, self._grad_arr, self._step_arr,
-                                             float(self.param_groups[0]["lr"])), "dsbdd_optim_step")
-        return loss
+
+    @torch.no_grad()
+    def step_ranks(self, gathered, n_ranks):
+        """One step of data-parallel ranks (`dsbdd_optim_step_ranks`): row r of `gathered` (float32, on the device, unit
+        stride within a row; columns past the bucket's length are ignored) starts with rank r's gradient bucket.  The
+        first `n_ranks` rows are summed per element in rank order, ((g0 + g1) + g2) + ..., into this optimiser's bucket
+        by the first launch -- which may BE one of the rows (`gradient_bucket(flat=gathered[r, :elems])`) -- and the step
+        is `step()` on that sum, bit for bit.  `p.grad` is the bucket's view of `p`, or None: the tensor is skipped and
+        its region of every row is neither read nor written.  Step counts and state creation as in `step()`."""
+        bucket = self.gradient_bucket()
+        elems, n_ranks = bucket.flat.numel(), int(n_ranks)
+        if (not torch.is_tensor(gathered) or gathered.dtype != torch.float32 or gathered.device != self.device or
+                gathered.dim() != 2 or gathered.stride(1) != 1 or gathered.shape[1] < elems):
+            raise TypeError("step_ranks needs a 2-d float32 tensor on the parameters' device with rows of at least %d "
+                            "contiguous elements" % elems)
+        if not 1 <= n_ranks <= gathered.shape[0]:
+            raise ValueError("n_ranks must be 1 to the number of rows (%d), got %d" % (gathered.shape[0], n_ranks))
+        ptrs = []
+        for i, p in enumerate(self._params):
+            g = p.grad
+            ptrs.append(p.data_ptr())
+            if g is None:
+                self._grad_arr[i] = None
+                continue
+            view = bucket.view(p)
+            if g.data_ptr() != view.data_ptr() or g.shape != view.shape or g.dtype != torch.float32 or not g.is_contiguous():
+                raise ValueError("step_ranks: p.grad must be the gradient bucket's view of the parameter, or None")
+            self._grad_arr[i] = g.data_ptr()
+            self._steps[i] += 1
+            self._step_arr[i] = self._steps[i]
+            if self._steps[i] == 1 and p not in self.state:
+                self._make_state(i)
+        stream = self._stream()
+        self._follow_params(ptrs, stream)
+        _lib.check(self.lib.dsbdd_optim_step_ranks(self._h, stream, gathered.data_ptr(), gathered.stride(0), n_ranks,
+                                                   bucket.flat.data_ptr(), self._grad_arr, self._step_arr,
+                                                   float(self.param_groups[0]["lr"])), "dsbdd_optim_step_ranks")
 
     # ---- the device-side record ---------------------------------------------------------------------------------------
     def clip_report(self):

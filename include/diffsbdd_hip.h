@@ -682,7 +682,14 @@ int dsbdd_score_reduce(void* stream, int64_t batch, int32_t n_slots, const float
  *     no state update); steps [n_tensors] = the tensor's own step count INCLUDING this step (>= 1; ignored where grads is NULL).
  *   _state_read: out [64] doubles: [0] entries in the queue, [1 .. 50] the entries newest first, [51] clipped steps,
  *     [52] last norm, [53] last threshold, [54] steps, [55] last clip coefficient.  _state_write sets the queue (newest
- *     first) and the two counters. */
+ *     first) and the two counters.
+ *   _step_ranks: the step of data-parallel ranks.  gathered: the flat gradient buckets of the n_ranks contributing ranks
+ *     (each in the layout of _state_offset, rank r at gathered + r * rank_stride floats).  Launch 1 folds them per element in
+ *     rank order, ((g0 + g1) + g2) + ..., float32 adds with one rounding each, stores the sum to out_flat (_state_elems()
+ *     floats; may be one of the inputs) and forms the per-chunk sums of squares with the bits the norm launch of _step
+ *     leaves on that sum; launch 2 is the update launch of _step on out_flat.  Without clipping launch 1 still reduces.
+ *     grads [n_tensors]: NULL = no gradient (the tensor's region is neither read nor written in any bucket and may hold
+ *     NaN), else exactly out_flat + _state_offset(i).  steps, lr: as for _step.  No atomics: bitwise reproducible. */
 typedef struct {
   double lr, beta1, beta2, eps, weight_decay;
   int32_t clip_grad;      /* 0: plain AdamW, one launch */
@@ -696,6 +703,8 @@ size_t dsbdd_optim_workspace_bytes(const dsbdd_optim* o);
 int dsbdd_optim_bind(dsbdd_optim* o, void* stream, float* m, float* v, float* vmax, void* ws, size_t ws_bytes);
 int dsbdd_optim_set_params(dsbdd_optim* o, void* stream, float* const* params);
 int dsbdd_optim_step(dsbdd_optim* o, void* stream, const float* const* grads, const int32_t* steps, double lr);
+int dsbdd_optim_step_ranks(dsbdd_optim* o, void* stream, const float* gathered, int64_t rank_stride, int32_t n_ranks,
+                           float* out_flat, const float* const* grads, const int32_t* steps, double lr);
 int dsbdd_optim_state_read(dsbdd_optim* o, void* stream, double* out, int32_t capacity);
 int dsbdd_optim_state_write(dsbdd_optim* o, void* stream, const double* items, int32_t n_items, double clips, double steps);
 
