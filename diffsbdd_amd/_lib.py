@@ -99,6 +99,7 @@ SIGNATURES = {
                                          _P, _P, _I64, _P, _P, _P]),
     "dsbdd_engine_buffer": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "dsbdd_engine_shell_read": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64]),
+    "dsbdd_engine_list2_read": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
     "dsbdd_engine_graph_stats": (C.c_int, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
     "dsbdd_engine_last_plan": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

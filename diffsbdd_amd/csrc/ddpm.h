@@ -23,6 +23,39 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return r;
 }
 
+// K sums at once, each through block_sum's tree (red[t] += red[t + o], o = kThreads / 2 ... 1: the same pairs in the same
+// order, so the same bits as K block_sum calls), with one set of barriers for all of them; the steps inside wave 0
+// (o < 64) pair registers by lane shuffles and need no barrier.  v holds the totals on return, in every thread.
+constexpr int kRedSlots = 8;
+template <int K>
+__device__ __forceinline__ void block_sum_n(float (&v)[K], float (*red)[kThreads]) {
+  static_assert(K <= kRedSlots && kThreads >= 128, "red[kRedSlots][kThreads]");
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < K; ++k) red[k][t] = v[k];
+  __syncthreads();
+  for (int o = kThreads / 2; o >= 64; o >>= 1) {
+    if (t < o) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) red[k][t] += red[k][t + o];
+    }
+    __syncthreads();
+  }
+  if (t < 64) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float x = red[k][t];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);   // lane t < o takes lane t + o < 2 o: a finished partial sum
+      if (t == 0) red[k][0] = x;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = red[k][0];
+  __syncthreads();
+}
+
 // ---- Philox4x32-10 (Salmon et al. 2011) + Box-Muller -----------------------
 __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
   const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
@@ -76,7 +109,7 @@ struct NoiseKeyed {
 template <class Noise>
 __device__ __forceinline__ void cond_update_body(float* z_lig, float* xh_poc, const float* eps, const Noise& noise, int l0, int l1,
                                                  int p0, int p1, int dl, int dp, float alpha_ts, float c_eps, float sigma,
-                                                 int remove_com, float* red) {
+                                                 int remove_com, float (*red)[kThreads]) {
   const int t = threadIdx.x;
   const int nl = l1 - l0;
   float s[3] = {0.f, 0.f, 0.f};
@@ -92,8 +125,9 @@ __device__ __forceinline__ void cond_update_body(float* z_lig, float* xh_poc, co
   }
   if (!remove_com) return;
   const float cnt = nl > 0 ? (float)nl : 1.f;
-  float m[3];
-  for (int c = 0; c < 3; ++c) m[c] = block_sum(s[c], red) / cnt;
+  float m[3] = {s[0], s[1], s[2]};
+  block_sum_n(m, red);
+  for (int c = 0; c < 3; ++c) m[c] /= cnt;
   for (int idx = t; idx < nl * 3; idx += kThreads) z_lig[(size_t)(l0 + idx / 3) * dl + idx % 3] -= m[idx % 3];
   for (int idx = t; idx < (p1 - p0) * 3; idx += kThreads)
     xh_poc[(size_t)(p0 + idx / 3) * dp + idx % 3] -= m[idx % 3];
@@ -103,8 +137,9 @@ __global__ __launch_bounds__(kThreads) void cond_update_kernel(
     float* z_lig, float* xh_poc, const float* eps, const float* noise, const int64_t* mask_lig,
     int n_lig, const int64_t* mask_poc, int n_poc, int dl, int dp, float alpha_ts, float c_eps,
     float sigma, int remove_com) {
-  __shared__ float red[kThreads];
-  const SampleRows r = sample_rows(mask_lig, n_lig, mask_poc, n_poc, blockIdx.x);
+  __shared__ float red[kRedSlots][kThreads];
+  __shared__ int s_rows[4];
+  const SampleRows r = sample_rows_wg(mask_lig, n_lig, mask_poc, n_poc, blockIdx.x, s_rows);
   cond_update_body(z_lig, xh_poc, eps, NoiseTensor{noise}, r.l0, r.l1, r.p0, r.p1, dl, dp, alpha_ts, c_eps, sigma, remove_com,
                    red);
 }
@@ -115,9 +150,10 @@ __global__ __launch_bounds__(kThreads) void joint_update_kernel(
     float* z_lig, float* z_poc, const float* eps_l, const float* eps_p, const float* noise_l,
     const float* noise_p, const int64_t* mask_lig, int n_lig, const int64_t* mask_poc, int n_poc,
     int dl, int dp, float alpha_ts, float c_eps, float sigma, int center_noise) {
-  __shared__ float red[kThreads];
+  __shared__ float red[kRedSlots][kThreads];
+  __shared__ int s_rows[4];
   const int t = threadIdx.x;
-  const SampleRows r = sample_rows(mask_lig, n_lig, mask_poc, n_poc, blockIdx.x);
+  const SampleRows r = sample_rows_wg(mask_lig, n_lig, mask_poc, n_poc, blockIdx.x, s_rows);
   const int l0 = r.l0, l1 = r.l1, p0 = r.p0, p1 = r.p1, nl = l1 - l0, np = p1 - p0;
   const float cnt = (nl + np) > 0 ? (float)(nl + np) : 1.f;
   float mn[3] = {0.f, 0.f, 0.f};
@@ -127,7 +163,8 @@ __global__ __launch_bounds__(kThreads) void joint_update_kernel(
       for (int c = 0; c < 3; ++c) sl[c] += noise_l[(size_t)i * dl + c];
     for (int i = p0 + t; i < p1; i += kThreads)
       for (int c = 0; c < 3; ++c) sl[c] += noise_p[(size_t)i * dp + c];
-    for (int c = 0; c < 3; ++c) mn[c] = block_sum(sl[c], red) / cnt;
+    block_sum_n(sl, red);
+    for (int c = 0; c < 3; ++c) mn[c] = sl[c] / cnt;
   }
   float s[3] = {0.f, 0.f, 0.f};
   for (int idx = t; idx < nl * dl; idx += kThreads) {
@@ -146,8 +183,9 @@ __global__ __launch_bounds__(kThreads) void joint_update_kernel(
     z_poc[o] = v;
     if (c < 3) s[c] += v;
   }
-  float m[3];
-  for (int c = 0; c < 3; ++c) m[c] = block_sum(s[c], red) / cnt;
+  float m[3] = {s[0], s[1], s[2]};
+  block_sum_n(m, red);
+  for (int c = 0; c < 3; ++c) m[c] /= cnt;
   for (int idx = t; idx < nl * 3; idx += kThreads) z_lig[(size_t)(l0 + idx / 3) * dl + idx % 3] -= m[idx % 3];
   for (int idx = t; idx < np * 3; idx += kThreads) z_poc[(size_t)(p0 + idx / 3) * dp + idx % 3] -= m[idx % 3];
 }
@@ -159,22 +197,28 @@ __global__ __launch_bounds__(kThreads) void joint_update_kernel(
 // chains of ~20-100 small torch kernels (index_add_ with float atomics among them).
 
 // sum over rows [r0, r1) of columns 0..2 of a [rows][ld] matrix (optionally only rows with sel != 0)
-__device__ __forceinline__ void rows_sum3(const float* a, int ld, int r0, int r1, const float* sel, float* red,
-                                          float (&out)[3], float* count = nullptr) {
+__device__ __forceinline__ void rows_sum3(const float* a, int ld, int r0, int r1, const float* sel,
+                                          float (*red)[kThreads], float (&out)[3], float* count = nullptr) {
   float s[3] = {0.f, 0.f, 0.f}, cnt = 0.f;
   for (int i = r0 + (int)threadIdx.x; i < r1; i += kThreads) {
     if (sel && sel[i] == 0.f) continue;
     s[0] += a[(size_t)i * ld]; s[1] += a[(size_t)i * ld + 1]; s[2] += a[(size_t)i * ld + 2];
     cnt += 1.f;
   }
-  for (int c = 0; c < 3; ++c) out[c] = block_sum(s[c], red);
-  if (count) *count = block_sum(cnt, red);
+  if (count) {
+    float v[4] = {s[0], s[1], s[2], cnt};
+    block_sum_n(v, red);
+    out[0] = v[0]; out[1] = v[1]; out[2] = v[2]; *count = v[3];
+  } else {
+    block_sum_n(s, red);
+    out[0] = s[0]; out[1] = s[1]; out[2] = s[2];
+  }
 }
 
 // out[b][0..2] = mean over the rows of sample b of x[:, 0..2]  (scatter_mean, count clamped to >= 1)
 __global__ __launch_bounds__(kThreads) void segment_mean3_kernel(const float* x, int ld, const int64_t* mask,
                                                                  int n_rows, float* out) {
-  __shared__ float red[kThreads];
+  __shared__ float red[kRedSlots][kThreads];
   const int b = blockIdx.x;
   const int r0 = lower_bound_i64(mask, n_rows, b), r1 = lower_bound_i64(mask, n_rows, b + 1);
   float s[3];
@@ -190,9 +234,10 @@ __global__ __launch_bounds__(kThreads) void segment_mean3_kernel(const float* x,
 __global__ __launch_bounds__(kThreads) void cond_affine_noise_kernel(
     float* z_lig, float* xh_poc, const float* noise, const int64_t* mask_lig, int n_lig,
     const int64_t* mask_poc, int n_poc, int dl, int dp, float a, float sigma, int remove_com) {
-  __shared__ float red[kThreads];
+  __shared__ float red[kRedSlots][kThreads];
+  __shared__ int s_rows[4];
   const int t = threadIdx.x;
-  const SampleRows r = sample_rows(mask_lig, n_lig, mask_poc, n_poc, blockIdx.x);
+  const SampleRows r = sample_rows_wg(mask_lig, n_lig, mask_poc, n_poc, blockIdx.x, s_rows);
   const int nl = r.l1 - r.l0;
   float s[3] = {0.f, 0.f, 0.f};
   for (int idx = t; idx < nl * dl; idx += kThreads) {
@@ -204,8 +249,9 @@ __global__ __launch_bounds__(kThreads) void cond_affine_noise_kernel(
   }
   if (!remove_com) return;
   const float cnt = nl > 0 ? (float)nl : 1.f;
-  float m[3];
-  for (int c = 0; c < 3; ++c) m[c] = block_sum(s[c], red) / cnt;
+  float m[3] = {s[0], s[1], s[2]};
+  block_sum_n(m, red);
+  for (int c = 0; c < 3; ++c) m[c] /= cnt;
   for (int idx = t; idx < nl * 3; idx += kThreads) z_lig[(size_t)(r.l0 + idx / 3) * dl + idx % 3] -= m[idx % 3];
   for (int idx = t; idx < (r.p1 - r.p0) * 3; idx += kThreads)
     xh_poc[(size_t)(r.p0 + idx / 3) * dp + idx % 3] -= m[idx % 3];
@@ -219,9 +265,10 @@ __global__ __launch_bounds__(kThreads) void joint_affine_noise_kernel(
     float* z_lig, float* z_poc, const float* noise_l, const float* noise_p, const int64_t* mask_lig,
     int n_lig, const int64_t* mask_poc, int n_poc, int dl, int dp, float a, float sigma,
     int center_noise, int remove_com) {
-  __shared__ float red[kThreads];
+  __shared__ float red[kRedSlots][kThreads];
+  __shared__ int s_rows[4];
   const int t = threadIdx.x;
-  const SampleRows r = sample_rows(mask_lig, n_lig, mask_poc, n_poc, blockIdx.x);
+  const SampleRows r = sample_rows_wg(mask_lig, n_lig, mask_poc, n_poc, blockIdx.x, s_rows);
   const int nl = r.l1 - r.l0, np = r.p1 - r.p0;
   const float cnt = (nl + np) > 0 ? (float)(nl + np) : 1.f;
   float mn[3] = {0.f, 0.f, 0.f};
@@ -249,8 +296,9 @@ __global__ __launch_bounds__(kThreads) void joint_affine_noise_kernel(
     if (c < 3) s[c] += v;
   }
   if (!remove_com) return;
-  float m[3];
-  for (int c = 0; c < 3; ++c) m[c] = block_sum(s[c], red) / cnt;
+  float m[3] = {s[0], s[1], s[2]};
+  block_sum_n(m, red);
+  for (int c = 0; c < 3; ++c) m[c] /= cnt;
   for (int idx = t; idx < nl * 3; idx += kThreads) z_lig[(size_t)(r.l0 + idx / 3) * dl + idx % 3] -= m[idx % 3];
   for (int idx = t; idx < np * 3; idx += kThreads) z_poc[(size_t)(r.p0 + idx / 3) * dp + idx % 3] -= m[idx % 3];
 }
@@ -277,7 +325,7 @@ struct CondRepaintArgs {
 
 template <class Noise>
 __device__ __forceinline__ void cond_repaint_body(const CondRepaintArgs& p, const SampleRows& r, int b, const Noise& noise1,
-                                                  const Noise& noise2, float* red) {
+                                                  const Noise& noise2, float (*red)[kThreads]) {
   const int t = threadIdx.x, dl = p.dl, dp = p.dp;
   const int nl = r.l1 - r.l0, np = r.p1 - r.p0;
   float cp[3];
@@ -298,19 +346,25 @@ __device__ __forceinline__ void cond_repaint_body(const CondRepaintArgs& p, cons
   float m1[3] = {0.f, 0.f, 0.f};
   if (p.remove_com) {
     const float cnt = nl > 0 ? (float)nl : 1.f;
-    for (int c = 0; c < 3; ++c) m1[c] = block_sum(s[c], red) / cnt;
+    block_sum_n(s, red);
+    for (int c = 0; c < 3; ++c) m1[c] = s[c] / cnt;
   } else {
     __syncthreads();
   }
   for (int idx = t; idx < nl * 3; idx += kThreads) p.zk_tmp[(size_t)(r.l0 + idx / 3) * dl + idx % 3] -= m1[idx % 3];
   __syncthreads();   // zk_tmp rows of this sample are re-read by other threads below
   // centres of mass of the fixed atoms of both parts
-  float ck[3], cu[3], nf = 0.f;
-  rows_sum3(p.zk_tmp, dl, r.l0, r.l1, p.fixed, red, ck, &nf);
-  rows_sum3(p.z_lig, dl, r.l0, r.l1, p.fixed, red, cu);
-  const float nfc = nf > 0.f ? nf : 1.f;
+  // (both sums and the count walk the same rows: one pass, one tree; v = known x 3, unknown x 3, count)
+  float v[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int i = r.l0 + t; i < r.l1; i += kThreads) {
+    if (p.fixed[i] == 0.f) continue;
+    for (int c = 0; c < 3; ++c) { v[c] += p.zk_tmp[(size_t)i * dl + c]; v[3 + c] += p.z_lig[(size_t)i * dl + c]; }
+    v[6] += 1.f;
+  }
+  block_sum_n(v, red);
+  const float nfc = v[6] > 0.f ? v[6] : 1.f;
   float dx[3];
-  for (int c = 0; c < 3; ++c) dx[c] = cu[c] / nfc - ck[c] / nfc;
+  for (int c = 0; c < 3; ++c) dx[c] = v[3 + c] / nfc - v[c] / nfc;
   // blend (+ optional q(z_t | z_s))
   float s2[3] = {0.f, 0.f, 0.f};
   for (int idx = t; idx < nl * dl; idx += kThreads) {
@@ -329,7 +383,8 @@ __device__ __forceinline__ void cond_repaint_body(const CondRepaintArgs& p, cons
   float m2[3] = {0.f, 0.f, 0.f};
   if (p.renoise && p.remove_com) {
     const float cnt = nl > 0 ? (float)nl : 1.f;
-    for (int c = 0; c < 3; ++c) m2[c] = block_sum(s2[c], red) / cnt;
+    block_sum_n(s2, red);
+    for (int c = 0; c < 3; ++c) m2[c] = s2[c] / cnt;
     for (int idx = t; idx < nl * 3; idx += kThreads) p.z_lig[(size_t)(r.l0 + idx / 3) * dl + idx % 3] -= m2[idx % 3];
   }
   // the pocket follows every translation of the ligand frame, in the reference's order
@@ -343,8 +398,9 @@ __device__ __forceinline__ void cond_repaint_body(const CondRepaintArgs& p, cons
 }
 
 __global__ __launch_bounds__(kThreads) void cond_repaint_kernel(CondRepaintArgs p) {
-  __shared__ float red[kThreads];
-  const SampleRows r = sample_rows(p.mask_lig, p.n_lig, p.mask_poc, p.n_poc, blockIdx.x);
+  __shared__ float red[kRedSlots][kThreads];
+  __shared__ int s_rows[4];
+  const SampleRows r = sample_rows_wg(p.mask_lig, p.n_lig, p.mask_poc, p.n_poc, blockIdx.x, s_rows);
   cond_repaint_body(p, r, blockIdx.x, NoiseTensor{p.noise1}, NoiseTensor{p.noise2}, red);
 }
 
@@ -362,10 +418,11 @@ struct CondStepArgs {
 };
 
 __global__ __launch_bounds__(kThreads) void cond_step_keyed_kernel(CondStepArgs a) {
-  __shared__ float red[kThreads];
+  __shared__ float red[kRedSlots][kThreads];
+  __shared__ int s_rows[4];
   const int b = blockIdx.x;
   const CondRepaintArgs& p = a.rp;
-  const SampleRows r = sample_rows(p.mask_lig, p.n_lig, p.mask_poc, p.n_poc, b);
+  const SampleRows r = sample_rows_wg(p.mask_lig, p.n_lig, p.mask_poc, p.n_poc, b, s_rows);
   const uint64_t gs = (uint64_t)(a.sample_ids ? a.sample_ids[b] : b + a.sample_offset);
   cond_update_body(p.z_lig, p.xh_poc, a.eps, NoiseKeyed{a.seed, a.draw, gs}, r.l0, r.l1, r.p0, r.p1, p.dl, p.dp, a.u_alpha_ts,
                    a.u_c_eps, a.u_sigma, p.remove_com, red);
@@ -395,9 +452,10 @@ struct JointRepaintArgs {
 };
 
 __global__ __launch_bounds__(kThreads) void joint_repaint_kernel(JointRepaintArgs p) {
-  __shared__ float red[kThreads];
+  __shared__ float red[kRedSlots][kThreads];
+  __shared__ int s_rows[4];
   const int t = threadIdx.x, dl = p.dl, dp = p.dp;
-  const SampleRows r = sample_rows(p.mask_lig, p.n_lig, p.mask_poc, p.n_poc, blockIdx.x);
+  const SampleRows r = sample_rows_wg(p.mask_lig, p.n_lig, p.mask_poc, p.n_poc, blockIdx.x, s_rows);
   const int nl = r.l1 - r.l0, np = r.p1 - r.p0;
   const float cnt = (nl + np) > 0 ? (float)(nl + np) : 1.f;
   float a3[3], b3[3], mn[3];
@@ -461,8 +519,9 @@ __global__ __launch_bounds__(kThreads) void joint_repaint_kernel(JointRepaintArg
     p.z_poc[o] = v;
   }
   if (!p.renoise) return;
-  float m[3];
-  for (int c = 0; c < 3; ++c) m[c] = block_sum(s[c], red) / cnt;
+  float m[3] = {s[0], s[1], s[2]};
+  block_sum_n(m, red);
+  for (int c = 0; c < 3; ++c) m[c] /= cnt;
   for (int idx = t; idx < nl * 3; idx += kThreads) p.z_lig[(size_t)(r.l0 + idx / 3) * dl + idx % 3] -= m[idx % 3];
   for (int idx = t; idx < np * 3; idx += kThreads) p.z_poc[(size_t)(r.p0 + idx / 3) * dp + idx % 3] -= m[idx % 3];
 }

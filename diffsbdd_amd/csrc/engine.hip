@@ -299,6 +299,18 @@ int dsbdd_engine_buffer(const dsbdd_engine* e, int which, void** out) {
   return DSBDD_OK;
 }
 
+int dsbdd_engine_list2_read(const dsbdd_engine* e, int which, void* dst, int64_t count) {
+  if (!e || !dst || count < 0) return fail(DSBDD_ERR_ARG, "bad argument");
+  if (!e->ws) return fail(DSBDD_ERR_STATE, "no workspace bound");
+  const int64_t N = e->cap_lig + e->cap_poc;
+  const int* src = which == DSBDD_LIST2_DEG ? e->deg2 : (which == DSBDD_LIST2_ROW_PTR ? e->row_ptr2 : nullptr);
+  if (!src) return fail(DSBDD_ERR_ARG, "unknown list-2 buffer");
+  if (count > N + (which == DSBDD_LIST2_ROW_PTR ? 1 : 0)) return fail(DSBDD_ERR_CAPACITY, "list-2 read past the buffer");
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(dst, src, (size_t)count * 4, hipMemcpyDeviceToHost));
+  return DSBDD_OK;
+}
+
 int dsbdd_engine_shell_read(const dsbdd_engine* e, int which, int list, void* dst, int64_t count) {
   if (!e || !dst || count < 0) return fail(DSBDD_ERR_ARG, "bad argument");
   if (!e->shell_mem) return fail(DSBDD_ERR_STATE, "no shell stage has run on this engine");

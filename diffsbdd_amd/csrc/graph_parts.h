@@ -84,10 +84,49 @@ __device__ __forceinline__ void block_sum3(float s0, float s1, float s2, float (
   const int t = threadIdx.x;
   red[0][t] = s0; red[1][t] = s1; red[2][t] = s2;
   __syncthreads();
-  for (int o = kThreads / 2; o > 0; o >>= 1) {
+  for (int o = kThreads / 2; o >= 64; o >>= 1) {
     if (t < o) { red[0][t] += red[0][t + o]; red[1][t] += red[1][t + o]; red[2][t] += red[2][t + o]; }
     __syncthreads();
   }
+  // the steps o = 32 .. 1 stay inside wave 0: the same pairs (t, t + o) in the same order, by lane shuffles, no barriers
+  if (t < 64) {
+    float x0 = red[0][t], x1 = red[1][t], x2 = red[2][t];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { x0 += __shfl_down(x0, o); x1 += __shfl_down(x1, o); x2 += __shfl_down(x2, o); }
+    if (t == 0) { red[0][0] = x0; red[1][0] = x1; red[2][0] = x2; }
+  }
+  __syncthreads();
+}
+
+// first index of the sorted a[0..n) whose entry is >= v, found by the 64 lanes of a wave together: every round probes 64
+// evenly spaced entries and keeps the gap the answer lies in -- 3 dependent loads for 2^18 entries, where the bisection of
+// lower_bound_i64 takes 18.  The same integer.
+template <class I>
+__device__ __forceinline__ int lower_bound_wave(const I* a, int n, long long v, int lane) {
+  static_assert(sizeof(I) == 8, "64-bit masks");
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int step = (hi - lo + 63) / 64;
+    const int idx = lo + lane * step;
+    const int c = __popcll(__ballot(idx < hi && a[idx] < v));   // sorted: the probes below v are the first c
+    if (c == 0) return lo;
+    const int last = lo + (c - 1) * step;                        // a[last] < v <= a[last + step] (or the end)
+    hi = min(last + step, hi);
+    lo = last + 1;
+  }
+  return lo;
+}
+
+// sample_rows from the masks by the four waves of a workgroup at once (wave w finds bound w); s_rows: 4 ints of LDS
+__device__ __forceinline__ SampleRows sample_rows_wg(const int64_t* mask_lig, int n_lig, const int64_t* mask_poc,
+                                                     int n_poc, int b, int* s_rows) {
+  static_assert(kThreads == 256, "one wave per bound");
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int r = w < 2 ? lower_bound_wave(mask_lig, n_lig, b + (w & 1), lane)
+                      : lower_bound_wave(mask_poc, n_poc, b + (w & 1), lane);
+  if (lane == 0) s_rows[w] = r;
+  __syncthreads();
+  return SampleRows{s_rows[0], s_rows[1], s_rows[2], s_rows[3]};
 }
 
 // mean[b] = mean of x over ALL nodes of sample b = blockIdx.x (egnn_new.py:307-310): the body of sample_mean_kernel, of

@@ -173,7 +173,7 @@ static int build_edges_impl(hipStream_t s, const float* x, int n_lig, int N, int
                      poc_off, n_lig, N, cut, deg, (const int*)nullptr, (int*)nullptr, (int*)nullptr,
                      (float*)nullptr, 0, status, act_flag, SegAlign{}, (int*)nullptr, l2, 0, lvl);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, (const int*)deg, row_ptr, N, sg,
+  hipLaunchKernelGGL(scan_kernel, dim3(l2.deg ? 2 : 1), dim3(1024), 0, s, (const int*)deg, row_ptr, N, sg,
                      (const int*)l2.deg, l2.row_ptr, l2.seg);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL((edges_kernel<true>), dim3(blocks), dim3(kThreads), 0, s, x, node_batch, lig_off,

@@ -17,7 +17,9 @@
 // its segment depends on its own sample only, so results stay independent of the batch composition.
 //
 //   levels_kernel   one workgroup per sample: hop levels 2, 3 by relaxation over the natural-order list
-//                   (level 1 comes from the count pass), then rows / edges per (level, sample)
+//                   (level 1 comes from the count pass), then rows / edges per (level, sample); the sample's
+//                   levels are held in LDS and its pocket-row edges in registers, one thread per edge (row
+//                   walk over global memory for a sample that does not fit)
 //   level_scan_kernel   one workgroup: exclusive scans over the kLevels * B segments
 //   level_place_kernel  one workgroup per sample, wave L places level L: new row_ptr, lvl_list, pads
 //   level_copy_kernel   one thread per natural-list slot: move the edge to its new position (and to its shell list)
@@ -63,14 +65,15 @@ struct LevelArgs {
   unsigned long long* sh_stats;
 };
 
-__global__ __launch_bounds__(kThreads) void levels_kernel(LevelArgs a) {
-  __shared__ int s_rows[kLevels], s_edges[kLevels], s_shell[kShellLists];
-  __shared__ float s_red[3][kThreads];
-  if (a.mean_out) sample_mean_body(a.mean_x, a.lig_off, a.poc_off, a.n_lig, a.mean_out, s_red);
-  const int b = blockIdx.x, t = threadIdx.x;
-  const SampleRows r = sample_rows(a.lig_off, a.poc_off, a.n_lig, b);
-  if (t < kLevels) { s_rows[t] = 0; s_edges[t] = 0; }
-  if (t < kShellLists) s_shell[t] = 0;
+// levels_kernel keeps a sample's pocket levels in LDS and its pocket-row edges in registers when they fit (a sample is
+// a few hundred nodes and a few thousand edges); a larger sample takes the walk over global memory (levels_rows_global).
+constexpr int kLvlRows = 2048;     // pocket rows of a sample held in LDS
+constexpr int kLvlEdges = 8192;    // slots of the sample's pocket segment of the natural-order list held in registers
+
+// One thread per pocket row, over global memory: the relaxation passes, then the row / edge / shell counts.
+__device__ __forceinline__ void levels_rows_global(const LevelArgs& a, const SampleRows& r, int* s_rows, int* s_edges,
+                                                   int* s_shell) {
+  const int t = threadIdx.x;
   for (int k = 2; k < kLevels - 1; ++k) {
     __syncthreads();                       // level k-1 is final (global writes of this workgroup are visible to it)
     for (int i = r.p0 + t; i < r.p1; i += kThreads) {
@@ -100,6 +103,126 @@ __global__ __launch_bounds__(kThreads) void levels_kernel(LevelArgs a) {
       atomicAdd(&s_shell[L - 2], d2);
     }
   }
+}
+
+// The same results from LDS and registers, one thread per EDGE: the pocket rows of a sample own one contiguous piece
+// [e0, e1) of the natural-order list (rows in node order, then the segment's padding).  levels_stage reads the piece
+// once, coalesced, every load independent of the others, into (row, column) codes local to the sample that stay in the
+// thread's registers (thread t owns slots t, t + kThreads, ...); levels_solve then runs the passes and the shell count
+// on the sample's levels in LDS.  Entries that are no edge of this sample's pocket rows (padding; anything at all
+// after an overflow of the list) get code -1 and are skipped.
+constexpr int kLvlPer = kLvlEdges / kThreads;   // edge slots per thread
+constexpr int kLvlBatch = 8;                     // slots whose LDS reads are issued together
+constexpr int kLvlStage = 16;                    // slots whose global loads are issued together
+constexpr int kLvlLig = 0xffff;                  // column code of a ligand node (its level is 0)
+static_assert(kLvlPer % kLvlBatch == 0 && kLvlPer % kLvlStage == 0 && kLvlRows < kLvlLig, "codes: row << 16 | column");
+
+__device__ __forceinline__ void levels_stage(const LevelArgs& a, const SampleRows& r, int e0, int ne, int (&code)[kLvlPer],
+                                             int* s_lvl, int* s_deg, int* s_cnt) {
+  const int t = threadIdx.x, np = r.p1 - r.p0;
+  for (int i = t; i < np; i += kThreads) { s_lvl[i] = a.lvl[r.p0 + i]; s_deg[i] = a.deg[r.p0 + i]; s_cnt[i] = 0; }
+#pragma unroll
+  for (int u = 0; u < kLvlPer; ++u) code[u] = -1;
+  if (ne <= 0) return;
+#pragma unroll
+  for (int g = 0; g < kLvlPer; g += kLvlStage) {
+    if (g * kThreads >= ne) break;         // (the same for every thread)
+    int row[kLvlStage], col[kLvlStage];
+#pragma unroll
+    for (int u = 0; u < kLvlStage; ++u) {  // unconditional loads (a slot past the end reads the last one): one latency
+      const int q = min((g + u) * kThreads + t, ne - 1);
+      row[u] = a.erow_nat[e0 + q];
+      col[u] = a.ecol_nat[e0 + q];
+    }
+#pragma unroll
+    for (int u = 0; u < kLvlStage; ++u) {
+      const int i = row[u], j = col[u];
+      const bool mine = (g + u) * kThreads + t < ne && i >= r.p0 && i < r.p1;
+      const int jc = (j >= r.l0 && j < r.l1) ? kLvlLig : ((j >= r.p0 && j < r.p1) ? j - r.p0 : -1);
+      code[g + u] = (mine && jc >= 0) ? (((i - r.p0) << 16) | jc) : -1;
+    }
+  }
+}
+
+__device__ __forceinline__ void levels_solve(const LevelArgs& a, const SampleRows& r, int ne, const int (&code)[kLvlPer],
+                                             int* s_rows, int* s_edges, int* s_shell, int* s_lvl, const int* s_deg,
+                                             int* s_cnt) {
+  const int t = threadIdx.x, np = r.p1 - r.p0;
+  for (int k = 2; k < kLevels - 1; ++k) {
+    __syncthreads();                       // level k-1 is final
+#pragma unroll
+    for (int g = 0; g < kLvlPer; g += kLvlBatch) {
+      if (g * kThreads >= ne) break;       // (the same for every thread)
+      int li[kLvlBatch], lj[kLvlBatch];
+#pragma unroll
+      for (int u = 0; u < kLvlBatch; ++u) {
+        // (reads at a safe index whatever the code, then the choice: nothing waits inside a branch)
+        const int c = code[g + u], j = c & 0xffff;
+        const bool pj = c >= 0 && j != kLvlLig;              // (a ligand neighbour would have made the row level 1)
+        const int vi = s_lvl[c >= 0 ? c >> 16 : 0], vj = s_lvl[pj ? j : 0];
+        li[u] = c >= 0 ? vi : -1;
+        lj[u] = pj ? vj : -1;
+      }
+      // writers of this pass store k over kLevels-1 and readers test == k-1: no race
+#pragma unroll
+      for (int u = 0; u < kLvlBatch; ++u)
+        if (li[u] == kLevels - 1 && lj[u] == k - 1) s_lvl[code[g + u] >> 16] = k;
+    }
+  }
+  __syncthreads();                         // the levels are final
+  if (a.n_shell > 0) {
+#pragma unroll
+    for (int g = 0; g < kLvlPer; g += kLvlBatch) {
+      if (g * kThreads >= ne) break;
+      int li[kLvlBatch], lj[kLvlBatch];
+#pragma unroll
+      for (int u = 0; u < kLvlBatch; ++u) {
+        const int c = code[g + u], j = c & 0xffff;
+        const bool pj = c >= 0 && j != kLvlLig;
+        const int vi = s_lvl[c >= 0 ? c >> 16 : 0], vj = s_lvl[pj ? j : 0];
+        li[u] = c >= 0 ? vi : -1;
+        lj[u] = pj ? vj : 0;                                 // (a ligand column: level 0)
+      }
+      // a shell row's edges from columns one level further in
+#pragma unroll
+      for (int u = 0; u < kLvlBatch; ++u)
+        if (li[u] >= 2 && li[u] - 2 < a.n_shell && lj[u] < li[u]) atomicAdd(&s_cnt[code[g + u] >> 16], 1);
+    }
+  }
+  __syncthreads();
+  for (int i = t; i < np; i += kThreads) {
+    const int L = s_lvl[i];
+    if (L >= 2 && L < kLevels - 1) a.lvl[r.p0 + i] = L;   // (the other levels are what edges_kernel wrote)
+    atomicAdd(&s_rows[L], 1);              // integer sums: order does not matter
+    atomicAdd(&s_edges[L], s_deg[i]);
+    if (L >= 2 && L - 2 < a.n_shell) {
+      a.sh_deg[r.p0 + i] = s_cnt[i];
+      atomicAdd(&s_shell[L - 2], s_cnt[i]);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void levels_kernel(LevelArgs a) {
+  __shared__ int s_rows[kLevels], s_edges[kLevels], s_shell[kShellLists];
+  __shared__ float s_red[3][kThreads];
+  __shared__ int s_lvl[kLvlRows], s_deg[kLvlRows], s_cnt[kLvlRows];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const SampleRows r = sample_rows(a.lig_off, a.poc_off, a.n_lig, b);
+  // the pocket rows' piece of the natural-order list (clipped like every walk over it)
+  int e0 = 0, e1 = 0;
+  if (r.p1 > r.p0) {
+    e0 = max(a.row_ptr_nat[r.p0], 0);
+    e1 = min(a.row_ptr_nat[r.p1 - 1] + a.deg[r.p1 - 1], a.e_cap_nat);
+  }
+  const int ne = max(e1 - e0, 0);
+  const bool fits = r.p1 - r.p0 <= kLvlRows && ne <= kLvlEdges;   // (the same for every thread of the workgroup)
+  int code[kLvlPer];
+  if (fits) levels_stage(a, r, e0, ne, code, s_lvl, s_deg, s_cnt);    // (its loads are in flight during the mean)
+  if (a.mean_out) sample_mean_body(a.mean_x, a.lig_off, a.poc_off, a.n_lig, a.mean_out, s_red);
+  if (t < kLevels) { s_rows[t] = 0; s_edges[t] = 0; }
+  if (t < kShellLists) s_shell[t] = 0;
+  if (fits) levels_solve(a, r, ne, code, s_rows, s_edges, s_shell, s_lvl, s_deg, s_cnt);
+  else levels_rows_global(a, r, s_rows, s_edges, s_shell);
   int le = 0;
   for (int i = r.l0 + t; i < r.l1; i += kThreads) le += a.deg[i];
   if (le) atomicAdd(&s_edges[0], le);

@@ -1,5 +1,5 @@
 // Output head of a ligand-output-only call in pocket-conditioning mode, ONE launch instead of three
-// (embedding_out GEMM + decoder MLP + finalize: 21.6 + 12.8 + 4.2 us for 1472 ligand rows, all launch-latency):
+// (embedding_out GEMM + decoder MLP + finalize; times of the one launch: profiles/small_kernels.md):
 //
 //     hout = h W_out + b_out                    egnn_new.py:241   (the time column, dynamics.py:147, is never formed)
 //     eps_h = W1 SiLU(W0 hout[:, :J] + b0) + b1   dynamics.py:152 (atom_decoder)
@@ -34,6 +34,20 @@ __global__ __launch_bounds__(kThreads) void lig_head_kernel(LigHeadArgs p) {
   const int r0 = blockIdx.x * kHeadRows;
   const int nr = min(kHeadRows, p.n_lig - r0);
   const int H = p.H, J = p.J;
+  // W_out^T goes through LDS in chunks of 32 k.  A chunk's loads are all independent (one latency) and are issued one
+  // chunk AHEAD, into registers -- the first together with the rows of h --: they land while the chunk before them is
+  // multiplied, so one round trip is exposed, not one per chunk
+  constexpr int NL = kHeadKC * 128 / kThreads;
+  float wv[NL];
+  auto wload = [&](int k0) {
+#pragma unroll
+    for (int u = 0; u < NL; ++u) {
+      const int i = t + u * kThreads, kk = i >> 7, cc = i & 127;
+      wv[u] = p.WoT[(size_t)(k0 + kk) * p.ldo + (cc < J ? cc : 0)];
+    }
+  };
+  wload(0);
+  const bool w0_lds = J * p.n_hid <= kHeadKC * 128;      // the decoder's W0^T [J][n_hid] fits sW (a larger one stays in L2)
   for (int i = t; i < kHeadRows * H / 4; i += kThreads) {
     const int r = i / (H / 4), k4 = i - r * (H / 4);
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -41,26 +55,24 @@ __global__ __launch_bounds__(kThreads) void lig_head_kernel(LigHeadArgs p) {
     *reinterpret_cast<float4*>(sH + r * H + 4 * k4) = v;
   }
   __syncthreads();
-  // embedding_out: thread (c, half) -> column c of 8 rows; W_out^T goes through LDS in chunks of 32 k (one coalesced
-  // burst per chunk: the loop is a latency chain, not a bandwidth problem)
+  // embedding_out: thread (c, half) -> column c of 8 rows
   {
     const int c = t & 127, rb = (t >> 7) * 8;
     float acc[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] = 0.f;
     for (int k0 = 0; k0 < H; k0 += kHeadKC) {
-      {   // all of a thread's loads first (independent, one latency), then the LDS stores
-        constexpr int NL = kHeadKC * 128 / kThreads;
-        float wv[NL];
+#pragma unroll
+      for (int u = 0; u < NL; ++u) sW[t + u * kThreads] = wv[u];
+      __syncthreads();
+      if (k0 + kHeadKC < H) wload(k0 + kHeadKC);
+      else if (w0_lds) {                   // behind the last chunk: the decoder's first layer, for sW once it is free
 #pragma unroll
         for (int u = 0; u < NL; ++u) {
-          const int i = t + u * kThreads, kk = i >> 7, cc = i & 127;
-          wv[u] = p.WoT[(size_t)(k0 + kk) * p.ldo + (cc < J ? cc : 0)];
+          const int i = t + u * kThreads, kk = i / p.n_hid;
+          wv[u] = i < J * p.n_hid ? p.W0T[(size_t)kk * p.ld0 + (i - kk * p.n_hid)] : 0.f;
         }
-#pragma unroll
-        for (int u = 0; u < NL; ++u) sW[t + u * kThreads] = wv[u];
       }
-      __syncthreads();
 #pragma unroll 2
       for (int k = 0; k < kHeadKC; k += 4) {
         const float w0 = sW[k * 128 + c], w1 = sW[(k + 1) * 128 + c], w2 = sW[(k + 2) * 128 + c], w3 = sW[(k + 3) * 128 + c];
@@ -77,12 +89,20 @@ __global__ __launch_bounds__(kThreads) void lig_head_kernel(LigHeadArgs p) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) sO[(rb + i) * 128 + c] = acc[i] + b;
     }
+    if (w0_lds) {                          // (the loop's last barrier is behind every read of W_out^T in sW)
+#pragma unroll
+      for (int u = 0; u < NL; ++u) sW[t + u * kThreads] = wv[u];
+    }
   }
   __syncthreads();
   for (int idx = t; idx < kHeadRows * p.n_hid; idx += kThreads) {
     const int r = idx / p.n_hid, j = idx - r * p.n_hid;
     float a = 0.f;
-    for (int k = 0; k < J; ++k) a = fmaf(sO[r * 128 + k], p.W0T[(size_t)k * p.ld0 + j], a);
+    if (w0_lds) {
+      for (int k = 0; k < J; ++k) a = fmaf(sO[r * 128 + k], sW[k * p.n_hid + j], a);
+    } else {
+      for (int k = 0; k < J; ++k) a = fmaf(sO[r * 128 + k], p.W0T[(size_t)k * p.ld0 + j], a);
+    }
     sD[r * 64 + j] = silu(a + p.b0[j]);
   }
   __syncthreads();

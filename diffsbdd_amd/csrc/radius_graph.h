@@ -170,11 +170,9 @@ __global__ __launch_bounds__(1024) void scan_kernel(const int* deg, int* row_ptr
                                                     const int* deg_b, int* row_ptr_b, SegAlign seg_b) {
   __shared__ int s_wave[16];
   __shared__ int s_carry;
-  scan_one(deg, row_ptr, n, seg, s_wave, &s_carry);
-  if (deg_b) {                     // second list of the same launch (EdgeList2)
-    __syncthreads();
-    scan_one(deg_b, row_ptr_b, n, seg_b, s_wave, &s_carry);
-  }
+  // the second list of the same launch (EdgeList2) is workgroup 1's: the two scans share nothing (grid = 2 with deg_b)
+  if (blockIdx.x == 0) scan_one(deg, row_ptr, n, seg, s_wave, &s_carry);
+  else if (deg_b) scan_one(deg_b, row_ptr_b, n, seg_b, s_wave, &s_carry);
 }
 
 __device__ void scan_one(const int* deg, int* row_ptr, int n, SegAlign seg, int* s_wave, int* s_carry_p) {

@@ -290,6 +290,12 @@ int dsbdd_engine_buffer(const dsbdd_engine* e, int which, void** ptr_out);
 enum { DSBDD_SHELL_STATS = 0, DSBDD_SHELL_COUNT, DSBDD_SHELL_ROW, DSBDD_SHELL_COL, DSBDD_SHELL_PTR, DSBDD_SHELL_DEG };
 int dsbdd_engine_shell_read(const dsbdd_engine* e, int which, int list, void* dst, int64_t count);
 
+/* Read-out of the second edge list of the last call that had a pocket frame (csrc/radius_graph.h EdgeList2: the edges with
+ * a ligand endpoint): copies `count` int32 to host memory (synchronises the device).  DEG: per node, its edges in that
+ * list; ROW_PTR: [n_nodes + 1] the first slot of a row (32-aligned (sample, node set) segments), then the padded total. */
+enum { DSBDD_LIST2_DEG = 0, DSBDD_LIST2_ROW_PTR };
+int dsbdd_engine_list2_read(const dsbdd_engine* e, int which, void* dst, int64_t count);
+
 /* ---- DDPM reverse-step updates -------------------------------------------
  * ConditionalDDPM.sample_p_zs_given_zt after the dynamics call
  * (conditional_model.py:448-464): in place
