@@ -176,6 +176,11 @@ SIGNATURES = {
     "dsbdd_score_cond_pre": (C.c_int, [_P, C.POINTER(LossCfg), _I32, _I64, _I64, _I64, _I64] + [_P] * 17),
     "dsbdd_score_cond_post": (C.c_int, [_P, C.POINTER(LossCfg), _I32, _I64, _I64, _I64, _I64] + [_P] * 7),
     "dsbdd_score_reduce": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P]),
+    # the same bound under the joint model (csrc/score_joint.h)
+    "dsbdd_score_joint_rows": (C.c_int, [_I32]),
+    "dsbdd_score_joint_pre": (C.c_int, [_P, C.POINTER(LossCfg), _I32, _I64, _I64, _I64, _I64, _I32] + [_P] * 20),
+    "dsbdd_score_joint_post": (C.c_int, [_P, C.POINTER(LossCfg), _I32, _I64, _I64, _I64, _I64] + [_P] * 11),
+    "dsbdd_score_joint_reduce": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P]),
     # the optimiser step and the auxiliary loss of the native training loop (csrc/optim.h, csrc/lj_loss.h)
     "dsbdd_optim_create": (C.c_int, [C.POINTER(OptimCfg), _I32, C.POINTER(_I64), C.POINTER(_P)]),
     "dsbdd_optim_destroy": (None, [_P]),

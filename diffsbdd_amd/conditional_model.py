@@ -445,6 +445,11 @@ class ConditionalDDPM(EnVariationalDiffusion):
         return score.nll_given_pocket(self, ligand, pocket, n_times=n_times, times=times, weights=weights, seed=seed,
                                       ligand_ids=ligand_ids, max_states=max_states, return_terms=return_terms)
 
+    def nll_of_complex(self, ligand, pocket, **kwargs):
+        """The likelihood of the whole complex is defined for the joint model (EnVariationalDiffusion.nll_of_complex)."""
+        raise NotImplementedError(f"{type(self).__name__}: a pocket-conditioned model has no likelihood of the complex; "
+                                  "score its ligands with nll_given_pocket")
+
 
 class SimpleConditionalDDPM(ConditionalDDPM):
     """The same model without the subspace trick (conditional_model.py:702-746):

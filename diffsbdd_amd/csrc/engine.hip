@@ -56,6 +56,7 @@ using namespace dsbdd;
 #include "train_net.h"
 #include "loss_head.h"
 #include "score.h"
+#include "score_joint.h"
 #include "optim.h"
 #include "lj_loss.h"
 #include "train_api.h"

@@ -1,6 +1,6 @@
 // C-ABI entry points of training (included by engine.hip): argument checks around the building blocks (train_blocks.h)
 // and the network walk (train_net.h), then the native training loop around the network call: the loss terms of the
-// pocket-conditioned step (loss_head.h), the likelihood bound of given ligands (score.h), the fused clipping + AdamW step (optim.h), the auxiliary LJ loss (lj_loss.h).
+// pocket-conditioned step (loss_head.h), the likelihood bound of given ligands (score.h, score_joint.h), the fused clipping + AdamW step (optim.h), the auxiliary LJ loss (lj_loss.h).
 #pragma once
 
 static LossCfg loss_cfg_of(const dsbdd_loss_cfg* c) {
@@ -347,6 +347,65 @@ int dsbdd_score_reduce(void* stream, int64_t batch, int32_t n_slots, const float
   if (batch < 1 || n_slots < 2 || batch * n_slots >= (1ll << 31) || !weights || !per_state || !per_ligand || !out)
     return fail(DSBDD_ERR_ARG, "bad argument");
   hipLaunchKernelGGL(score_reduce_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream),
+                     (int)batch, (int)n_slots, weights, per_state, per_ligand, out);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+// ---- the same bound under the joint model: both node sets noised and scored (score_joint.h) ---------------------------------
+int dsbdd_score_joint_rows(int32_t which) { return which == 0 ? SJ_ROWS : which == 1 ? SL_ROWS : which == 2 ? SJO_ROWS : 0; }
+
+int dsbdd_score_joint_pre(void* stream, const dsbdd_loss_cfg* cfg, int32_t n_slots, int64_t first_state, int64_t chunk_states,
+                          int64_t cap_lig, int64_t cap_pocket, int32_t center, const float* lig_x, const float* lig_h,
+                          const int64_t* lig_mask, const float* pocket_x, const float* pocket_h, const int64_t* pocket_mask,
+                          const float* noise_lig, const float* noise_pocket, const float* t_int, const float* gamma_table,
+                          const float* logpn_table, float* eps_lig, float* eps_pocket, float* z_lig, float* z_pocket,
+                          int64_t* mask_lig_out, int64_t* mask_pocket_out, float* t_out, float* per_state, float* per_ligand) {
+  StreamDevice stream_device_(stream);
+  if (!score_chunk_ok(cfg, n_slots, first_state, chunk_states, cap_lig, cap_pocket))
+    return fail(DSBDD_ERR_ARG, "bad configuration or chunk (virtual atoms are not supported; n_slots >= 2; the chunk lies inside "
+                               "the batch * n_slots states)");
+  if (!t_int || !gamma_table || !logpn_table || cfg->n1_tab < 1 || cfg->n2_tab < 1 || !t_out || !per_state || !per_ligand ||
+      (cfg->n_lig > 0 && (!lig_x || !lig_h || !lig_mask || !noise_lig || !eps_lig || !z_lig || !mask_lig_out)) ||
+      (cfg->n_pocket > 0 && (!pocket_x || !pocket_h || !pocket_mask || !noise_pocket || !eps_pocket || !z_pocket ||
+                             !mask_pocket_out)))
+    return fail(DSBDD_ERR_ARG, "null argument");
+  const ScoreChunk ch{n_slots, (int)first_state, cfg->batch * n_slots, (int)cap_lig, (int)cap_pocket};
+  hipLaunchKernelGGL(score_joint_pre_kernel, dim3((unsigned)chunk_states), dim3(kLossThreads), 0, static_cast<hipStream_t>(stream),
+                     loss_cfg_of(cfg), ch, (int)(center != 0), lig_x, lig_h, reinterpret_cast<const long long*>(lig_mask), pocket_x,
+                     pocket_h, reinterpret_cast<const long long*>(pocket_mask), noise_lig, noise_pocket, t_int, gamma_table,
+                     logpn_table, eps_lig, eps_pocket, z_lig, z_pocket, reinterpret_cast<long long*>(mask_lig_out),
+                     reinterpret_cast<long long*>(mask_pocket_out), t_out, per_state, per_ligand);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_score_joint_post(void* stream, const dsbdd_loss_cfg* cfg, int32_t n_slots, int64_t first_state, int64_t chunk_states,
+                           int64_t cap_lig, int64_t cap_pocket, const float* lig_h, const int64_t* lig_mask, const float* pocket_h,
+                           const int64_t* pocket_mask, const float* net_lig, const float* net_pocket, const float* eps_lig,
+                           const float* eps_pocket, const float* z_lig, const float* z_pocket, float* per_state) {
+  StreamDevice stream_device_(stream);
+  if (!score_chunk_ok(cfg, n_slots, first_state, chunk_states, cap_lig, cap_pocket))
+    return fail(DSBDD_ERR_ARG, "bad configuration or chunk (virtual atoms are not supported; n_slots >= 2; the chunk lies inside "
+                               "the batch * n_slots states)");
+  if (!per_state || (cfg->n_lig > 0 && (!lig_h || !lig_mask || !net_lig || !eps_lig || !z_lig)) ||
+      (cfg->n_pocket > 0 && (!pocket_h || !pocket_mask || !net_pocket || !eps_pocket || !z_pocket)))
+    return fail(DSBDD_ERR_ARG, "null argument");
+  const ScoreChunk ch{n_slots, (int)first_state, cfg->batch * n_slots, (int)cap_lig, (int)cap_pocket};
+  hipLaunchKernelGGL(score_joint_post_kernel, dim3((unsigned)chunk_states), dim3(kLossThreads), 0, static_cast<hipStream_t>(stream),
+                     loss_cfg_of(cfg), ch, lig_h, reinterpret_cast<const long long*>(lig_mask), pocket_h,
+                     reinterpret_cast<const long long*>(pocket_mask), net_lig, net_pocket, eps_lig, eps_pocket, z_lig, z_pocket,
+                     per_state);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_score_joint_reduce(void* stream, int64_t batch, int32_t n_slots, const float* weights, const float* per_state,
+                             const float* per_ligand, float* out) {
+  StreamDevice stream_device_(stream);
+  if (batch < 1 || n_slots < 2 || batch * n_slots >= (1ll << 31) || !weights || !per_state || !per_ligand || !out)
+    return fail(DSBDD_ERR_ARG, "bad argument");
+  hipLaunchKernelGGL(score_joint_reduce_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream),
                      (int)batch, (int)n_slots, weights, per_state, per_ligand, out);
   HIP_TRY(hipGetLastError());
   return DSBDD_OK;

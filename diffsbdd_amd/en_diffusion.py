@@ -1131,7 +1131,17 @@ class EnVariationalDiffusion(nn.Module):
     def nll_given_pocket(self, ligand, pocket, **kwargs):
         """Scoring given ligands is defined for the pocket-conditioned models (ConditionalDDPM.nll_given_pocket)."""
         raise NotImplementedError(f"{type(self).__name__}: ligands are scored under pocket-conditioned models only "
-                                  "(the joint model is out of scope)")
+                                  "(the joint model has no likelihood given the pocket: use nll_of_complex)")
+
+    def nll_of_complex(self, ligand, pocket, n_times=None, times=None, weights=None, seed=0, ligand_ids=None, max_states=64,
+                       center=True, return_terms=False):
+        """The model's negative log-likelihood bound of GIVEN ligand-pocket complexes, -log p(ligand, pocket): K time slots
+        and one zero slot per complex, all (complex, time) states evaluated by one network call per chunk of `max_states`
+        states (diffsbdd_amd/score.py has the estimator, the time grid, the noise keying and `center`).
+        -> nll float32 [B]."""
+        from . import score
+        return score.nll_of_complex(self, ligand, pocket, n_times=n_times, times=times, weights=weights, seed=seed,
+                                    ligand_ids=ligand_ids, max_states=max_states, center=center, return_terms=return_terms)
 
     def log_pN(self, N_lig, N_pocket):
         return self.size_distribution.log_prob(N_lig, N_pocket)

@@ -487,13 +487,20 @@ class LigandGenerator:
     # -- scoring given ligands (score.py) ---------------------------------------------------------------------
     @torch.no_grad()
     def score_ligands(self, pdb_file, molecules, pocket_ids=None, ref_ligand=None, n_times=10, seed=0, max_states=64):
-        """The model's negative log-likelihood bound of given molecules in one pocket (`ddpm.nll_given_pocket`; lower =
-        more likely under the model).  `molecules` as for `diversify_ligands`: `Molecule` objects, (xyz, elements) pairs
-        or an SDF path; the pocket is selected as in `generate_ligands`.  `n_times` time slots per molecule on one seeded
-        grid shared by all of them ('all': every diffusion time).  Returns one dict per molecule, in order:
-        {'nll', 'loss_t', 'loss_0', 'kl_prior', 'log_pN', 'n_atoms'}."""
-        if not hasattr(self.ddpm, "diversify"):
-            raise NotImplementedError(f"{type(self.ddpm).__name__}: ligands are scored under pocket-conditioned models only")
+        """The model's negative log-likelihood bound of given molecules in one pocket (lower = more likely under the
+        model): `ddpm.nll_given_pocket` under a pocket-conditioned model, `ddpm.nll_of_complex(center=True)` under a joint
+        one (the bound of the whole complex: for candidates in one pocket it ranks as the conditional bound does).
+        `molecules` as for `diversify_ligands`: `Molecule` objects, (xyz, elements) pairs or an SDF path; the pocket is
+        selected as in `generate_ligands`.  `n_times` time slots per molecule on one seeded grid shared by all of them
+        ('all': every diffusion time).  Returns one dict per molecule, in order:
+        {'nll', 'loss_t', 'loss_0', 'kl_prior', 'log_pN', 'n_atoms'}; a joint model adds 'loss_t_lig', the ligand rows'
+        share of loss_t."""
+        from .conditional_model import ConditionalDDPM
+        from .en_diffusion import EnVariationalDiffusion
+        joint = not isinstance(self.ddpm, ConditionalDDPM)
+        if joint and not isinstance(self.ddpm, EnVariationalDiffusion):
+            raise NotImplementedError(f"{type(self.ddpm).__name__}: ligands are scored under pocket-conditioned models "
+                                      "(nll_given_pocket) and joint models (nll_of_complex) only")
         templates = ligand_io.as_templates(molecules, self.lig_type_encoder)
         n = len(templates)
         if n < 1:
@@ -503,11 +510,17 @@ class LigandGenerator:
         tmpl_x, tmpl_t, tmpl_sizes = ligand_io.upload_templates(templates, self.device)
         ligand, _ = ligand_io.pack_ligands(tmpl_x, tmpl_t, tmpl_sizes, list(range(n)), tmpl_sizes, self.atom_nf)
         grid = dict(times="all") if isinstance(n_times, str) else dict(n_times=n_times)
-        nll, terms = self.ddpm.nll_given_pocket(ligand, pocket, seed=seed, max_states=max_states, return_terms=True, **grid)
-        loss_0 = (terms["loss_0_x"] + terms["loss_0_h"]) + terms["neg_log_constants"]
-        cols = torch.stack([nll, terms["loss_t"], loss_0, terms["kl_prior"], terms["log_pN"]]).cpu().tolist()
-        return [dict(nll=cols[0][i], loss_t=cols[1][i], loss_0=cols[2][i], kl_prior=cols[3][i], log_pN=cols[4][i],
-                     n_atoms=int(tmpl_sizes[i])) for i in range(n)]
+        if joint:
+            nll, terms = self.ddpm.nll_of_complex(ligand, pocket, seed=seed, max_states=max_states, center=True,
+                                                  return_terms=True, **grid)
+            loss_0 = ((terms["loss_0_x_ligand"] + terms["loss_0_x_pocket"]) + terms["loss_0_h"]) + terms["neg_log_constants"]
+        else:
+            nll, terms = self.ddpm.nll_given_pocket(ligand, pocket, seed=seed, max_states=max_states, return_terms=True, **grid)
+            loss_0 = (terms["loss_0_x"] + terms["loss_0_h"]) + terms["neg_log_constants"]
+        names = ["nll", "loss_t", "loss_0", "kl_prior", "log_pN"] + (["loss_t_lig"] if joint else [])
+        cols = torch.stack([nll, terms["loss_t"], loss_0, terms["kl_prior"], terms["log_pN"]]
+                           + ([terms["loss_t_lig"]] if joint else [])).cpu().tolist()
+        return [dict({k: cols[j][i] for j, k in enumerate(names)}, n_atoms=int(tmpl_sizes[i])) for i in range(n)]
 
     def reference_ligand(self, pdb_file, ref_ligand):
         """(xyz, element symbols) of the ligand that defines the pocket: first record of an SDF file, or the group

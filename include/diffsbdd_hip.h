@@ -673,6 +673,44 @@ int dsbdd_score_cond_post(void* stream, const dsbdd_loss_cfg* cfg, int32_t n_slo
 int dsbdd_score_reduce(void* stream, int64_t batch, int32_t n_slots, const float* weights, const float* per_state,
                        const float* per_ligand, float* out);
 
+/* ---- the same bound under the joint model (csrc/score_joint.h; diffsbdd_amd/score.py nll_of_complex) ------------------------
+ * EnVariationalDiffusion.nll_of_complex: the evaluation branch of EnVariationalDiffusion.forward (en_diffusion.py:336-469)
+ * for K integer times per complex.  States, chunks, row offsets, cfg and the refusals are those of the entry points above;
+ * the joint model noises and scores BOTH node sets, so the chunk arrays of both hold noised rows, logpn_table is
+ * log p(n_lig, n_pocket) and the degrees of freedom are 3 (n_lig + n_pocket - 1).  cfg->remove_com is not read.
+ * _joint_rows(which): number of rows of per_state (0), per_ligand (1), out (2).
+ * _joint_pre: noise_lig [cap_lig][3 + atom_nf], noise_pocket [cap_pocket][3 + residue_nf] = standard normal draws in chunk
+ *   layout; their coordinate part is centred here over the state's ligand + pocket rows.  center != 0: the complex's mean of
+ *   the normalised coordinates over ligand + pocket rows is subtracted first (the model's training data is centred that way;
+ *   the reference's forward leaves it to the data set).  Writes eps_* (the centred noise), z_* = alpha_t xh + sigma_t eps,
+ *   both masks (int64, state ids local to the chunk, sorted), t_out [chunk_states] = t / timesteps, per_state
+ *   [_joint_rows(0)][B * n_slots]: rows t, gamma_t, alpha_t, sigma_t, SNR_weight (and, by _joint_post, error_t_lig,
+ *   error_t_pocket, loss_0_x_ligand, loss_0_x_pocket, loss_0_h) in column g, and -- on the state that is a complex's slot 0 --
+ *   per_ligand [_joint_rows(1)][B]: kl_prior, neg_log_constants, delta_log_px, log_pN.
+ * _joint_post: net_* = the network's output for (z_lig, z_pocket, t_out).  Time slots: error_t_* = sum over the node set's
+ *   rows and all its columns of (eps - net)^2; zero slots: loss_0_x_* = 0.5 sum over the coordinates, loss_0_h = - sum over
+ *   both node sets of log p(h | z_0).
+ * _joint_reduce: once per call after every chunk.  out [_joint_rows(2)][B]: nll, loss_t, loss_t_lig, loss_0_x_ligand,
+ *   loss_0_x_pocket, loss_0_h, neg_log_constants, kl_prior, delta_log_px, log_pN with
+ *     loss_t     = sum_k ((-0.5 w[b][k]) SNR_weight) (error_t_lig + error_t_pocket)   (k ascending, float32)
+ *     loss_t_lig = the same sum over error_t_lig alone
+ *     nll = (((loss_t + (((loss_0_x_ligand + loss_0_x_pocket) + loss_0_h) + neg_log_constants)) + kl_prior) - delta_log_px)
+ *           - log_pN.
+ * Every sum is taken in a fixed order; no atomics. */
+int dsbdd_score_joint_rows(int32_t which);
+int dsbdd_score_joint_pre(void* stream, const dsbdd_loss_cfg* cfg, int32_t n_slots, int64_t first_state, int64_t chunk_states,
+                          int64_t cap_lig, int64_t cap_pocket, int32_t center, const float* lig_x, const float* lig_h,
+                          const int64_t* lig_mask, const float* pocket_x, const float* pocket_h, const int64_t* pocket_mask,
+                          const float* noise_lig, const float* noise_pocket, const float* t_int, const float* gamma_table,
+                          const float* logpn_table, float* eps_lig, float* eps_pocket, float* z_lig, float* z_pocket,
+                          int64_t* mask_lig_out, int64_t* mask_pocket_out, float* t_out, float* per_state, float* per_ligand);
+int dsbdd_score_joint_post(void* stream, const dsbdd_loss_cfg* cfg, int32_t n_slots, int64_t first_state, int64_t chunk_states,
+                           int64_t cap_lig, int64_t cap_pocket, const float* lig_h, const int64_t* lig_mask, const float* pocket_h,
+                           const int64_t* pocket_mask, const float* net_lig, const float* net_pocket, const float* eps_lig,
+                           const float* eps_pocket, const float* z_lig, const float* z_pocket, float* per_state);
+int dsbdd_score_joint_reduce(void* stream, int64_t batch, int32_t n_slots, const float* weights, const float* per_state,
+                             const float* per_ligand, float* out);
+
 /* ---- the optimiser step of the native training loop (csrc/optim.h) --------------------------------------------------------
  * One step = configure_gradient_clipping (lightning_modules.py:874-899) + torch.optim.AdamW(amsgrad=True).step() of the
  * reference in two launches and without a device-to-host copy: per-chunk sums of g^2 in a fixed order; then every
