@@ -124,6 +124,8 @@ SIGNATURES = {
                                     C.c_uint32]),
     "dsbdd_node_linear": (C.c_int, [_P, _P, _I32, _I32, _P, _I32, _I32, _P, _I32, _P, _P, _I32,
                                     _P, _I32, _I64, _I32, _I32]),
+    "dsbdd_chain_split_host": (_I64, [_I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I64]),
+    "dsbdd_chain_split_probe": (C.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I64, _P]),
     "dsbdd_build_edges": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, C.POINTER(Config),
                                     _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "dsbdd_bond_orders": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _P, C.c_float, C.c_float,

@@ -1,5 +1,5 @@
 // Thin C-ABI wrappers of the stand-alone kernels (included by engine.hip): DDPM steps (ddpm.h), keyed noise, node GEMM,
-// bond orders (molecule.h), molecule graph statistics and fingerprint distances (mol_metrics.h), ligand packing (ligand_pack.h), the radius graph (radius_graph.h).
+// the node chain's row split (chain_split.h), bond orders (molecule.h), molecule graph statistics and fingerprint distances (mol_metrics.h), ligand packing (ligand_pack.h), the radius graph (radius_graph.h).
 #pragma once
 
 extern "C" {
@@ -159,6 +159,44 @@ int dsbdd_node_linear(void* stream, const float* A1, int32_t lda1, int32_t K1, c
       (reinterpret_cast<uintptr_t>(WT) & 15))
     return fail(DSBDD_ERR_ARG, "bad argument (WT must be 16-byte aligned with ldw % 4 == 0)");
   HIP_TRY(nl(static_cast<hipStream_t>(stream), A1, lda1, K1, A2, lda2, K2, WT, ldw, bias, R, ldr, C, ldc, M, N, act));
+  return DSBDD_OK;
+}
+
+// the argument checks of the two chain-split entry points (H, projections and rows as launch_node_chain takes them)
+static bool chain_split_args_ok(int32_t M, int32_t n_proj, const void* proj_N, const void* proj_first, const void* proj_count,
+                                int32_t H, int32_t grid, const void* header, const void* pieces, int64_t capacity) {
+  return header && capacity >= 0 && (capacity == 0 || pieces) && grid >= 1 && (H == 64 || H == 128 || H == 192 || H == 256) &&
+         n_proj >= 0 && n_proj <= kChainMaxProj && (n_proj == 0 || (proj_N && proj_first && proj_count)) && M <= (8 << 20);
+}
+static const char* const kChainSplitBadArg =
+    "bad argument (null output, grid < 1, H not 64 / 128 / 192 / 256, more than 3 projections or more than 8 M rows)";
+
+int64_t dsbdd_chain_split_host(int32_t M, int32_t do_mlp, int32_t n_proj, const int32_t* proj_N,
+                               const int32_t* proj_first, const int32_t* proj_count, int32_t H, int32_t grid,
+                               uint32_t* header, int32_t* pieces, int64_t capacity) {
+  if (!chain_split_args_ok(M, n_proj, proj_N, proj_first, proj_count, H, grid, header, pieces, capacity))
+    return fail(DSBDD_ERR_ARG, kChainSplitBadArg);
+  ChainSplitIn in{};
+  in.M = M; in.do_mlp = do_mlp; in.n_proj = n_proj; in.H = H; in.grid = grid;
+  for (int q = 0; q < n_proj; ++q) { in.N[q] = proj_N[q]; in.first[q] = proj_first[q]; in.count[q] = proj_count[q]; }
+  const ChainSplit sp(in);
+  sp.report(header);
+  return chain_split_list(sp, grid, grid, ~0u, pieces, capacity);
+}
+
+int dsbdd_chain_split_probe(void* stream, int32_t M, const int32_t* m_count, int32_t do_mlp, int32_t n_proj,
+                            const int32_t* proj_N, const int32_t* proj_first, const int32_t* const* proj_count,
+                            int32_t H, int32_t grid, uint32_t* header, int32_t* pieces, int64_t capacity,
+                            int64_t* n_pieces) {
+  StreamDevice stream_device_(stream);
+  if (!n_pieces || !chain_split_args_ok(M, n_proj, proj_N, proj_first, proj_count, H, grid, header, pieces, capacity))
+    return fail(DSBDD_ERR_ARG, kChainSplitBadArg);
+  NodeChainArgs a{};
+  a.M = M; a.m_count = m_count; a.do_mlp = do_mlp; a.n_proj = n_proj;
+  for (int q = 0; q < n_proj; ++q) { a.proj[q].N = proj_N[q]; a.proj[q].first = proj_first[q]; a.proj[q].count = proj_count[q]; }
+  hipLaunchKernelGGL(chain_split_probe_kernel, dim3(grid), dim3(64), 0, static_cast<hipStream_t>(stream), a, (int)H, header,
+                     pieces, (long long)capacity, reinterpret_cast<long long*>(n_pieces));
+  HIP_TRY(hipGetLastError());
   return DSBDD_OK;
 }
 

@@ -24,6 +24,7 @@
 // Every output element is one fmaf chain over k in ascending 16-k groups, independent of the row split, the number of
 // workgroups and the batch composition (bitwise contract of DESIGN.md §5).
 #pragma once
+#include "chain_split.h"
 #include "common.h"
 
 namespace dsbdd {
@@ -48,9 +49,8 @@ __device__ __forceinline__ void chain_ts(int slot) {
 #endif
 
 constexpr int kChainThreads = 512;     // 8 waves: one workgroup per CU, two waves per SIMD
-constexpr int kChainRowsMax = 96;      // rows a workgroup holds in LDS at a time (6 row tiles)
 constexpr int kChainChunkK = 64;       // k per streamed input chunk of stage 1
-constexpr int kChainMaxProj = 3;
+// (kChainRowsMax = 96 rows a workgroup holds in LDS at a time, kChainMaxProj = 3: chain_split.h)
 
 // Lane-major packed weights for the MFMA A operand: for the 16-column tile ct and the 16-k group g,
 // dst[((ct * (K/16) + g) * 64 + lane) * 4 + s] = WT[16 g + 4 (lane >> 4) + s][16 ct + (lane & 15)]
@@ -125,15 +125,9 @@ __device__ __forceinline__ void chain_kloop(f32x4 (&acc)[RT][CT], XOf&& x_of, co
                                             Hook&& next_chunk) {
   float4 w0[CT], w1[CT], x0[RT], x1[RT];
   auto load = [&](int g, float4 (&wv)[CT], float4 (&xv)[RT]) {
-#ifdef DSBDD_DIAG_CHAIN_NOW
-    if (g == 0)
-#endif
 #pragma unroll
     for (int t = 0; t < CT; ++t) wv[t] = ld4(wp + t * wstride + (size_t)g * 256);
     const float* xs = x_of(g);
-#ifdef DSBDD_DIAG_CHAIN_NOX
-    if (g == 0)
-#endif
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) xv[rt] = *reinterpret_cast<const float4*>(xs + 64 * rt);
   };
@@ -167,20 +161,13 @@ __device__ __forceinline__ void chain_kloop(f32x4 (&acc)[RT][CT], XOf&& x_of, co
 }
 
 // All stages for one range of RT row tiles starting at logical row r0.
-#ifndef DSBDD_CHAIN_WHOLE
-#define DSBDD_CHAIN_WHOLE 1
-#endif
-#ifndef DSBDD_CHAIN_PRE
-#define DSBDD_CHAIN_PRE 1
-#endif
-
 template <int H, int RT>
 __device__ __forceinline__ void chain_range(const NodeChainArgs& p, const int r0, const int M, float* smem,
                                             const int* pcount) {
   constexpr int R16 = 16 * RT;
   constexpr int kLdsFloats = kChainRowsMax * H + 2 * (kChainChunkK / 4) * kChainRowsMax * 4;
   // few rows: the whole [h | agg] input of the range fits behind the panels -> one DMA burst, one barrier, no chunking
-  constexpr bool WHOLE = DSBDD_CHAIN_WHOLE && R16 * 3 * H <= kLdsFloats;
+  constexpr bool WHOLE = R16 * 3 * H <= kLdsFloats;
   float* sPanel = smem;                                // [H / 4][R16][4]
   float* sChunk = smem + R16 * H;                      // WHOLE: [2H / 4][R16][4]; else 2 chunk buffers
   constexpr int CTW = H >= 192 ? 2 : 1;              // 16-column tiles per wave in the H-column stages; H / (16 CTW) waves
@@ -285,7 +272,7 @@ __device__ __forceinline__ void chain_range(const NodeChainArgs& p, const int r0
       auto x_panel = [&](int g) { return xs + (size_t)g * 16 * R16; };
       auto no_hook = [](int) {};
       // residual rows: with few row tiles requested before the K loop and consumed after it (register budget)
-      constexpr bool PRE = DSBDD_CHAIN_PRE && RT <= 4;
+      constexpr bool PRE = RT <= 4;
       float4 hn[RT][CTW];
       auto load_res = [&]() {
 #pragma unroll
@@ -362,199 +349,56 @@ __device__ __forceinline__ void chain_range(const NodeChainArgs& p, const int r0
   CHAIN_TS(7);
 }
 
+// What the split needs from the launch's arguments, device scalars read (node_chain_kernel and the probe share it).
+__device__ __forceinline__ ChainSplitIn chain_split_input(const NodeChainArgs& p, int H, int grid) {
+  ChainSplitIn in{};
+  in.M = p.m_count ? min(p.M, *p.m_count) : p.M;
+  in.do_mlp = p.do_mlp; in.n_proj = p.n_proj; in.H = H; in.grid = grid;
+  if (in.M <= 0) return in;
+#pragma unroll
+  for (int q = 0; q < kChainMaxProj; ++q)
+    if (q < p.n_proj) {
+      in.N[q] = p.proj[q].N; in.first[q] = p.proj[q].first;
+      in.count[q] = p.proj[q].count ? *p.proj[q].count : kChainAllRows;
+    }
+  return in;
+}
+
 template <int H>
 __global__ __launch_bounds__(kChainThreads, 2) void node_chain_kernel(NodeChainArgs p) {
   __shared__ float smem[kChainRowsMax * H + 2 * (kChainChunkK / 4) * kChainRowsMax * 4];
   CHAIN_TS(0);
-  const int M = p.m_count ? min(p.M, *p.m_count) : p.M;
-  if (M <= 0) return;
-  // ---- cost-weighted split of the row list into ranges of 16-row tiles (identical arithmetic in every workgroup) ----
-  // cost of a row, in units of H*H/16 MAC: 48 for the node MLP + N_p / H * 16 for every projection that covers it.
-  // All of it in 32-bit arithmetic on wave-uniform values (rows x 240 units < 2^31: launch_node_chain rejects more than 8 M
-  // rows): round 3's 64-bit version -- bisection of the cumulative cost, 64-bit divisions -- cost every workgroup 7 us
-  // before its first load (in-kernel timeline, profiles/r4h_node_chain_timeline.md).
-  int cnt[kChainMaxProj], fst[kChainMaxProj];
-  unsigned wgt[kChainMaxProj];
-  const unsigned w_mlp = p.do_mlp ? 48u : 0u;
-  int M_work = p.do_mlp ? M : 0;                           // rows behind the last problem's end have no work
-#pragma unroll
-  for (int q = 0; q < kChainMaxProj; ++q) {
-    cnt[q] = 0; wgt[q] = 0; fst[q] = 0;
-    if (q < p.n_proj) {
-      fst[q] = min(M, p.proj[q].first);
-      cnt[q] = p.proj[q].count ? min(M - fst[q], *p.proj[q].count) : M - fst[q];
-      if (cnt[q] < 0) cnt[q] = 0;
-      wgt[q] = (unsigned)(p.proj[q].N * 16 / H);
-      M_work = max(M_work, fst[q] + cnt[q]);
-    }
-  }
-  const int Mw = M_work;
-  if (Mw <= 0) return;
-  CHAIN_NOTE(11, (unsigned long long)(Mw > 0 ? wall_clock64() : 0));     // row counts loaded
-  // cumulative cost of the logical rows [0, r)
-  auto cost_to = [&](int r) {
-    unsigned f = w_mlp * (unsigned)min(r, M_work);
-#pragma unroll
-    for (int q = 0; q < kChainMaxProj; ++q) f += wgt[q] * (unsigned)max(0, min(r - fst[q], cnt[q]));
-    return f;
-  };
-  // F is piecewise linear: its slope only changes where a problem starts or ends (<= 8 breakpoints, sorted here)
-  constexpr int NB = 2 * kChainMaxProj + 3;
-  int bpv[NB];
-  unsigned Fb[NB];
-  {
-    int nb = 0;
-    bpv[nb++] = 0;
-#pragma unroll
-    for (int q = 0; q < kChainMaxProj; ++q) {
-      bpv[nb++] = q < p.n_proj ? min(Mw, fst[q]) : Mw;
-      bpv[nb++] = q < p.n_proj ? min(Mw, fst[q] + cnt[q]) : Mw;
-    }
-    bpv[nb++] = min(Mw, p.do_mlp ? M : Mw);
-    bpv[nb++] = Mw;
-#pragma unroll
-    for (int a2 = 1; a2 < NB; ++a2)                        // insertion sort, fully unrolled (the arrays stay in registers)
-#pragma unroll
-      for (int b2 = NB - 1; b2 > 0; --b2)
-        if (b2 <= a2 && bpv[b2] < bpv[b2 - 1]) { const int tmp = bpv[b2]; bpv[b2] = bpv[b2 - 1]; bpv[b2 - 1] = tmp; }
-#pragma unroll
-    for (int a2 = 0; a2 < NB; ++a2) Fb[a2] = cost_to(bpv[a2]);
-  }
-  const unsigned total = Fb[NB - 1];
-  if (total == 0) return;
-  // the cheapest row of the list = the smallest positive slope of a piece
-  unsigned w_min = ~0u;
-#pragma unroll
-  for (int a2 = 0; a2 < NB - 1; ++a2) {
-    const int len = bpv[a2 + 1] - bpv[a2];
-    if (len > 0 && Fb[a2 + 1] > Fb[a2]) w_min = min(w_min, (Fb[a2 + 1] - Fb[a2]) / (unsigned)len);
-  }
-  if (w_min == ~0u || w_min == 0) w_min = 1;
-  // number of ranges: a multiple of the grid, large enough that a range of the cheapest rows fits kChainRowsMax (the
-  // boundaries are rounded UP to tiles, so a range has floor or ceil of (rows per range / 16) tiles, never more)
-  const unsigned per_max = (unsigned)kChainRowsMax * w_min;
-  unsigned V = (total + per_max - 1) / per_max;
-  V = (V + gridDim.x - 1) / gridDim.x * gridDim.x;
-  // first row (multiple of 16) whose cumulative cost reaches y: F inverted piece by piece, one 32-bit division
-  auto row_at = [&](unsigned y) {
-    if (y == 0) return 0;
-    if (y > total) return (Mw + 15) / 16 * 16;
-    // the piece [b[a], b[a + 1]) with F(b[a]) < y <= F(b[a + 1]): the first a whose end reaches y (F is non-decreasing,
-    // F(b[0]) = 0 < y); pieces of zero length or zero slope can never be it
-    int base = bpv[NB - 2], bnext = bpv[NB - 1];
-    unsigned fbase = Fb[NB - 2], fnext = Fb[NB - 1];
-    bool found = false;
-#pragma unroll
-    for (int a2 = 0; a2 < NB - 1; ++a2)
-      if (!found && Fb[a2 + 1] >= y) { found = true; base = bpv[a2]; bnext = bpv[a2 + 1]; fbase = Fb[a2]; fnext = Fb[a2 + 1]; }
-    const int len = bnext - base;
-    int r = bnext;
-    if (len > 0 && fnext > fbase) {
-      const unsigned slope = (fnext - fbase) / (unsigned)len;   // exact: the cost per row is constant inside a piece
-      r = base + (int)((y - fbase + slope - 1) / slope);
-    }
-    return (r + 15) / 16 * 16;
-  };
-  // Forced cuts (round 4): a range that STRADDLES the end of a projection problem multiplies all its row tiles for a
-  // projection that covers some of them -- it was the slowest workgroup of every launch (171 vs 153 us in the timeline).
-  // The row list is therefore cut at every problem's start (rounded down to a tile) and end (rounded up), and every
-  // segment between two cuts gets its share of the V ranges by cost and splits them with the same inversion of F.
-  // Only for launches of >= 3 row tiles per workgroup: below that the ranges are 1 - 2 tiles, nothing straddles for long, and
-  // the extra arithmetic (1.5 us) is what shows (measured: 19.8 k rows 165.5 -> 153.9 us, 11.5 k 109.6 -> 111.5, 3.6 k 54.9 -> 57.8).
-  constexpr int NC = 2 * kChainMaxProj + 3;
-  const int Tt = (Mw + 15) >> 4;
-  const bool forced = Tt >= 3 * (int)gridDim.x;
-  const unsigned tq = total / V, trem = total % V;         // ceil(total v / V) = tq v + ceil(trem v / V): no 64-bit division
-  auto target = [&](unsigned v) { return tq * v + (trem * v + V - 1) / V; };
-  int cut[NC];
-  unsigned fcut[NC], nrg[NC];                              // F at the cuts; ranges of the segment that starts at cut a
-  unsigned Vs = V;
-  if (forced) {
-  {
-    int nc = 0;
-    cut[nc++] = 0;
-#pragma unroll
-    for (int q = 0; q < kChainMaxProj; ++q) {
-      cut[nc++] = (q < p.n_proj && cnt[q] > 0) ? min(Tt, fst[q] >> 4) : Tt;
-      cut[nc++] = (q < p.n_proj && cnt[q] > 0) ? min(Tt, (fst[q] + cnt[q] + 15) >> 4) : Tt;
-    }
-    cut[nc++] = p.do_mlp ? min(Tt, (M + 15) >> 4) : Tt;
-    cut[nc++] = Tt;
-#pragma unroll
-    for (int a2 = 1; a2 < NC; ++a2)
-#pragma unroll
-      for (int b2 = NC - 1; b2 > 0; --b2)
-        if (b2 <= a2 && cut[b2] < cut[b2 - 1]) { const int tmp = cut[b2]; cut[b2] = cut[b2 - 1]; cut[b2 - 1] = tmp; }
-  }
-#pragma unroll
-  for (int a2 = 0; a2 < NC; ++a2) fcut[a2] = cost_to(min(Mw, cut[a2] << 4));
-  Vs = 0;
-  {
-    int big = 0; unsigned cbig = 0;
-#pragma unroll
-    for (int a2 = 0; a2 < NC - 1; ++a2) {
-      const unsigned c = fcut[a2 + 1] - fcut[a2];
-      const int tiles = cut[a2 + 1] - cut[a2];
-      unsigned n = 0;
-      if (tiles > 0) {
-        n = (unsigned)((float)c * (float)V / (float)total + 0.5f);
-        n = max(n, (unsigned)((tiles + kChainRowsMax / 16 - 1) / (kChainRowsMax / 16)));   // every range fits the LDS panels
-        n = min(max(n, 1u), (unsigned)tiles);
-        if (c > cbig) { cbig = c; big = a2; }
-      }
-      nrg[a2] = n; Vs += n;
-    }
-    nrg[NC - 1] = 0;
-    // the ranges left over (or borrowed) by the rounding go to (come from) the most expensive segment
-#pragma unroll
-    for (int a2 = 0; a2 < NC - 1; ++a2)
-      if (a2 == big && Vs != V) {
-        const int tiles = cut[a2 + 1] - cut[a2];
-        const int lo_n = (tiles + kChainRowsMax / 16 - 1) / (kChainRowsMax / 16);
-        int n = (int)nrg[a2] + (int)V - (int)Vs;
-        n = min(max(n, max(lo_n, 1)), tiles);
-        Vs = Vs - nrg[a2] + (unsigned)n;
-        nrg[a2] = (unsigned)n;
-      }
-  }
-  }  // forced
-  for (unsigned v = blockIdx.x; v < Vs; v += gridDim.x) {
+  const ChainSplitIn in = chain_split_input(p, H, (int)gridDim.x);
+  CHAIN_NOTE(11, (unsigned long long)(in.M > 0 ? wall_clock64() : 0));     // row counts loaded
+  const ChainSplit sp(in);                                 // (identical arithmetic in every workgroup: chain_split.h)
+  // chain_range indexes the clamped counts by a run-time q: a copy of their own, so that the split's tables, which only
+  // unrolled loops index, stay in registers
+  const int cnt[kChainMaxProj] = {sp.cnt[0], sp.cnt[1], sp.cnt[2]};
+  for (unsigned v = blockIdx.x; v < sp.Vs; v += gridDim.x) {
     int r0, r1;
-    if (!forced) {
-      r0 = v == 0 ? 0 : row_at(target(v));
-      r1 = v + 1 == V ? (Mw + 15) / 16 * 16 : row_at(target(v + 1));
-    } else {
-    // segment and position of range v
-    unsigned j = v, ns = 1, f0 = 0, cseg = 0;
-    int b0 = 0, b1 = Tt;
-    bool found = false;
-#pragma unroll
-    for (int a2 = 0; a2 < NC - 1; ++a2) {
-      if (!found && j < nrg[a2]) { found = true; ns = nrg[a2]; f0 = fcut[a2]; cseg = fcut[a2 + 1] - fcut[a2]; b0 = cut[a2]; b1 = cut[a2 + 1]; }
-      if (!found) j -= nrg[a2];
-    }
-    if (!found) break;
-    const unsigned sq = cseg / ns, srem = cseg % ns;       // ceil(cseg j / ns) = sq j + ceil(srem j / ns)
-    auto seg_target = [&](unsigned jj) { return f0 + sq * jj + (srem * jj + ns - 1) / ns; };
-    r0 = j == 0 ? (b0 << 4) : min(max(row_at(seg_target(j)), b0 << 4), b1 << 4);
-    r1 = j + 1 == ns ? (b1 << 4) : min(max(row_at(seg_target(j + 1)), b0 << 4), b1 << 4);
-    }
+    if (!sp.range(v, r0, r1)) break;
     CHAIN_NOTE(12, (unsigned long long)(r1 >= r0 ? wall_clock64() : 0));   // range known
-    int nt = (r1 - r0) / 16;
-    int rs = r0;
-    while (nt > 0) {                                       // (at most one piece unless the rounding overshoots)
-      const int take = nt > kChainRowsMax / 16 ? kChainRowsMax / 16 : nt;
+    chain_pieces(r0, r1, [&](int rs, int take) {
       switch (take) {
-        case 1: chain_range<H, 1>(p, rs, Mw, smem, cnt); break;
-        case 2: chain_range<H, 2>(p, rs, Mw, smem, cnt); break;
-        case 3: chain_range<H, 3>(p, rs, Mw, smem, cnt); break;
-        case 4: chain_range<H, 4>(p, rs, Mw, smem, cnt); break;
-        case 5: chain_range<H, 5>(p, rs, Mw, smem, cnt); break;
-        default: chain_range<H, 6>(p, rs, Mw, smem, cnt); break;
+        case 1: chain_range<H, 1>(p, rs, sp.Mw, smem, cnt); break;
+        case 2: chain_range<H, 2>(p, rs, sp.Mw, smem, cnt); break;
+        case 3: chain_range<H, 3>(p, rs, sp.Mw, smem, cnt); break;
+        case 4: chain_range<H, 4>(p, rs, sp.Mw, smem, cnt); break;
+        case 5: chain_range<H, 5>(p, rs, sp.Mw, smem, cnt); break;
+        default: chain_range<H, 6>(p, rs, sp.Mw, smem, cnt); break;
       }
-      rs += 16 * take; nt -= take;
-    }
+    });
   }
+}
+
+// The split as the DEVICE computes it, for the tests (dsbdd_chain_split_probe): one thread per workgroup goes through
+// node_chain_kernel's lines up to chain_range and writes its pieces where the host's list has them, the last one the header.
+__global__ void chain_split_probe_kernel(NodeChainArgs p, int H, unsigned* header, int* pieces, long long capacity,
+                                         long long* n_pieces) {
+  if (threadIdx.x != 0) return;
+  const ChainSplit sp(chain_split_input(p, H, (int)gridDim.x));
+  const long long n = chain_split_list(sp, gridDim.x, blockIdx.x + 1, blockIdx.x, pieces, capacity);
+  if (blockIdx.x == gridDim.x - 1) { sp.report(header); *n_pieces = n; }
 }
 
 inline hipError_t launch_node_chain(hipStream_t s, const NodeChainArgs& a, int H, int n_cu) {

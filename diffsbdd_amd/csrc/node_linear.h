@@ -184,13 +184,11 @@ struct NodeGroupArgs { NodeLinearArgs p[kMaxGroup]; };
 // 64 / 64: 34.83, 32 / 32: 35.10, 16 / 32: 35.21, 128 / 64: 32.7 -- short steps (16 MFMAs per wave between
 // barriers, 8 KB of LDS per workgroup) beat long ones here: the launches are a few tiles per CU, so what counts is
 // how soon a workgroup's first MFMA issues and how many workgroups a CU holds, not the barrier count.
-#ifndef DSBDD_NODE_BK2
-#define DSBDD_NODE_BK2 16        // 64-column tile
-#endif
-#ifndef DSBDD_NODE_BK1
-#define DSBDD_NODE_BK1 32        // 32-column (half) tile
-#endif
-constexpr int node_bk(int ct) { return ct == 1 ? DSBDD_NODE_BK1 : (ct == 2 ? DSBDD_NODE_BK2 : 128 / ct); }
+constexpr int node_bk(int ct) {
+  constexpr int kBk1 = 32;       // 32-column (half) tile
+  constexpr int kBk2 = 16;       // 64-column tile
+  return ct == 1 ? kBk1 : (ct == 2 ? kBk2 : 128 / ct);
+}
 
 // One 128-row x (32*CT)-column output tile, computed by the calling workgroup.
 template <int CT>
@@ -204,9 +202,6 @@ __device__ __forceinline__ void node_gemm_tile(const NodeLinearArgs& p, const in
   const int K = p.K1 + p.K2;
 
   auto streamB = [&](int ks, int buf) {
-#ifdef DSBDD_DIAG_NODE_NODMA
-    return;   // DIAGNOSTIC ONLY (wrong results): the weight slices are never streamed
-#endif
 #pragma unroll
     for (int i = 0; i < BI; ++i) {
       const int f = t + kThreads * i;                // float4 index: row f/RQ, column chunk f%RQ
@@ -224,14 +219,8 @@ __device__ __forceinline__ void node_gemm_tile(const NodeLinearArgs& p, const in
   auto loadA = [&](int ks, float4 (&dst)[NG]) {
     const int k0 = ks * BK;                          // a K step never straddles A1 | A2
     const float* src = k0 < p.K1 ? a1 + k0 : a2 + (k0 - p.K1);
-#ifdef DSBDD_DIAG_NODE_NOA
-#pragma unroll
-    for (int g = 0; g < NG; ++g) dst[g] = make_float4(0.1f, 0.2f, 0.3f, (float)ks);   // DIAGNOSTIC ONLY (wrong results)
-    (void)src;
-#else
 #pragma unroll
     for (int g = 0; g < NG; ++g) dst[g] = ld4(src + 8 * g);
-#endif
   };
 
   f32x16 acc[CT];
@@ -268,11 +257,7 @@ __device__ __forceinline__ void node_gemm_tile(const NodeLinearArgs& p, const in
     }
 #pragma unroll
     for (int g = 0; g < NG; ++g) cur[g] = nxt[g];
-#ifdef DSBDD_DIAG_NODE_NOBARRIER
-    __builtin_amdgcn_s_waitcnt(0x0f70);   // DIAGNOSTIC ONLY (racy): vmcnt(0) without the workgroup barrier
-#else
     __syncthreads();
-#endif
   }
 
   // epilogue.  C may alias R (the node MLP's residual is updated in place), so the compiler

@@ -416,6 +416,27 @@ int dsbdd_node_linear(void* stream, const float* A1, int32_t lda1, int32_t K1, c
                       const float* R, int32_t ldr, float* C, int32_t ldc, int64_t M, int32_t N,
                       int32_t act);
 
+/* The row split of the node-chain kernel (csrc/chain_split.h) as compiled, for every workgroup of a launch
+ * of `grid` workgroups: which 16-row tiles each one runs, in order.  Host only -- no GPU is touched, it works where the
+ * library loads without one.  M: logical rows (what the kernel has after min(M, *m_count)); projection q of n_proj <= 3
+ * has proj_N[q] columns and covers proj_count[q] rows from row proj_first[q] (count 0x7fffffff: all that follow; both are
+ * clamped to M inside).  header: uint32[5] = (Mw rows with work, total cost, V ranges planned, Vs ranges dealt out, forced
+ * cuts 0 / 1), all zero when nothing is dealt out; pieces: int32 [capacity][3] = (workgroup, first row, tiles <= 6),
+ * workgroup by workgroup.  Returns the number of pieces there are (capacity 0: only counts), or DSBDD_ERR_ARG. */
+int64_t dsbdd_chain_split_host(int32_t M, int32_t do_mlp, int32_t n_proj, const int32_t* proj_N,
+                               const int32_t* proj_first, const int32_t* proj_count, int32_t H, int32_t grid,
+                               uint32_t* header, int32_t* pieces, int64_t capacity);
+
+/* The same split as the DEVICE computes it: one small launch of `grid` workgroups that read the device scalars through the
+ * kernel's own lines (m_count: device int32 or NULL; proj_count: host array of n_proj device int32 pointers, NULL entry =
+ * all rows that follow) and write header, pieces (layout as above, device memory) and n_pieces (device int64: the pieces
+ * there are, of which the first `capacity` are written).  Same argument checks as the kernel's launcher: H in {64, 128,
+ * 192, 256}, at most 3 projections, M <= 8 << 20. */
+int dsbdd_chain_split_probe(void* stream, int32_t M, const int32_t* m_count, int32_t do_mlp, int32_t n_proj,
+                            const int32_t* proj_N, const int32_t* proj_first, const int32_t* const* proj_count,
+                            int32_t H, int32_t grid, uint32_t* header, int32_t* pieces, int64_t capacity,
+                            int64_t* n_pieces);
+
 /* Radius graph (dynamics.py:169-187) -> edge list sorted by (row, col).
  * x [n_lig+n_pocket][3]; scratch: node_batch [N], lig_off/poc_off [batch+1],
  * deg [N], row_ptr [N+1] (row_ptr[N] = number of edges). */

@@ -19,6 +19,7 @@ from diffsbdd_amd.conditional_model import ConditionalDDPM, SimpleConditionalDDP
 from oracle import ddpm_oracle as do
 from oracle import egnn_oracle as eo
 from oracle import weights as W
+from tests import _chain_split_cases as cs
 from tests import _emulate as em
 from tests._golden import Case, DYN_CASES, GOLDEN_DIR
 
@@ -437,10 +438,11 @@ def test_stage_plan_model():
 
 
 def test_node_chain_row_split_covers_every_tile_once_and_balances_cost():
-    """Host model of the row split of csrc/node_chain.h (tests/_emulate.node_chain_ranges mirrors the device code):
+    """The row split of csrc/chain_split.h as compiled (dsbdd_chain_split_host runs the kernel's own text on the host):
     for the benchmark's stages and for random problems every 16-row tile of the work range belongs to exactly one piece,
     no piece exceeds 96 rows, and no workgroup carries more than the mean cost plus one tile of the most expensive rows
     (which is what makes 19.8 k rows a single round on 256 CUs)."""
+    lib = _lib.load()
     rng = np.random.RandomState(0)
     cases = [(19776, 256, True, [(512, 3639, 0), (512, 1472, 0), (512, None, 0)]),        # all rows, full chain
              (18764 + 286, 256, True, [(512, 3639, 286), (512, 1472, 286), (512, None, 0)]),  # ghost rows in front
@@ -453,11 +455,14 @@ def test_node_chain_row_split_covers_every_tile_once_and_balances_cost():
                   int(rng.choice([0, 0, rng.randint(0, M + 1)]))) for _ in range(rng.randint(0, 4))]
         cases.append((M, int(rng.choice([8, 104, 256, 304])), bool(rng.rand() < 0.7) or not projs, projs))
     for M, grid, do_mlp, projs in cases:
-        pieces, (Mw, total, V) = em.node_chain_ranges(M, grid, do_mlp, projs)
+        flat, (Mw, total, V, Vs, forced) = cs.host_split(lib, M, grid, do_mlp, projs)
+        pieces = cs.per_workgroup(flat, grid)
         if Mw == 0 or total == 0:
             assert all(not p for p in pieces)
             continue
         n_tiles = (Mw + 15) // 16
+        assert forced == (n_tiles >= 3 * grid)
+        assert forced or Vs == V
         seen = np.zeros(n_tiles, dtype=int)
         for wg in pieces:
             for r0, take in wg:
@@ -479,8 +484,33 @@ def test_node_chain_row_split_covers_every_tile_once_and_balances_cost():
             # V / grid ranges per workgroup, each at most total / V plus one tile of the most expensive rows
             assert max(loads) <= total / grid + (V // grid) * 16 * w_max + 1e-9
     # the headline stage: one range per CU, 5 or 6 tiles each
-    pieces, (_, _, V) = em.node_chain_ranges(19776, 256, True, [(512, 3639, 0), (512, 1472, 0), (512, None, 0)])
+    flat, (_, _, V, _, _) = cs.host_split(lib, 19776, 256, True, [(512, 3639, 0), (512, 1472, 0), (512, None, 0)])
+    pieces = cs.per_workgroup(flat, 256)
     assert V == 256 and all(len(p) == 1 for p in pieces) and {t for p in pieces for _, t in p} <= {1, 2, 3, 4, 5, 6}
+
+
+def test_chain_split_reproduces_the_parent_commits_ranges():
+    """tests/golden/chain_split_parent.npz holds what the split computed before it moved into csrc/chain_split.h (recorded
+    from that commit's kernel text on a CPU, tests/golden/make_golden_chain_split.py): header and every (workgroup, first
+    row, tiles) piece of the existing test's cases, 300 small random ones and the edge list of the GPU test at H = 256 and
+    128, and five launches of 0.6 M - 8 M rows as header + digest.  The compiled code reproduces all of it exactly."""
+    lib = _lib.load()
+    z = np.load(cs.GOLDEN)
+    rows = [cs.case_row(*c, H) for H in cs.HS for c in cs.listed_cases()]
+    assert z["cases"].tolist() == rows and len(rows) == 2 * (348 + len(cs.EDGE))
+    n_forced = 0
+    for i, (c, H) in enumerate((c, H) for H in cs.HS for c in cs.listed_cases()):
+        flat, header = cs.host_split(lib, *c, H=H)
+        assert header == tuple(z["header"][i]), (c, H)
+        assert np.array_equal(flat, z["pieces"][z["piece_off"][i]:z["piece_off"][i + 1]]), (c, H)
+        n_forced += header[4]
+    assert n_forced > len(rows) // 2                  # most of the cases take the forced path
+    large = [(c, H) for H in cs.HS for c in cs.LARGE]
+    assert z["large_cases"].tolist() == [cs.case_row(*c, H) for c, H in large]
+    for i, (c, H) in enumerate(large):
+        flat, header = cs.host_split(lib, *c, H=H)
+        assert header == tuple(z["large_header"][i]) and len(flat) == z["large_pieces"][i]
+        assert cs.digest(flat) == str(z["large_digest"][i]), (c, H)
 
 
 def test_edge_tile_walk_covers_both_lists_once_and_slice_staging_covers_a_slice_once():
