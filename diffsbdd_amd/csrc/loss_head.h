@@ -14,7 +14,9 @@
 //
 // Every per-sample sum is a fixed-order reduction inside the sample's workgroup (torch: index_add_ with atomics).
 // Formulas and their order follow the torch mirror line by line (cited below by the mirror's method names, which cite the
-// reference); tests/test_gpu_train.py compares all twelve terms and the parameter gradients between the two paths.
+// reference); tests/test_gpu_train.py compares all twelve terms and the parameter gradients between the two paths, and
+// tests/test_gpu_loss_head_kernels.py drives each of the six kernels alone through the C ABI against a float64 restatement
+// of the header's contract (tests/_loss64.py, pinned to the oracle by tests/test_loss_restatement.py).
 //
 // The joint model (EnVariationalDiffusion.forward, diffsbdd_amd/en_diffusion.py) has the same three launches further down:
 // loss_joint_pre_kernel / loss_joint_post_kernel / loss_joint_post_bwd_kernel (tests/test_gpu_joint_loss_head.py).

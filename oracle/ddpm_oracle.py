@@ -218,7 +218,8 @@ def normalize(m, ligand=None, pocket=None):
             return None
         d = dict(d)
         d["x"] = d["x"] / m.norm_values[0]
-        d["one_hot"] = (d["one_hot"].float() - m.norm_biases[1]) / m.norm_values[1]
+        oh = d["one_hot"] if d["one_hot"].is_floating_point() else d["one_hot"].float()   # (a float64 batch stays float64)
+        d["one_hot"] = (oh - m.norm_biases[1]) / m.norm_values[1]
         return d
     return nz(ligand), nz(pocket)
 
