@@ -39,6 +39,7 @@
 #include "ligand_pack.h"
 #include "molecule.h"
 #include "mol_metrics.h"
+#include "pose_check.h"
 #include "node_chain.h"
 #include "node_linear.h"
 #include "train.h"

@@ -196,15 +196,20 @@ class LigandGenerator:
     @torch.no_grad()
     def generate_ligands(self, pdb_file, n_samples, pocket_ids=None, ref_ligand=None, num_nodes_lig=None,
                          sanitize=False, largest_frag=False, relax_iter=0, timesteps=None,
-                         n_nodes_bias=0, n_nodes_min=0, **kwargs):
+                         n_nodes_bias=0, n_nodes_min=0, pose=None, **kwargs):
+        """`pose=True` (or a dict of `tol` / `contact`) checks every sample against the heavy atoms of the selected
+        residues on the device (pose.py) and attaches the record as `m.pose`."""
         if sanitize or relax_iter:
             raise NotImplementedError(self._RDKIT_REFUSAL)
+        pose = self._pose_options(pose)
         residues = self.select_pocket_residues(pdb_file, pocket_ids, ref_ligand)
         pocket = self.prepare_pocket(residues, repeats=n_samples)
         xh_lig, lig_mask = self.sample_for_pocket(pocket, n_samples, num_nodes_lig, timesteps,
                                                   n_nodes_bias, n_nodes_min, **kwargs)
         x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
-        return build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=n_samples)
+        stats = None if pose is None else self._pose_stats(x, atom_type, lig_mask, [residues], [n_samples], pose)
+        return build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=n_samples,
+                               pose=stats)
 
     def _drop_virtual(self, xh_lig, lig_mask):
         """(x, atom_type, lig_mask) of the generated atoms; with virtual nodes the atoms of the virtual class are
@@ -215,6 +220,64 @@ class LigandGenerator:
             keep = atom_type != self.virtual_atom
             x, atom_type, lig_mask = x[keep], atom_type[keep], lig_mask[keep]
         return x, atom_type, lig_mask
+
+    # -- pose checks of the sampled batch (pose.py): only with the samplers' `pose=` option ------------------------------
+    @staticmethod
+    def _pose_options(pose):
+        """The samplers' `pose` keyword: None / False = off (nothing runs); True = the module's defaults; a dict with
+        'tol' / 'contact' (and 'residues' where the sampler is not given any: `diversify_ligands`)."""
+        if pose is None or pose is False:
+            return None
+        from . import pose as pose_mod
+        opts = {} if pose is True else dict(pose)
+        unknown = set(opts) - {"tol", "contact", "residues"}
+        if unknown:
+            raise ValueError(f"pose: unknown option(s) {sorted(unknown)}")
+        opts.setdefault("tol", pose_mod.CLASH_TOLERANCE)
+        opts.setdefault("contact", pose_mod.CONTACT_CUTOFF)
+        return opts
+
+    def _pose_pocket(self, residues):
+        """Heavy atoms of a job's residues as a one-group `pose.PocketAtoms` on the device: uploaded once per residue
+        list (a test-set job hands the same list to every one of its batches) and kept while the list lives here."""
+        from . import pose as pose_mod
+        cache = self.__dict__.setdefault("_pose_pockets", {})
+        hit = cache.get(id(residues))
+        if hit is None or hit[0] is not residues:
+            while len(cache) >= 256:
+                cache.pop(next(iter(cache)))
+            hit = (residues, pose_mod.PocketAtoms.upload([pose_mod.pocket_atoms(residues)], self.device))
+            cache[id(residues)] = hit
+        return hit[1]
+
+    def _pose_stats(self, x, atom_type, lig_mask, residue_sets, counts, opts):
+        """`pose.pose_check` of a sampled batch (after `_drop_virtual`): one group per job, `counts[k]` samples on group k."""
+        from . import pose as pose_mod
+        if "_pose_radii" not in self.__dict__:
+            self._pose_radii = torch.as_tensor(pose_mod.radius_table(self.lig_type_decoder), device=self.device)
+        pockets = pose_mod.PocketAtoms.concat([self._pose_pocket(r) for r in residue_sets])
+        groups = np.repeat(np.arange(len(counts)), counts)
+        return pose_mod.pose_check(x, self._pose_radii[atom_type], lig_mask, pockets, groups, batch=int(sum(counts)),
+                                   tol=opts["tol"], contact=opts["contact"])
+
+    @torch.no_grad()
+    def check_poses(self, pdb_file, molecules, pocket_ids=None, ref_ligand=None, scope="protein", tol=None, contact=None):
+        """Clash and contact counts of given molecules against the protein of `pdb_file` (pose.py; one launch).
+        `molecules` as for `score_ligands`: `Molecule` objects, (xyz, elements) pairs or an SDF path.  scope 'protein':
+        every ATOM residue of the file; 'pocket': the selection of `generate_ligands` (`pocket_ids` or `ref_ligand`).
+        Returns one dict per molecule, in order: {'n_atoms', 'clash_pairs', 'clash_atoms', 'contact_pairs',
+        'contact_atoms', 'nonfinite', 'min_distance'} over heavy atoms."""
+        from . import pose as pose_mod
+        if scope == "pocket":
+            residues = self.select_pocket_residues(pdb_file, pocket_ids, ref_ligand)
+        elif scope == "protein":
+            residues = pocket_io.read_pdb_residues(pdb_file)
+        else:
+            raise ValueError("scope must be 'protein' or 'pocket'")
+        pockets = pose_mod.PocketAtoms.upload([pose_mod.pocket_atoms(residues)], self.device)
+        records = pose_mod.check_molecules(molecules, pockets, tol=pose_mod.CLASH_TOLERANCE if tol is None else tol,
+                                           contact=pose_mod.CONTACT_CUTOFF if contact is None else contact)
+        return [r.as_dict() for r in records]
 
     def _ligand_sizes(self, num_nodes_lig, n_nodes_bias=0, n_nodes_min=0):
         """Bias and minimum of generate_ligands (lightning_modules.py:806-811).  With virtual nodes every ligand already
@@ -262,7 +325,7 @@ class LigandGenerator:
     # -- several different pockets in one batch ---------------------------
     @torch.no_grad()
     def generate_for_pockets(self, jobs, timesteps=None, largest_frag=False, n_nodes_bias=0,
-                             n_nodes_min=0, seed=None, sample_ids=None, **kwargs):
+                             n_nodes_min=0, seed=None, sample_ids=None, pose=None, **kwargs):
         """One sampling batch over several different pockets.
 
         The reference's test driver (test.py:59-176) samples one pocket at a time; the
@@ -271,7 +334,10 @@ class LigandGenerator:
         samples than fit.  `jobs`: list of (residues, n_samples, num_nodes_lig or None).
         Returns one list of molecules per job.  With keyed noise (`seed`, and `sample_ids` = one
         global id per slot of the packed batch) a sample is the same molecule in any packing that
-        gives it the same global id."""
+        gives it the same global id.
+        `pose=True` (or a dict of `tol` / `contact`): one more launch checks every sample against the heavy atoms of its
+        job's residues before the molecules are built; every molecule carries the record as `m.pose`."""
+        pose = self._pose_options(pose)
         parts, sizes, counts = [], [], []
         base = 0
         for residues, n, n_lig in jobs:
@@ -292,7 +358,8 @@ class LigandGenerator:
         xh_lig, lig_mask = self.sample_for_pocket(pocket, base, torch.cat(sizes), timesteps,
                                                   n_nodes_bias, n_nodes_min, **kwargs)
         x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
-        mols = build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=base)
+        stats = None if pose is None else self._pose_stats(x, atom_type, lig_mask, [j[0] for j in jobs], counts, pose)
+        mols = build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=base, pose=stats)
         out, o = [], 0
         for n in counts:
             out.append(mols[o:o + n])
@@ -397,7 +464,7 @@ class LigandGenerator:
 
     @torch.no_grad()
     def inpaint_for_pockets(self, jobs, timesteps=None, resamplings=1, center="ligand", largest_frag=False,
-                            seed=None, sample_ids=None, jump_length=1, cone_mode=2):
+                            seed=None, sample_ids=None, jump_length=1, cone_mode=2, pose=None):
         """Several design jobs in one batch: the packed-batch twin of `generate_for_pockets`.  `jobs`: list of
         (residues, n_samples, substructure, add_n_nodes or sizes) -- `substructure` a `Molecule` or an (xyz, elements)
         pair, the last entry None (sizes drawn), an int (atoms to add) or one ligand size per sample.  Returns one list
@@ -406,8 +473,10 @@ class LigandGenerator:
         id.  For that the engine's per-batch choices must not follow the packing either: the forward cone, which the
         model otherwise switches by the number of distinct pockets in the batch (en_diffusion.cone_mode; on and off
         differ in rounding), is pinned to `cone_mode` (2 = on, 0 = off; None = the model's own per-batch rule) and the
-        automatic 16-row granule is switched off for the call, as the test-set driver does (testset.make_hip_sampler)."""
+        automatic 16-row granule is switched off for the call, as the test-set driver does (testset.make_hip_sampler).
+        `pose`: as for `generate_for_pockets`."""
         self._check_inpaint_model(center)
+        pose = self._pose_options(pose)
         if cone_mode not in (None, 0, 2):
             raise ValueError("cone_mode must be 2, 0 or None")
         parts, templates, slot_tmpl, sizes, counts = [], [], [], [], []
@@ -444,7 +513,8 @@ class LigandGenerator:
         finally:
             self.ddpm.cone_mode, self.ddpm.edge_granule16 = saved
         x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
-        mols = build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=base)
+        stats = None if pose is None else self._pose_stats(x, atom_type, lig_mask, [j[0] for j in jobs], counts, pose)
+        mols = build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=base, pose=stats)
         out, o = [], 0
         for n in counts:
             out.append(mols[o:o + n])
@@ -465,13 +535,18 @@ class LigandGenerator:
         return out_lig, lig_mask
 
     @torch.no_grad()
-    def diversify_ligands(self, pocket, molecules, noising_steps, largest_frag=False, seed=None):
+    def diversify_ligands(self, pocket, molecules, noising_steps, largest_frag=False, seed=None, pose=None):
         """Partially noise and denoise ligands in their pocket: the reference's `diversify_ligands`
         (optimize.py:92-147).  `pocket`: the dict of `prepare_pocket(residues, repeats=len(molecules))`; `molecules`:
         a list of `Molecule` objects or (xyz, elements) pairs, or an SDF path -- one ligand per pocket replica.
-        Returns one molecule per input, in order."""
+        Returns one molecule per input, in order.  `pose`: a dict with `residues` (the residues `pocket` was prepared from:
+        the pocket dict holds the model's nodes, not the protein's atoms) and optionally `tol` / `contact` attaches the pose
+        record of every result as `m.pose`."""
         if not hasattr(self.ddpm, "diversify"):
             raise NotImplementedError(f"{type(self.ddpm).__name__} has no diversify (pocket-conditioned models only)")
+        pose = self._pose_options(pose)
+        if pose is not None and pose.get("residues") is None:
+            raise ValueError("diversify_ligands: pose needs the residues the pocket was prepared from (pose=dict(residues=...))")
         templates = ligand_io.as_templates(molecules, self.lig_type_encoder)
         n = len(pocket["size"])
         if len(templates) != n:
@@ -482,7 +557,8 @@ class LigandGenerator:
             self.ddpm.seed(seed)
         xh_lig, lig_mask = self._diversify_chain(pocket, ligand, noising_steps)
         x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
-        return build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=n)
+        stats = None if pose is None else self._pose_stats(x, atom_type, lig_mask, [pose["residues"]], [n], pose)
+        return build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=n, pose=stats)
 
     # -- scoring given ligands (score.py) ---------------------------------------------------------------------
     @torch.no_grad()
@@ -658,9 +734,12 @@ def main(argv=None):
                     help="allow a full unpickle of the checkpoint file")
     ap.add_argument("--metrics", action="store_true",
                     help="write metrics.json next to the output (metrics.MoleculeSetMetrics of the written molecules)")
+    ap.add_argument("--pose", action="store_true",
+                    help="check every sample against the pocket's heavy atoms (pose.py): records to stderr and <outfile>.pose.csv")
     a = ap.parse_args(argv)
     bs = a.batch_size or a.n_samples
     assert a.n_samples % bs == 0
+    extra = dict(pose=True) if a.pose else {}
     gen = LigandGenerator.from_checkpoint(a.checkpoint, device="cuda", trusted=a.trusted_checkpoint)
     molecules = []
     for i in range(a.n_samples // bs):
@@ -669,8 +748,15 @@ def main(argv=None):
         molecules += gen.generate_ligands(
             a.pdbfile, bs, a.resi_list, a.ref_ligand, n_lig, a.sanitize, largest_frag=not a.all_frags,
             relax_iter=(200 if a.relax else 0), resamplings=a.resamplings, jump_length=a.jump_length,
-            timesteps=a.timesteps)
+            timesteps=a.timesteps, **extra)
     write_sdf(a.outfile, molecules)
+    if a.pose:
+        from . import pose as pose_mod
+        print("[generate] " + pose_mod.POSE_COVERAGE, file=sys.stderr)
+        rows = [(os.path.basename(a.outfile), k, m.pose) for k, m in enumerate(molecules)]
+        for _, k, rec in rows:
+            print(f"[generate] pose mol_{k}: {rec.as_dict()}", file=sys.stderr)
+        pose_mod.write_csv(a.outfile + ".pose.csv", rows)
     from .molecules import PROCESS_MOLECULE_COVERAGE
     print("[generate] " + PROCESS_MOLECULE_COVERAGE, file=sys.stderr)
     print(f"wrote {len(molecules)} molecules to {a.outfile}")

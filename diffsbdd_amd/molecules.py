@@ -63,6 +63,8 @@ class Molecule:
                  if i in new_index and j in new_index]
         m = Molecule(self.positions[keep], [self.symbols[a] for a in keep], bonds)
         m.n_generated_atoms = self.num_atoms          # size of the sample the fragment was cut from
+        if hasattr(self, "pose"):                     # pose record (pose.MolPose): the kept atoms' rows, totals recomputed
+            m.pose = self.pose.subset(keep)
         return m
 
     def valences(self):
@@ -169,13 +171,15 @@ def bond_orders(x, atom_type, lig_mask, info, n_max=None, batch=None):
     return out, sizes
 
 
-def build_molecules(x, atom_type, lig_mask, info, largest_frag=False, batch=None):
+def build_molecules(x, atom_type, lig_mask, info, largest_frag=False, batch=None, pose=None):
     """Batch version of `build_molecule(..., use_openbabel=False)` +
     `process_molecule(largest_frag=...)` (molecule_builder.py:140-160, 162-214):
-    list of `Molecule`, one per sample, in sample order."""
+    list of `Molecule`, one per sample, in sample order.  `pose`: the `pose.PoseStats` of the same batch; every
+    molecule then carries its record as `m.pose` (a fragment: the record of its atoms)."""
     if isinstance(info, str):
         info = dataset_info(info)
     orders, sizes = bond_orders(x, atom_type, lig_mask, info, batch=batch)
+    poses = None if pose is None else pose.molecules()
     orders = orders.cpu().numpy()
     sizes = sizes.cpu().numpy()
     xs = x.detach().float().cpu().numpy()
@@ -187,6 +191,8 @@ def build_molecules(x, atom_type, lig_mask, info, largest_frag=False, batch=None
         ii, jj = np.nonzero(orders[b, :n, :n])
         bonds = [(int(i), int(j), int(orders[b, i, j])) for i, j in zip(ii, jj)]
         m = Molecule(xs[o:o + n].copy(), [dec[int(t)] for t in ts[o:o + n]], bonds)
+        if poses is not None:
+            m.pose = poses[b]
         mols.append(m.largest_fragment() if largest_frag else m)
         o += n
     return mols

@@ -219,15 +219,28 @@ def cone_mode_for_jobs(jobs: List[PocketJob]) -> int:
     return 2 if n >= 5 * max(len(jobs), 1) else 0
 
 
-def make_hip_sampler(gen, timesteps=None, seed=0, largest_frag=True, n_nodes_bias=0, n_nodes_min=0, cone_mode=2, **kwargs):
+def all_of(*filters):
+    """Conjunction of acceptance filters (None entries are skipped); None when there is none."""
+    filters = [f for f in filters if f is not None]
+    if not filters:
+        return None
+    return filters[0] if len(filters) == 1 else (lambda m: all(f(m) for f in filters))
+
+
+def make_hip_sampler(gen, timesteps=None, seed=0, largest_frag=True, n_nodes_bias=0, n_nodes_min=0, cone_mode=2, pose=None,
+                     **kwargs):
     """`sample_batch` for TestSetDriver on a `generate.LigandGenerator`: one packed sampling batch on
     the GPU (LigandGenerator.generate_for_pockets).  Global sample id of slot k of a job's r-th round =
     index * 2^20 + (samples generated for the job so far) + k: independent of the packing.
     cone_mode: the engine's forward cone for EVERY batch of the run (2 = on, the default; 0 = off;
-    `cone_mode_for_jobs(all jobs)` picks by the requested samples per pocket)."""
+    `cone_mode_for_jobs(all jobs)` picks by the requested samples per pocket).
+    pose: the pose hook of `generate_for_pockets` (True or a dict of tol / contact): molecules then carry `m.pose`, which
+    `pose.pose_filter` reads.  A named parameter: the other keywords end in `sample_for_pocket`."""
     import torch
     if cone_mode not in (0, 2):
         raise ValueError("cone_mode must be 0 or 2 (a per-batch choice would make molecules depend on the packing)")
+    if pose is not None:
+        kwargs = dict(kwargs, pose=pose)
 
     def ligand_sizes(job, ids):
         """Ligand sizes of the slots `ids` of one job: fixed, or drawn from p(n_lig | n_pocket)
@@ -314,7 +327,14 @@ def main(argv=None):
     ap.add_argument("--trusted-checkpoint", action="store_true")
     ap.add_argument("--metrics", action="store_true",
                     help="write metrics.json (metrics.MoleculeSetMetrics of the raw molecules, one group per pocket)")
+    ap.add_argument("--max_clashes", type=int, default=None,
+                    help="check every sample against its pocket's heavy atoms (pose.py) and accept at most this many clash "
+                         "pairs; rejected slots are refilled; metrics.json gains a 'pose' block")
+    ap.add_argument("--min_contact_fraction", type=float, default=None,
+                    help="with --max_clashes: also ask this share of a molecule's atoms to be in contact with the pocket")
     a = ap.parse_args(argv)
+    if a.min_contact_fraction is not None and a.max_clashes is None:
+        ap.error("--min_contact_fraction needs --max_clashes")
     from .molecules import PROCESS_MOLECULE_COVERAGE
     print("[testset] " + PROCESS_MOLECULE_COVERAGE, file=sys.stderr)
     if a.relax:
@@ -332,10 +352,16 @@ def main(argv=None):
     jobs = jobs_from_test_dir(gen, a.test_dir, a.n_samples, test_list, a.fix_n_nodes)
     mine = assign_to_ranks(number_jobs(jobs), world)[rank]
     extra = dict(resamplings=a.resamplings, jump_length=a.jump_length) if gen.mode == "joint" else {}
+    pose_valid = None
+    if a.max_clashes is not None:
+        from . import pose as pose_mod
+        print("[testset] " + pose_mod.POSE_COVERAGE, file=sys.stderr)
+        pose_valid = pose_mod.pose_filter(a.max_clashes, a.min_contact_fraction)
+        extra["pose"] = True
     driver = TestSetDriver(make_hip_sampler(gen, a.timesteps, a.seed, largest_frag=not a.all_frags,
                                             n_nodes_bias=a.n_nodes_bias, n_nodes_min=a.n_nodes_min,
                                             cone_mode=cone_mode_for_jobs(jobs), **extra),
-                           a.batch_size, is_valid=valence_filter if a.sanitize else None)
+                           a.batch_size, is_valid=all_of(pose_valid, valence_filter if a.sanitize else None))
     failed = None
     try:
         driver.run(mine)
@@ -353,11 +379,25 @@ def main(argv=None):
     if rank == 0:
         with open(os.path.join(a.outdir, "process_molecule.txt"), "w") as f:
             f.write(PROCESS_MOLECULE_COVERAGE + "\n")
+    metrics_path = os.path.join(a.outdir, "metrics.json" if world == 1 else f"metrics.rank{rank}.json")
+    pose_block = None
+    if a.max_clashes is not None:               # of the molecules as written: raw/ and processed/ (this rank's pockets)
+        pose_block = {"max_clashes": a.max_clashes, "min_contact_fraction": a.min_contact_fraction,
+                      "raw": pose_mod.summarize_poses([m for j in mine for m in j.raw]),
+                      "accepted": pose_mod.summarize_poses([m for j in mine for m in j.valid]),
+                      "pockets": [{"name": j.name, "raw": pose_mod.summarize_poses(j.raw),
+                                   "accepted": pose_mod.summarize_poses(j.valid)} for j in mine],
+                      "coverage": pose_mod.POSE_COVERAGE}
     if a.metrics:                               # of the molecules as written under raw/ (this rank's pockets)
         from . import metrics
         summary = metrics.summarize([[m for m in j.raw if m is not None] for j in mine], gen.dataset_info, [j.name for j in mine], gen.device)
-        metrics.write_summary(os.path.join(a.outdir, "metrics.json" if world == 1 else f"metrics.rank{rank}.json"), summary,
-                              prefix="[testset] ")
+        if pose_block is not None:
+            summary["pose"] = pose_block
+        metrics.write_summary(metrics_path, summary, prefix="[testset] ")
+    elif pose_block is not None:
+        import json
+        with open(metrics_path, "w") as f:
+            json.dump({"pose": pose_block}, f, indent=1)
     if rank == 0 and times:
         secs = [t[1] for t in times]
         mean = sum(secs) / len(secs)

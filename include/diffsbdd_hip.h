@@ -821,6 +821,24 @@ int dsbdd_mol_graph_stats(void* stream, const int8_t* order, const int32_t* atom
 int dsbdd_fp_diversity(void* stream, const uint32_t* fingerprint, const int32_t* group_off, int64_t n_groups, double* sum,
                        int64_t* pairs);
 
+/* Pose checks of a batch of ligands against the heavy atoms of their pockets (csrc/pose_check.h), one launch, one
+ * workgroup per molecule.  lig_x [N][3] (Angstrom) and lig_r [N] (van-der-Waals radii) hold the molecules one after the
+ * other, mol_off [batch+1] their first rows (N = mol_off[batch]; empty molecules allowed), mol_group [batch] the pocket
+ * group of every molecule in any order; poc_x [M][3], poc_r [M] the pocket atoms, group_off [n_groups+1] the first row of
+ * every group (M = group_off[n_groups]; a pocket shared by many molecules is stored once, a group may be unused).
+ * float32, every operation rounded on its own:  d = sqrt((dx dx + dy dy) + dz dz);  clash iff d < (r_i + r_j) - tol;
+ * contact iff d < contact; both strict, false for NaN.
+ * atom_out [N][4]: clashing pocket atoms, pocket atoms in contact, index within the group of the nearest pocket atom (ties:
+ * the smallest index; -1 without one), bit pattern of its d (+inf without one).
+ * mol_out [batch][8]: n_atoms, clash pairs, atoms with a clash, contact pairs, atoms with a contact, nonfinite (1 when a
+ * coordinate of the molecule is NaN or +-inf), bit pattern of the smallest d, 0.
+ * No atomics; the result does not depend on the order of anything.  Offsets and group ids are range-checked on the device:
+ * a molecule whose rows or group fail the check is read as empty / as having an empty group.  batch = 0 launches nothing;
+ * null pointers, negative counts and a non-finite or negative tol / contact are DSBDD_ERR_ARG. */
+int dsbdd_pose_check(void* stream, const float* lig_x, const float* lig_r, const int32_t* mol_off, int64_t batch,
+                     const int32_t* mol_group, const float* poc_x, const float* poc_r, const int32_t* group_off,
+                     int64_t n_groups, float tol, float contact, int32_t* atom_out, int32_t* mol_out);
+
 /* ---- ligands as input: the packed batch of the design front ends -------------*/
 /* One launch that writes the ligand batch of substructure inpainting and of
  * diversification (inpaint.py:114-141, optimize.py:39-62 of the reference build
