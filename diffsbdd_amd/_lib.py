@@ -133,6 +133,8 @@ SIGNATURES = {
     "dsbdd_mol_graph_stats": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "dsbdd_fp_diversity": (C.c_int, [_P, _P, _P, _I64, _P, _P]),
     "dsbdd_pose_check": (C.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P, _P, _I64, _F, _F, _P, _P]),
+    "dsbdd_vina_type": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _I32, _P, _P]),
+    "dsbdd_vina_score": (C.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, _P]),
     "dsbdd_pack_ligands": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _P, _P, _P, _I64, _I64, _I32, _P, _P, _P, _P, _P]),
     # training-step building blocks (struct arguments are passed by pointer: ctypes.byref / arrays)
     "dsbdd_train_scratch_bytes": (C.c_size_t, [_I32, _I64, _I64]),

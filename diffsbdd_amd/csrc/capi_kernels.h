@@ -268,6 +268,38 @@ int dsbdd_pose_check(void* stream, const float* lig_x, const float* lig_r, const
   return DSBDD_OK;
 }
 
+int dsbdd_vina_type(void* stream, const int8_t* order, const int32_t* atom_type, const int32_t* mol_off, int64_t batch,
+                    int32_t n_types, const int32_t* class_elem, int32_t n_max, int32_t* lig_code, int32_t* mol_int) {
+  StreamDevice stream_device_(stream);
+  if (!order || !atom_type || !mol_off || !class_elem || !lig_code || !mol_int) return fail(DSBDD_ERR_ARG, "null argument");
+  if (batch < 0 || batch > 0x7fffffff || n_types < 1) return fail(DSBDD_ERR_ARG, "bad batch or n_types");
+  if (n_max < 1 || n_max > kMolMaxAtoms)
+    return fail(DSBDD_ERR_ARG, "n_max must be in [1, " + std::to_string(kMolMaxAtoms) + "]");
+  if (batch == 0) return DSBDD_OK;
+  VinaTypeArgs a{reinterpret_cast<const signed char*>(order), atom_type, mol_off, class_elem, (int)batch, n_types, n_max,
+                 lig_code, mol_int};
+  hipLaunchKernelGGL(vina_type_kernel, dim3((unsigned)batch), dim3(64), 0, static_cast<hipStream_t>(stream), a);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_vina_score(void* stream, const float* lig_x, const int32_t* lig_code, const int32_t* mol_off, int64_t batch,
+                     const int32_t* mol_group, const int32_t* mol_int, const float* poc_x, const int32_t* poc_code,
+                     const int32_t* group_off, int64_t n_groups, float* atom_out, float* mol_out, int32_t* mol_flag) {
+  StreamDevice stream_device_(stream);
+  if (!lig_x || !lig_code || !mol_off || !mol_group || !mol_int || !poc_x || !poc_code || !group_off || !atom_out ||
+      !mol_out || !mol_flag)
+    return fail(DSBDD_ERR_ARG, "null argument");
+  if (batch < 0 || batch > 0x7fffffff || n_groups < 0 || n_groups > 0x7fffffff)
+    return fail(DSBDD_ERR_ARG, "bad batch or n_groups");
+  if (batch == 0) return DSBDD_OK;
+  VinaScoreArgs a{lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_code, group_off, (int)batch, (int)n_groups,
+                  atom_out, mol_out, mol_flag};
+  hipLaunchKernelGGL(vina_score_kernel, dim3((unsigned)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
 int dsbdd_pack_ligands(void* stream, const float* tmpl_x, const int32_t* tmpl_type, const int32_t* tmpl_ptr,
                        int32_t n_tmpl, int64_t tmpl_rows, const int32_t* slot_tmpl, const int32_t* slot_size,
                        const int32_t* slot_off, int64_t batch, int64_t n_rows, int32_t atom_nf, float* x,

@@ -40,6 +40,7 @@
 #include "molecule.h"
 #include "mol_metrics.h"
 #include "pose_check.h"
+#include "vina_score.h"
 #include "node_chain.h"
 #include "node_linear.h"
 #include "train.h"

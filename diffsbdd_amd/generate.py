@@ -196,20 +196,22 @@ class LigandGenerator:
     @torch.no_grad()
     def generate_ligands(self, pdb_file, n_samples, pocket_ids=None, ref_ligand=None, num_nodes_lig=None,
                          sanitize=False, largest_frag=False, relax_iter=0, timesteps=None,
-                         n_nodes_bias=0, n_nodes_min=0, pose=None, **kwargs):
+                         n_nodes_bias=0, n_nodes_min=0, pose=None, vina=None, **kwargs):
         """`pose=True` (or a dict of `tol` / `contact`) checks every sample against the heavy atoms of the selected
-        residues on the device (pose.py) and attaches the record as `m.pose`."""
+        residues on the device (pose.py) and attaches the record as `m.pose`.  `vina=True` scores every sample against
+        the same atoms (vina.py: a Vina-type score, not smina output) and attaches the record as `m.vina`."""
         if sanitize or relax_iter:
             raise NotImplementedError(self._RDKIT_REFUSAL)
-        pose = self._pose_options(pose)
+        pose, vina = self._pose_options(pose), self._vina_options(vina)
         residues = self.select_pocket_residues(pdb_file, pocket_ids, ref_ligand)
         pocket = self.prepare_pocket(residues, repeats=n_samples)
         xh_lig, lig_mask = self.sample_for_pocket(pocket, n_samples, num_nodes_lig, timesteps,
                                                   n_nodes_bias, n_nodes_min, **kwargs)
         x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
         stats = None if pose is None else self._pose_stats(x, atom_type, lig_mask, [residues], [n_samples], pose)
+        scores = None if vina is None else self._vina_stats(x, atom_type, lig_mask, [residues], [n_samples])
         return build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=n_samples,
-                               pose=stats)
+                               pose=stats, vina=scores)
 
     def _drop_virtual(self, xh_lig, lig_mask):
         """(x, atom_type, lig_mask) of the generated atoms; with virtual nodes the atoms of the virtual class are
@@ -259,6 +261,55 @@ class LigandGenerator:
         groups = np.repeat(np.arange(len(counts)), counts)
         return pose_mod.pose_check(x, self._pose_radii[atom_type], lig_mask, pockets, groups, batch=int(sum(counts)),
                                    tol=opts["tol"], contact=opts["contact"])
+
+    # -- Vina-type score of the sampled batch (vina.py): only with the samplers' `vina=` option -----------------------------
+    @staticmethod
+    def _vina_options(vina):
+        """The samplers' `vina` keyword: None / False = off (nothing runs); True = on; a dict may carry 'residues' where the
+        sampler is not given any (`diversify_ligands`)."""
+        if vina is None or vina is False:
+            return None
+        opts = {} if vina is True else dict(vina)
+        unknown = set(opts) - {"residues"}
+        if unknown:
+            raise ValueError(f"vina: unknown option(s) {sorted(unknown)}")
+        return opts
+
+    def _vina_pocket(self, residues):
+        """Typed heavy atoms of a job's residues as a one-group `vina.VinaPocket` on the device: typed and uploaded once per
+        residue list, as `_pose_pocket`."""
+        from . import vina as vina_mod
+        cache = self.__dict__.setdefault("_vina_pockets", {})
+        hit = cache.get(id(residues))
+        if hit is None or hit[0] is not residues:
+            while len(cache) >= 256:
+                cache.pop(next(iter(cache)))
+            hit = (residues, vina_mod.VinaPocket.upload([vina_mod.type_pocket(residues)], self.device))
+            cache[id(residues)] = hit
+        return hit[1]
+
+    def _vina_stats(self, x, atom_type, lig_mask, residue_sets, counts):
+        """`vina.vina_score` of a sampled batch (after `_drop_virtual`): one group per job, `counts[k]` samples on group k."""
+        from . import vina as vina_mod
+        pockets = vina_mod.VinaPocket.concat([self._vina_pocket(r) for r in residue_sets])
+        groups = np.repeat(np.arange(len(counts)), counts)
+        return vina_mod.vina_score(x, atom_type, lig_mask, pockets, self.dataset_info, groups, batch=int(sum(counts)))
+
+    @torch.no_grad()
+    def vina_scores(self, pdb_file, molecules, pocket_ids=None, ref_ligand=None, scope="protein"):
+        """Vina-type score of given molecules against the protein of `pdb_file` (vina.py; bonds perceived from distances as
+        for generated molecules).  `molecules` and `scope` as for `check_poses`.  Returns one dict per molecule, in order:
+        {'n_atoms', 'untyped', 'n_rot', 'nonfinite', 'gauss1', 'gauss2', 'repulsion', 'hydrophobic', 'hbond', 'inter',
+        'score'} over heavy atoms.  Not smina output: see `vina.VINA_COVERAGE`."""
+        from . import vina as vina_mod
+        if scope == "pocket":
+            residues = self.select_pocket_residues(pdb_file, pocket_ids, ref_ligand)
+        elif scope == "protein":
+            residues = pocket_io.read_pdb_residues(pdb_file)
+        else:
+            raise ValueError("scope must be 'protein' or 'pocket'")
+        pockets = vina_mod.VinaPocket.upload([vina_mod.type_pocket(residues)], self.device)
+        return [r.as_dict() for r in vina_mod.score_molecules(molecules, pockets, self.dataset_info)]
 
     @torch.no_grad()
     def check_poses(self, pdb_file, molecules, pocket_ids=None, ref_ligand=None, scope="protein", tol=None, contact=None):
@@ -325,7 +376,7 @@ class LigandGenerator:
     # -- several different pockets in one batch ---------------------------
     @torch.no_grad()
     def generate_for_pockets(self, jobs, timesteps=None, largest_frag=False, n_nodes_bias=0,
-                             n_nodes_min=0, seed=None, sample_ids=None, pose=None, **kwargs):
+                             n_nodes_min=0, seed=None, sample_ids=None, pose=None, vina=None, **kwargs):
         """One sampling batch over several different pockets.
 
         The reference's test driver (test.py:59-176) samples one pocket at a time; the
@@ -336,8 +387,9 @@ class LigandGenerator:
         global id per slot of the packed batch) a sample is the same molecule in any packing that
         gives it the same global id.
         `pose=True` (or a dict of `tol` / `contact`): one more launch checks every sample against the heavy atoms of its
-        job's residues before the molecules are built; every molecule carries the record as `m.pose`."""
-        pose = self._pose_options(pose)
+        job's residues before the molecules are built; every molecule carries the record as `m.pose`.
+        `vina=True`: two more launches score every sample against the same atoms (vina.py); the record is `m.vina`."""
+        pose, vina = self._pose_options(pose), self._vina_options(vina)
         parts, sizes, counts = [], [], []
         base = 0
         for residues, n, n_lig in jobs:
@@ -359,7 +411,9 @@ class LigandGenerator:
                                                   n_nodes_bias, n_nodes_min, **kwargs)
         x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
         stats = None if pose is None else self._pose_stats(x, atom_type, lig_mask, [j[0] for j in jobs], counts, pose)
-        mols = build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=base, pose=stats)
+        scores = None if vina is None else self._vina_stats(x, atom_type, lig_mask, [j[0] for j in jobs], counts)
+        mols = build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=base, pose=stats,
+                               vina=scores)
         out, o = [], 0
         for n in counts:
             out.append(mols[o:o + n])
@@ -464,7 +518,7 @@ class LigandGenerator:
 
     @torch.no_grad()
     def inpaint_for_pockets(self, jobs, timesteps=None, resamplings=1, center="ligand", largest_frag=False,
-                            seed=None, sample_ids=None, jump_length=1, cone_mode=2, pose=None):
+                            seed=None, sample_ids=None, jump_length=1, cone_mode=2, pose=None, vina=None):
         """Several design jobs in one batch: the packed-batch twin of `generate_for_pockets`.  `jobs`: list of
         (residues, n_samples, substructure, add_n_nodes or sizes) -- `substructure` a `Molecule` or an (xyz, elements)
         pair, the last entry None (sizes drawn), an int (atoms to add) or one ligand size per sample.  Returns one list
@@ -474,9 +528,9 @@ class LigandGenerator:
         model otherwise switches by the number of distinct pockets in the batch (en_diffusion.cone_mode; on and off
         differ in rounding), is pinned to `cone_mode` (2 = on, 0 = off; None = the model's own per-batch rule) and the
         automatic 16-row granule is switched off for the call, as the test-set driver does (testset.make_hip_sampler).
-        `pose`: as for `generate_for_pockets`."""
+        `pose`, `vina`: as for `generate_for_pockets`."""
         self._check_inpaint_model(center)
-        pose = self._pose_options(pose)
+        pose, vina = self._pose_options(pose), self._vina_options(vina)
         if cone_mode not in (None, 0, 2):
             raise ValueError("cone_mode must be 2, 0 or None")
         parts, templates, slot_tmpl, sizes, counts = [], [], [], [], []
@@ -514,7 +568,9 @@ class LigandGenerator:
             self.ddpm.cone_mode, self.ddpm.edge_granule16 = saved
         x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
         stats = None if pose is None else self._pose_stats(x, atom_type, lig_mask, [j[0] for j in jobs], counts, pose)
-        mols = build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=base, pose=stats)
+        scores = None if vina is None else self._vina_stats(x, atom_type, lig_mask, [j[0] for j in jobs], counts)
+        mols = build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=base, pose=stats,
+                               vina=scores)
         out, o = [], 0
         for n in counts:
             out.append(mols[o:o + n])
@@ -535,16 +591,19 @@ class LigandGenerator:
         return out_lig, lig_mask
 
     @torch.no_grad()
-    def diversify_ligands(self, pocket, molecules, noising_steps, largest_frag=False, seed=None, pose=None):
+    def diversify_ligands(self, pocket, molecules, noising_steps, largest_frag=False, seed=None, pose=None, vina=None):
         """Partially noise and denoise ligands in their pocket: the reference's `diversify_ligands`
         (optimize.py:92-147).  `pocket`: the dict of `prepare_pocket(residues, repeats=len(molecules))`; `molecules`:
         a list of `Molecule` objects or (xyz, elements) pairs, or an SDF path -- one ligand per pocket replica.
         Returns one molecule per input, in order.  `pose`: a dict with `residues` (the residues `pocket` was prepared from:
         the pocket dict holds the model's nodes, not the protein's atoms) and optionally `tol` / `contact` attaches the pose
-        record of every result as `m.pose`."""
+        record of every result as `m.pose`.  `vina`: a dict with `residues` attaches the Vina-type score record of every
+        result as `m.vina` (vina.py)."""
         if not hasattr(self.ddpm, "diversify"):
             raise NotImplementedError(f"{type(self.ddpm).__name__} has no diversify (pocket-conditioned models only)")
-        pose = self._pose_options(pose)
+        pose, vina = self._pose_options(pose), self._vina_options(vina)
+        if vina is not None and vina.get("residues") is None:
+            raise ValueError("diversify_ligands: vina needs the residues the pocket was prepared from (vina=dict(residues=...))")
         if pose is not None and pose.get("residues") is None:
             raise ValueError("diversify_ligands: pose needs the residues the pocket was prepared from (pose=dict(residues=...))")
         templates = ligand_io.as_templates(molecules, self.lig_type_encoder)
@@ -558,7 +617,9 @@ class LigandGenerator:
         xh_lig, lig_mask = self._diversify_chain(pocket, ligand, noising_steps)
         x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
         stats = None if pose is None else self._pose_stats(x, atom_type, lig_mask, [pose["residues"]], [n], pose)
-        return build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=n, pose=stats)
+        scores = None if vina is None else self._vina_stats(x, atom_type, lig_mask, [vina["residues"]], [n])
+        return build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=n, pose=stats,
+                               vina=scores)
 
     # -- scoring given ligands (score.py) ---------------------------------------------------------------------
     @torch.no_grad()
@@ -651,7 +712,8 @@ class LigandGenerator:
         reference ligand repeated `population_size` times; every later generation takes the `top_k` molecules of the
         previous one by `objective`, each `population_size // top_k` times, and fills the remainder by a SEEDED draw
         among them (the reference draws unseeded).  `objective` is any callable on a `Molecule`, larger = better; QED
-        and SA need RDKit and are not provided -- where it is installed pass e.g. `lambda m: qed(m.to_rdkit())`.
+        and SA need RDKit and are not provided -- where it is installed pass e.g. `lambda m: qed(m.to_rdkit())`;
+        `vina.objective(self, residues)` is a built-in one that needs no RDKit (minus the Vina-type score of the pose).
         Molecules that come back empty do not enter the next generation.  Returns (molecules of the last generation,
         history): history is a list of {'generation', 'index', 'score', 'fate'} records, fate 'initial' (the
         reference), 'survived' (selected as a parent), 'purged', 'rejected' (no molecule) or 'final' (last generation).
@@ -736,10 +798,15 @@ def main(argv=None):
                     help="write metrics.json next to the output (metrics.MoleculeSetMetrics of the written molecules)")
     ap.add_argument("--pose", action="store_true",
                     help="check every sample against the pocket's heavy atoms (pose.py): records to stderr and <outfile>.pose.csv")
+    ap.add_argument("--vina", action="store_true",
+                    help="Vina-type score of every sample against the pocket's heavy atoms (vina.py; not smina output): "
+                         "records to stderr and <outfile>.vina.csv")
     a = ap.parse_args(argv)
     bs = a.batch_size or a.n_samples
     assert a.n_samples % bs == 0
     extra = dict(pose=True) if a.pose else {}
+    if a.vina:
+        extra["vina"] = True
     gen = LigandGenerator.from_checkpoint(a.checkpoint, device="cuda", trusted=a.trusted_checkpoint)
     molecules = []
     for i in range(a.n_samples // bs):
@@ -757,6 +824,13 @@ def main(argv=None):
         for _, k, rec in rows:
             print(f"[generate] pose mol_{k}: {rec.as_dict()}", file=sys.stderr)
         pose_mod.write_csv(a.outfile + ".pose.csv", rows)
+    if a.vina:
+        from . import vina as vina_mod
+        print("[generate] " + vina_mod.VINA_COVERAGE, file=sys.stderr)
+        rows = [(os.path.basename(a.outfile), k, m.vina) for k, m in enumerate(molecules)]
+        for _, k, rec in rows:
+            print(f"[generate] vina mol_{k}: {rec.as_dict()}", file=sys.stderr)
+        vina_mod.write_csv(a.outfile + ".vina.csv", rows)
     from .molecules import PROCESS_MOLECULE_COVERAGE
     print("[generate] " + PROCESS_MOLECULE_COVERAGE, file=sys.stderr)
     print(f"wrote {len(molecules)} molecules to {a.outfile}")

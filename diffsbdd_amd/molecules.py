@@ -65,6 +65,8 @@ class Molecule:
         m.n_generated_atoms = self.num_atoms          # size of the sample the fragment was cut from
         if hasattr(self, "pose"):                     # pose record (pose.MolPose): the kept atoms' rows, totals recomputed
             m.pose = self.pose.subset(keep)
+        if hasattr(self, "vina"):                     # score record (vina.MolVina): the kept atoms' rows, sums and rotors recomputed
+            m.vina = self.vina.subset(keep, bonds)
         return m
 
     def valences(self):
@@ -171,15 +173,17 @@ def bond_orders(x, atom_type, lig_mask, info, n_max=None, batch=None):
     return out, sizes
 
 
-def build_molecules(x, atom_type, lig_mask, info, largest_frag=False, batch=None, pose=None):
+def build_molecules(x, atom_type, lig_mask, info, largest_frag=False, batch=None, pose=None, vina=None):
     """Batch version of `build_molecule(..., use_openbabel=False)` +
     `process_molecule(largest_frag=...)` (molecule_builder.py:140-160, 162-214):
     list of `Molecule`, one per sample, in sample order.  `pose`: the `pose.PoseStats` of the same batch; every
-    molecule then carries its record as `m.pose` (a fragment: the record of its atoms)."""
+    molecule then carries its record as `m.pose` (a fragment: the record of its atoms).  `vina`: the `vina.VinaScores` of
+    the same batch, attached as `m.vina` in the same way."""
     if isinstance(info, str):
         info = dataset_info(info)
     orders, sizes = bond_orders(x, atom_type, lig_mask, info, batch=batch)
     poses = None if pose is None else pose.molecules()
+    scores = None if vina is None else vina.molecules()
     orders = orders.cpu().numpy()
     sizes = sizes.cpu().numpy()
     xs = x.detach().float().cpu().numpy()
@@ -193,6 +197,8 @@ def build_molecules(x, atom_type, lig_mask, info, largest_frag=False, batch=None
         m = Molecule(xs[o:o + n].copy(), [dec[int(t)] for t in ts[o:o + n]], bonds)
         if poses is not None:
             m.pose = poses[b]
+        if scores is not None:
+            m.vina = scores[b]
         mols.append(m.largest_fragment() if largest_frag else m)
         o += n
     return mols

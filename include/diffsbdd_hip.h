@@ -839,6 +839,47 @@ int dsbdd_pose_check(void* stream, const float* lig_x, const float* lig_r, const
                      const int32_t* mol_group, const float* poc_x, const float* poc_r, const int32_t* group_off,
                      int64_t n_groups, float tol, float contact, int32_t* atom_out, int32_t* mol_out);
 
+/* Vina-type interaction score of such a batch (csrc/vina_score.h; functional form and weights of Trott & Olson, J. Comput.
+ * Chem. 31 (2010) 455, heavy atoms only -- NOT the output of smina or Vina: no hydrogens, no charges, no intramolecular
+ * term).  Two launches: the typing of the ligand atoms from their bond orders, then the pair sum.
+ *
+ * Atom code, one int32 per atom: bits 0-3 the class (0 untyped, 1 C, 2 N, 3 O, 4 P, 5 S, 6 F, 7 Cl, 8 Br, 9 I, 10 metal;
+ * 11-15 are read as untyped), bit 4 hydrophobic, bit 5 hydrogen-bond donor, bit 6 acceptor.  Untyped atoms take part in
+ * no pair term; as neighbours in the typing rules they count as heteroatoms.
+ *
+ * dsbdd_vina_type: one wave per molecule, integers only.  order / atom_type / mol_off / n_max as for
+ * dsbdd_mol_graph_stats (orders outside 1..3 are no bond; a molecule longer than n_max is read as its first n_max atoms,
+ * the codes of the atoms after them are written 0); class_elem [n_types] the class of every atom type (a type id outside
+ * [0, n_types) or a class outside the list is untyped).  With s = the sum of bond orders at the atom and a heteroatom
+ * neighbour = any neighbour that is not carbon:  C hydrophobic iff it has no heteroatom neighbour;  F, Cl, Br, I
+ * hydrophobic;  N donor iff s < 3, acceptor iff s = 3 and one of its bonds has order >= 2;  O acceptor, donor iff s < 2;
+ * S, P no flags;  metal donor.  lig_code [N]; mol_int [batch][4] = typed atoms, untyped atoms, N_rot, 0, where N_rot = the
+ * bonds of order 1 that are in no ring (their ends are not connected when the bond is removed) and whose two ends both have
+ * heavy degree >= 2 (amide and conjugated bonds are not excluded).
+ *
+ * dsbdd_vina_score: one workgroup per molecule; lig_x / mol_off / mol_group / poc_x / group_off and every group
+ * convention exactly as for dsbdd_pose_check, lig_code [N] and poc_code [M] atom codes, mol_int what dsbdd_vina_type wrote
+ * (N_rot is read; a negative one as 0).  A pair of typed atoms counts iff its float32 distance r = sqrt((dx dx + dy dy) +
+ * dz dz), every operation rounded on its own, is < 8.0, strictly.  With d = r - R_i - R_j (R by class: C 1.9, N 1.8, O 1.7,
+ * P 2.1, S 2.0, F 1.5, Cl 1.8, Br 2.0, I 2.2, metal 1.2):
+ *   gauss1 = exp(-(d / 0.5)^2);  gauss2 = exp(-((d - 3) / 2)^2);  repulsion = d^2 if d < 0, else 0;
+ *   hydrophobic (both atoms hydrophobic) = 1 if d <= 0.5, 1.5 - d if 0.5 < d < 1.5, else 0;
+ *   hbond (one atom donor and the other acceptor, once per pair) = 1 if d <= -0.7, -d / 0.7 if -0.7 < d < 0, else 0,
+ * all evaluated and summed in float64 from the float32 r, stored as float32.
+ * atom_out [N][5]: the unweighted sums of the five terms over the atom's pairs.  mol_out [batch][8]: the five sums T_k over
+ * the molecule, inter = -0.035579 T_1 - 0.005156 T_2 + 0.840245 T_3 - 0.035069 T_4 - 0.587439 T_5,
+ * score = inter / (1 + 0.05846 N_rot) in kcal/mol, 0.  mol_flag [batch]: 1 when a coordinate of the molecule is NaN or
+ * +-inf; every float output of such a molecule, per atom and per molecule, is NaN.  An empty molecule or group gives zeros.
+ * No atomics; the order of every sum is a function of the molecule and its group alone, so the outputs are bitwise
+ * reproducible and do not depend on the rest of the batch.  Offsets, group ids, type ids and codes are range-checked on
+ * the device (a molecule whose rows fail the check is read as empty and its rows are not written).  batch = 0 launches
+ * nothing; null pointers, negative counts and an n_max outside [1, DSBDD_MOL_MAX_ATOMS] are DSBDD_ERR_ARG. */
+int dsbdd_vina_type(void* stream, const int8_t* order, const int32_t* atom_type, const int32_t* mol_off, int64_t batch,
+                    int32_t n_types, const int32_t* class_elem, int32_t n_max, int32_t* lig_code, int32_t* mol_int);
+int dsbdd_vina_score(void* stream, const float* lig_x, const int32_t* lig_code, const int32_t* mol_off, int64_t batch,
+                     const int32_t* mol_group, const int32_t* mol_int, const float* poc_x, const int32_t* poc_code,
+                     const int32_t* group_off, int64_t n_groups, float* atom_out, float* mol_out, int32_t* mol_flag);
+
 /* ---- ligands as input: the packed batch of the design front ends -------------*/
 /* One launch that writes the ligand batch of substructure inpainting and of
  * diversification (inpaint.py:114-141, optimize.py:39-62 of the reference build

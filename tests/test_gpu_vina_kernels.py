@@ -1,0 +1,202 @@
+"""GPU: dsbdd_vina_type and dsbdd_vina_score (csrc/vina_score.h) through the C ABI against their numpy restatements in
+diffsbdd_amd/vina.py -- integers EQUAL, floats inside the forward bound `vina.error_bound` evaluates in float64 --, bitwise
+reproducibility under re-packing, and the crystal fixture against its independent float64 statement.  Outputs live in
+guarded sentinel buffers; inputs are compared bit for bit afterwards."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from diffsbdd_amd import _lib, vina as V
+from tests import _vina_cases as C
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+GUARD, SENTINEL = 7, 0x5A5A5A5A
+
+
+def _guarded(rows, cols):
+    return torch.full((rows + 2 * GUARD,) + ((cols,) if cols else ()), SENTINEL, dtype=torch.int32, device=DEV)
+
+
+def _intact(buf, rows):
+    buf = buf.cpu().numpy()
+    return bool((buf[:GUARD] == SENTINEL).all() and (buf[GUARD + rows:] == SENTINEL).all())
+
+
+def _unchanged(tensors, b, keys):
+    for k in keys:
+        after = tensors[k].cpu().numpy()
+        assert after.dtype == np.ascontiguousarray(b[k]).dtype, k
+        assert np.array_equal(after.view(np.uint8), np.ascontiguousarray(b[k]).view(np.uint8)), k
+
+
+def launch_type(b):
+    """dsbdd_vina_type on a batch of numpy inputs -> (lig_code with the sentinel where nothing was written, mol_int)."""
+    lib = _lib.load()
+    t = {k: torch.as_tensor(np.ascontiguousarray(b[k]), device=DEV) for k in C.TYPE_KEYS}
+    N, B = len(b["atom_type"]), len(b["mol_off"]) - 1
+    code, mol = _guarded(N, 0), _guarded(B, V.MOL_INT)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    rc = lib.dsbdd_vina_type(stream, t["order"].data_ptr(), t["atom_type"].data_ptr(), t["mol_off"].data_ptr(), B,
+                             len(b["class_elem"]), t["class_elem"].data_ptr(), b["order"].shape[1], code[GUARD:].data_ptr(),
+                             mol[GUARD:].data_ptr())
+    _lib.check(rc, "dsbdd_vina_type")
+    torch.cuda.synchronize()
+    assert _intact(code, N) and _intact(mol, B)                          # nothing written before or after the outputs
+    _unchanged(t, b, C.TYPE_KEYS)
+    return code.cpu().numpy()[GUARD:GUARD + N], mol.cpu().numpy()[GUARD:GUARD + B]
+
+
+def launch_score(b):
+    """dsbdd_vina_score on a batch of numpy inputs -> (atom float32 [N,5], mol float32 [B,8], flag int32 [B]); rows nothing
+    was written to hold the sentinel's bit pattern."""
+    lib = _lib.load()
+    t = {k: torch.as_tensor(np.ascontiguousarray(b[k]), device=DEV) for k in C.SCORE_KEYS}
+    N, B = len(b["lig_x"]), len(b["mol_off"]) - 1
+    atom, mol, flag = _guarded(N, V.ATOM_OUT), _guarded(B, V.MOL_OUT), _guarded(B, 0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ptr = lambda k: (t[k] if t[k].numel() else torch.zeros(4, dtype=t[k].dtype, device=DEV)).data_ptr()
+    rc = lib.dsbdd_vina_score(stream, ptr("lig_x"), ptr("lig_code"), ptr("mol_off"), B, ptr("mol_group"), ptr("mol_int"),
+                              ptr("poc_x"), ptr("poc_code"), ptr("group_off"), len(b["group_off"]) - 1,
+                              atom[GUARD:].data_ptr(), mol[GUARD:].data_ptr(), flag[GUARD:].data_ptr())
+    _lib.check(rc, "dsbdd_vina_score")
+    torch.cuda.synchronize()
+    assert _intact(atom, N) and _intact(mol, B) and _intact(flag, B)
+    _unchanged(t, b, C.SCORE_KEYS)
+    return (atom.cpu().numpy()[GUARD:GUARD + N].view(np.float32), mol.cpu().numpy()[GUARD:GUARD + B].view(np.float32),
+            flag.cpu().numpy()[GUARD:GUARD + B])
+
+
+def _inside(got, want, bound, what):
+    """Every finite entry within its bound; NaN exactly where the restatement has NaN.  Prints the largest fraction used."""
+    got = got.astype(np.float64)
+    assert np.array_equal(np.isnan(got), np.isnan(want)), what
+    live = ~np.isnan(want)
+    err = np.abs(got - want)[live]
+    assert np.all(err <= bound[live]), (what, float((err - bound[live]).max()))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        frac = np.where(bound[live] > 0, err / bound[live], 0.0)
+    print(f"[{what}] largest error / bound = {frac.max() if frac.size else 0.0:.3e}")
+    return frac
+
+
+# 1 ---------------------------------------------------------------------------------------------------------------------------
+def test_typing_equals_the_restatement_on_a_ragged_batch():
+    b = C.type_batch()
+    assert len(b["mol_off"]) - 1 == 16 and b["order"].shape == (16, 128, 128) and max(b["sizes"]) == 140
+    want_code, want_mol = V._vina_type_host(*(b[k] for k in C.TYPE_KEYS), fill=SENTINEL)
+    code, mol = launch_type(b)
+    assert code.dtype == want_code.dtype and mol.dtype == want_mol.dtype
+    bad = np.nonzero(code != want_code)[0]
+    assert len(bad) == 0, (bad[:8], code[bad[:8]], want_code[bad[:8]])
+    assert np.array_equal(mol, want_mol), np.nonzero((mol != want_mol).any(1))[0]
+    # the cases the batch was built for did happen
+    off = b["true_off"]
+    assert mol[6].tolist() == [128, 0, 125, 0] and mol[7].tolist() == [128, 0, 125, 0] and mol[5].tolist() == [20, 0, 0, 0]
+    assert (code[off[7] + 128:off[8]] == 0).all()                          # past n_max: written, untyped
+    assert (code[off[11]:off[13]] == SENTINEL).all() and mol[11].tolist() == [0] * 4 == mol[12].tolist()   # the bad offset
+    assert mol[9].tolist() == [2, 1, 0, 0] and mol[10].tolist() == [2, 2, 1, 0] and mol[0].tolist() == [0] * 4
+    # a smaller n_max: every molecule is read as its first 20 atoms
+    small = dict(b, order=np.ascontiguousarray(b["order"][:, :20, :20]))
+    want_code, want_mol = V._vina_type_host(*(small[k] for k in C.TYPE_KEYS), fill=SENTINEL)
+    code, mol = launch_type(small)
+    assert np.array_equal(code, want_code) and np.array_equal(mol, want_mol) and mol[6].tolist() == [20, 0, 17, 0]
+
+
+# 2 ---------------------------------------------------------------------------------------------------------------------------
+def test_scores_within_the_bound_on_a_ragged_batch():
+    b = C.score_batch()
+    T = V.TILE
+    assert len(b["mol_off"]) - 1 == 16 and np.diff(b["group_off"]).tolist() == [0, 1, T, T + 1, 3 * T + 5, 10]
+    want, margin, atom_bound, mol_bound = C.score_reference()
+    assert margin > C.MARGIN                                               # no pair within 1e-4 A of the cutoff
+    atom, mol, flag = launch_score(b)
+    assert np.array_equal(flag, want.flag) and flag.sum() == 1 and flag[b["nan_mol"]] == 1
+    off = b["mol_off"]
+    fa = _inside(atom, want.atom, atom_bound, "atoms")
+    fm = _inside(mol[:, :7], want.mol[:, :7], mol_bound, "molecules")
+    live = flag == 0
+    assert (mol[live, 7] == 0).all() and np.isnan(mol[b["nan_mol"], :7]).all()
+    nan_rows = slice(off[b["nan_mol"]], off[b["nan_mol"] + 1])
+    assert np.isnan(atom[nan_rows]).all() and not np.isnan(np.delete(atom, np.r_[nan_rows], 0)).any()
+    # the cases the batch was built for did happen
+    assert (mol[live][:, :5].max(0) > 0).all()                              # every term is non-zero somewhere
+    for m in (0, b["empty_mol"], b["untyped_mol"], 10):                     # empty group, no atoms, all untyped, group id out of range
+        assert not mol[m].any() and not atom[off[m]:off[m + 1]].any(), m
+    big = atom[off[b["big_mol"]]:off[b["big_mol"] + 1]]
+    typed = (b["lig_code"][off[b["big_mol"]]:off[b["big_mol"] + 1]] & 15) % 13 != 0
+    assert len(big) == 300 and (big[typed, 1] > 0).all() and not big[~typed].any() and (big[:, 2] > 0).any()
+    assert mol[b["big_mol"], 1] == pytest.approx(big[:, 1].astype(np.float64).sum(), rel=1e-5)
+    print("largest error / bound per term (atoms):", fa.reshape(-1, 5).max(0) if fa.size % 5 == 0 else fa.max())
+
+
+# 3 ---------------------------------------------------------------------------------------------------------------------------
+def test_scores_are_bitwise_reproducible_and_independent_of_the_batch():
+    b = C.score_batch()
+    B = len(b["mol_off"]) - 1
+    atom, mol, flag = launch_score(b)
+    bits = lambda a: np.ascontiguousarray(a).view(np.int32)
+    atom2, mol2, flag2 = launch_score(b)
+    assert np.array_equal(bits(atom), bits(atom2)) and np.array_equal(bits(mol), bits(mol2)) and np.array_equal(flag, flag2)
+    off = b["mol_off"]
+    for m in range(B):                                                      # every molecule alone
+        one, rows = C.sub_batch(b, [m])
+        a1, m1, f1 = launch_score(one)
+        assert np.array_equal(bits(a1), bits(atom[rows])) and np.array_equal(bits(m1[0]), bits(mol[m])) and f1[0] == flag[m], m
+    order = list(range(B))[::-1]                                            # the batch with its molecules in reversed order
+    rev, rows = C.sub_batch(b, order)
+    ar, mr, fr = launch_score(rev)
+    assert np.array_equal(bits(ar), bits(atom[rows])) and np.array_equal(bits(mr), bits(mol[order])) and np.array_equal(fr, flag[order])
+    assert off[-1] == len(atom)
+
+
+# 4 ---------------------------------------------------------------------------------------------------------------------------
+def test_crystal_fixture_on_the_device_against_the_stored_float64_values():
+    z = C.fixture()
+    for name in z["names"]:
+        el, bonds = C.fixture_ligand(z, name)
+        n = len(el)
+        decoder = sorted(set(el))
+        tb = {"order": V.orders_from_bonds(n, bonds)[None], "atom_type": np.asarray([decoder.index(e) for e in el], np.int32),
+              "mol_off": np.asarray([0, n], np.int32), "class_elem": V.class_table(decoder)}
+        code, mol_int = launch_type(tb)
+        assert np.array_equal(code, z[f"{name}_lig_code"]) and mol_int[0].tolist() == [n, 0, int(z[f"{name}_n_rot"]), 0]
+        poc_x, poc_code = z[f"{name}_poc_x"], z[f"{name}_poc_code"]
+        for variant in ("crystal", "shifted"):
+            sb = {"lig_x": z[f"{name}_{variant}_x"], "lig_code": code, "mol_off": tb["mol_off"], "mol_group": np.zeros(1, np.int32),
+                  "mol_int": mol_int, "poc_x": poc_x, "poc_code": poc_code, "group_off": np.asarray([0, len(poc_x)], np.int32)}
+            atom_bound, mol_bound = V.error_bound(*(sb[k] for k in C.SCORE_KEYS))
+            atom, mol, flag = launch_score(sb)
+            assert flag[0] == 0
+            stored = np.concatenate([z[f"{name}_{variant}_terms"], [z[f"{name}_{variant}_inter"], z[f"{name}_{variant}_score"]]])
+            _inside(atom, z[f"{name}_{variant}_atom"], atom_bound, f"{name} {variant} atoms")
+            _inside(mol[:, :7], stored[None], mol_bound, f"{name} {variant} molecule")
+        # the front end on the same data: bonds from the file's list, the pocket typed from residue and atom names
+        pockets = V.VinaPocket.upload([V.type_pocket(C.fixture_residues(z, name))], DEV)
+        rec, = V.score_molecules([(z[f"{name}_crystal_x"], el, bonds)], pockets, bonds="file")
+        assert np.array_equal(rec.code, code) and rec.n_rot == int(z[f"{name}_n_rot"]) and rec.score < 0
+        assert rec.score == pytest.approx(float(z[f"{name}_crystal_score"]), abs=float(mol_bound[0, 6]) * 2 + 1e-6)
+
+
+# 5 ---------------------------------------------------------------------------------------------------------------------------
+def test_empty_batches_and_the_python_entry():
+    pockets = V.VinaPocket.upload([V.TypedPocket(np.asarray([[3.8, 0, 0]], np.float32), np.asarray([17], np.int32))], DEV)
+    none = V.vina_score(torch.zeros((0, 3), device=DEV), torch.zeros(0, dtype=torch.int64, device=DEV),
+                        torch.zeros(0, dtype=torch.int64, device=DEV), pockets, "crossdock", batch=0)
+    assert tuple(none.atom.shape) == (0, 5) and tuple(none.mol.shape) == (0, 8) and none.molecules() == []
+    hollow = V.vina_score(torch.zeros((0, 3), device=DEV), torch.zeros(0, dtype=torch.int64, device=DEV),
+                          torch.zeros(0, dtype=torch.int64, device=DEV), pockets, "crossdock", batch=3)
+    assert not hollow.mol.cpu().numpy().any() and hollow.flag.cpu().tolist() == [0, 0, 0]
+    # one carbon 3.8 A from a hydrophobic carbon: d = 0; a device group id out of range reads as an empty group
+    x = torch.zeros((2, 3), device=DEV)
+    st = V.vina_score(x, torch.zeros(2, dtype=torch.int64, device=DEV), torch.arange(2, device=DEV), pockets, "crossdock",
+                      mol_group=torch.tensor([0, 5], dtype=torch.int32, device=DEV))
+    assert st.lig_code.cpu().tolist() == [17, 17] and st.n_rot.cpu().tolist() == [0, 0]
+    assert st.terms.cpu().numpy()[0] == pytest.approx([1.0, np.exp(-2.25), 0.0, 1.0, 0.0], abs=1e-6)
+    assert not st.mol.cpu().numpy()[1].any()
+    with pytest.raises(ValueError, match="mol_group"):
+        V.vina_score(x, torch.zeros(2, dtype=torch.int64, device=DEV), torch.arange(2, device=DEV), pockets, "crossdock",
+                     mol_group=[0, 5])
