@@ -1,5 +1,5 @@
 // Thin C-ABI wrappers of the stand-alone kernels (included by engine.hip): DDPM steps (ddpm.h), keyed noise, node GEMM,
-// the node chain's row split (chain_split.h), bond orders (molecule.h), molecule graph statistics and fingerprint distances (mol_metrics.h), pose checks (pose_check.h), ligand packing (ligand_pack.h), the radius graph (radius_graph.h).
+// the node chain's row split (chain_split.h), bond orders (molecule.h), molecule graph statistics and fingerprint distances (mol_metrics.h), pose checks and the Vina-type score (pose_check.h, vina_score.h on pair_sweep.h), ligand packing (ligand_pack.h), the radius graph (radius_graph.h).
 #pragma once
 
 extern "C" {
@@ -250,18 +250,24 @@ int dsbdd_fp_diversity(void* stream, const uint32_t* fingerprint, const int32_t*
   return DSBDD_OK;
 }
 
+// the counts of the two pair entries (pair_sweep.h: PairBatch holds them as int)
+static int check_pair_counts(int64_t batch, int64_t n_groups) {
+  if (batch < 0 || batch > 0x7fffffff || n_groups < 0 || n_groups > 0x7fffffff)
+    return fail(DSBDD_ERR_ARG, "bad batch or n_groups");
+  return DSBDD_OK;
+}
+
 int dsbdd_pose_check(void* stream, const float* lig_x, const float* lig_r, const int32_t* mol_off, int64_t batch,
                      const int32_t* mol_group, const float* poc_x, const float* poc_r, const int32_t* group_off,
                      int64_t n_groups, float tol, float contact, int32_t* atom_out, int32_t* mol_out) {
   StreamDevice stream_device_(stream);
   if (!lig_x || !lig_r || !mol_off || !mol_group || !poc_x || !poc_r || !group_off || !atom_out || !mol_out)
     return fail(DSBDD_ERR_ARG, "null argument");
-  if (batch < 0 || batch > 0x7fffffff || n_groups < 0 || n_groups > 0x7fffffff)
-    return fail(DSBDD_ERR_ARG, "bad batch or n_groups");
+  if (int rc = check_pair_counts(batch, n_groups)) return rc;
   if (!std::isfinite(tol) || tol < 0.f || !std::isfinite(contact) || contact < 0.f)
     return fail(DSBDD_ERR_ARG, "tol and contact must be finite and not negative");
   if (batch == 0) return DSBDD_OK;
-  PoseArgs a{lig_x, lig_r, mol_off, mol_group, poc_x, poc_r, group_off, (int)batch, (int)n_groups, tol, contact,
+  PoseArgs a{{lig_x, mol_off, mol_group, poc_x, group_off, (int)batch, (int)n_groups}, lig_r, poc_r, tol, contact,
              atom_out, mol_out};
   hipLaunchKernelGGL(pose_check_kernel, dim3((unsigned)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
   HIP_TRY(hipGetLastError());
@@ -290,10 +296,9 @@ int dsbdd_vina_score(void* stream, const float* lig_x, const int32_t* lig_code, 
   if (!lig_x || !lig_code || !mol_off || !mol_group || !mol_int || !poc_x || !poc_code || !group_off || !atom_out ||
       !mol_out || !mol_flag)
     return fail(DSBDD_ERR_ARG, "null argument");
-  if (batch < 0 || batch > 0x7fffffff || n_groups < 0 || n_groups > 0x7fffffff)
-    return fail(DSBDD_ERR_ARG, "bad batch or n_groups");
+  if (int rc = check_pair_counts(batch, n_groups)) return rc;
   if (batch == 0) return DSBDD_OK;
-  VinaScoreArgs a{lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_code, group_off, (int)batch, (int)n_groups,
+  VinaScoreArgs a{{lig_x, mol_off, mol_group, poc_x, group_off, (int)batch, (int)n_groups}, lig_code, mol_int, poc_code,
                   atom_out, mol_out, mol_flag};
   hipLaunchKernelGGL(vina_score_kernel, dim3((unsigned)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
   HIP_TRY(hipGetLastError());

@@ -3,39 +3,26 @@
 // atom and its distance; per molecule the totals.  One launch, no host round trip: the sampled coordinates are on the
 // device before a molecule is built.
 //
-// pose_check_kernel: one workgroup per molecule.  The pocket atoms of the molecule's group pass through LDS in tiles of
-// kPoseTile (x, y, z, r as one float4 each: lane j reads 16 contiguous bytes, conflict free); wave w takes the ligand atoms
-// w, w + 4, ..., its lanes stride over the pocket atoms of the tile, a butterfly of wave shuffles folds the lanes.  Neither
-// the molecule nor the group has a size limit below int32: a molecule longer than the workgroup is a longer atom loop, a
-// group larger than a tile is a longer tile loop, and an atom's running record between tiles lives in its output row
-// (written and read back by lane 0 of the one wave that owns the atom).
-// No atomics: every reduction is an integer sum, a minimum, or an arg-min whose ties go to the smallest index -- all of them
-// independent of the order and of the mapping, which is what makes the numpy restatement (_pose_check_host) exact.
-// Every offset and group id read from device memory is range-checked before it is used: what fails the check is an empty
-// molecule / an empty group.
+// pose_check_kernel is pair_sweep (pair_sweep.h: the tiles, the waves, the carry between tiles, the range checks) under
+// PosePolicy; the fourth tile component is the pocket atom's radius.  Every reduction is an integer sum, a minimum, or
+// an arg-min whose ties go to the smallest index -- all of them independent of the order and of the mapping, which is
+// what makes the numpy restatement (_pose_check_host) exact.
 //
-// Arithmetic: float32, every operation rounded to nearest on its own (molecule.h:37-38 names the roundings the same way).
-// The toolkit's __fadd_rn / __fmul_rn are the plain operators and its __fsqrt_rn is the native (approximate) square root
-// unless OCML_BASIC_ROUNDED_OPERATIONS is defined, so here the roundings are enforced: the helpers below are compiled
-// with floating-point contraction off (no fused multiply-add), and the square root is sqrtf, which hipcc rounds correctly.
+// Arithmetic: float32, every operation rounded to nearest on its own (molecule.h:37-38 names the roundings the same way);
+// pair_dist2 and pose_clash_limit are compiled with floating-point contraction off, the root is a correctly rounded sqrtf.
 #pragma once
 #include "common.h"
+#include "pair_sweep.h"
 
 namespace dsbdd {
 
-constexpr int kPoseTile = 1024;     // pocket atoms per LDS tile (16 KiB)
 constexpr int kPoseAtomOut = 4;     // ints per ligand atom: n_clash, n_contact, nearest, bits of the smallest d
 constexpr int kPoseMolOut = 8;      // ints per molecule: n_atoms, clash pairs, clash atoms, contact pairs, contact atoms, nonfinite, bits of the smallest d, 0
 
 struct PoseArgs {
-  const float* lig_x;      // [N][3] Angstrom
+  PairBatch pairs;
   const float* lig_r;      // [N] van-der-Waals radius
-  const int* mol_off;      // [B+1] first row of every molecule (N = mol_off[B])
-  const int* mol_group;    // [B] pocket group of every molecule
-  const float* poc_x;      // [M][3]
   const float* poc_r;      // [M]
-  const int* group_off;    // [G+1] first pocket row of every group (M = group_off[G])
-  int batch, n_groups;
   float tol, contact;
   int* atom_out;           // [N][kPoseAtomOut]
   int* mol_out;            // [B][kPoseMolOut]
@@ -43,11 +30,7 @@ struct PoseArgs {
 
 // d = sqrt((dx dx + dy dy) + dz dz), five roundings and a correctly rounded root
 __device__ inline float pose_distance(float xi, float yi, float zi, float xj, float yj, float zj) {
-#pragma clang fp contract(off)
-  const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
-  const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-  const float s = (xx + yy) + zz;
-  return sqrtf(s);
+  return sqrtf(pair_dist2(xi, yi, zi, xj, yj, zj));
 }
 // (r_i + r_j) - tol
 __device__ inline float pose_clash_limit(float ri, float rj, float tol) {
@@ -55,100 +38,65 @@ __device__ inline float pose_clash_limit(float ri, float rj, float tol) {
   const float sum = ri + rj;
   return sum - tol;
 }
-__device__ inline bool pose_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 // (d, index) records: the smaller d wins, ties go to the smaller index; (+inf, -1) is "none" and never wins
 __device__ inline bool pose_closer(float d, int i, float than_d, int than_i) {
   return d < than_d || (d == than_d && i < than_i);
 }
 
-__global__ __launch_bounds__(kThreads) void pose_check_kernel(PoseArgs p) {
-  constexpr int kWaves = kThreads / 64;
-  __shared__ float4 tile[kPoseTile];
-  __shared__ int part[kWaves][6];
-  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const float inf = __builtin_inff();
-  // the molecule's rows and its group's rows, range-checked against the totals the offset arrays end in
-  const int n_total = p.mol_off[p.batch], m_total = p.group_off[p.n_groups];
-  const int lo = p.mol_off[b], hi = p.mol_off[b + 1];
-  const int n = (lo >= 0 && hi >= lo && hi <= n_total) ? hi - lo : 0;
-  const int g = p.mol_group[b];
-  int glo = 0, m = 0;
-  if (g >= 0 && g < p.n_groups) {
-    glo = p.group_off[g];
-    const int ghi = p.group_off[g + 1];
-    m = (glo >= 0 && ghi >= glo && ghi <= m_total) ? ghi - glo : 0;
+struct PosePolicy {
+  struct Atom { float x, y, z, r; };
+  struct Record { int n_clash, n_contact, near; float best; };
+  struct Total { int sum[4], nonfinite; float min_d; };            // clash pairs, clash atoms, contact pairs, contact atoms
+  const PoseArgs& p;
+  Total* part;             // [kThreads / 64] in LDS
+
+  __device__ static Record zero() { return {0, 0, -1, __builtin_inff()}; }
+  __device__ static Total zero_total() { return {{0, 0, 0, 0}, 0, __builtin_inff()}; }
+  __device__ float tile_word(size_t r) const { return p.poc_r[r]; }
+  __device__ Atom atom(size_t r, float x, float y, float z) const { return {x, y, z, p.lig_r[r]}; }
+  __device__ static bool skip(const Atom&) { return false; }
+  __device__ void pair(Record& c, const Atom& a, const float4 q, int index) const {
+    const float d = pose_distance(a.x, a.y, a.z, q.x, q.y, q.z);
+    c.n_clash += d < pose_clash_limit(a.r, q.w, p.tol);             // strict; false for NaN
+    c.n_contact += d < p.contact;
+    if (d < c.best) { c.best = d; c.near = index; }                 // the index ascends: the first of equal distances stays
   }
-  // totals of the atoms this wave owns (lane 0 keeps them)
-  int w_clash_pairs = 0, w_clash_atoms = 0, w_contact_pairs = 0, w_contact_atoms = 0, w_nonfinite = 0;
-  float w_min = inf;
-  const int n_tiles = m > 0 ? (m - 1) / kPoseTile + 1 : 1;       // an empty group: one pass over an empty tile
-  for (int t = 0; t < n_tiles; ++t) {
-    const int base = t * kPoseTile, cnt = min(kPoseTile, m - base);
-    if (t) __syncthreads();                                       // the previous tile has been read
-    for (int j = tid; j < cnt; j += kThreads) {
-      const size_t r = (size_t)glo + base + j;
-      tile[j] = make_float4(p.poc_x[3 * r], p.poc_x[3 * r + 1], p.poc_x[3 * r + 2], p.poc_r[r]);
-    }
-    __syncthreads();
-    const bool last = t == n_tiles - 1;
-    for (int a = wave; a < n; a += kWaves) {
-      const size_t r = (size_t)lo + a;
-      const float xi = p.lig_x[3 * r], yi = p.lig_x[3 * r + 1], zi = p.lig_x[3 * r + 2], ri = p.lig_r[r];
-      int n_clash = 0, n_contact = 0, near = -1;
-      float best = inf;
-      for (int j = lane; j < cnt; j += 64) {
-        const float4 q = tile[j];
-        const float d = pose_distance(xi, yi, zi, q.x, q.y, q.z);
-        n_clash += d < pose_clash_limit(ri, q.w, p.tol);          // strict; false for NaN
-        n_contact += d < p.contact;
-        if (d < best) { best = d; near = base + j; }              // j ascends: the first of equal distances stays
-      }
-      for (int o = 32; o; o >>= 1) {
-        n_clash += __shfl_xor(n_clash, o);
-        n_contact += __shfl_xor(n_contact, o);
-        const float od = __shfl_xor(best, o);
-        const int oi = __shfl_xor(near, o);
-        if (pose_closer(od, oi, best, near)) { best = od; near = oi; }
-      }
-      if (lane == 0) {
-        int* out = p.atom_out + kPoseAtomOut * r;
-        if (t) {                                                  // the record of the tiles before this one
-          n_clash += out[0];
-          n_contact += out[1];
-          const int pi = out[2];
-          const float pd = __int_as_float(out[3]);
-          if (pose_closer(pd, pi, best, near)) { best = pd; near = pi; }
-        }
-        out[0] = n_clash; out[1] = n_contact; out[2] = near; out[3] = __float_as_int(best);
-        if (last) {
-          w_clash_pairs += n_clash;
-          w_clash_atoms += n_clash > 0;
-          w_contact_pairs += n_contact;
-          w_contact_atoms += n_contact > 0;
-          w_nonfinite |= pose_nonfinite(xi) || pose_nonfinite(yi) || pose_nonfinite(zi);
-          if (best < w_min) w_min = best;
-        }
-      }
-    }
+  __device__ static void join(Record& c, int n_clash, int n_contact, int near, float best) {
+    c.n_clash += n_clash;
+    c.n_contact += n_contact;
+    if (pose_closer(best, near, c.best, c.near)) { c.best = best; c.near = near; }
   }
-  if (lane == 0) {
-    part[wave][0] = w_clash_pairs; part[wave][1] = w_clash_atoms; part[wave][2] = w_contact_pairs;
-    part[wave][3] = w_contact_atoms; part[wave][4] = w_nonfinite; part[wave][5] = __float_as_int(w_min);
+  __device__ static void fold(Record& c, int o) {
+    join(c, __shfl_xor(c.n_clash, o), __shfl_xor(c.n_contact, o), __shfl_xor(c.near, o), __shfl_xor(c.best, o));
   }
-  __syncthreads();
-  if (tid == 0) {
-    int s[5] = {0, 0, 0, 0, 0};
-    float dmin = inf;
-    for (int w = 0; w < kWaves; ++w) {
-      for (int k = 0; k < 4; ++k) s[k] += part[w][k];
-      s[4] |= part[w][4];
-      const float d = __int_as_float(part[w][5]);
-      if (d < dmin) dmin = d;
-    }
+  __device__ void carry(Record& c, size_t r) const {
+    const int* out = p.atom_out + kPoseAtomOut * r;
+    join(c, out[0], out[1], out[2], __int_as_float(out[3]));
+  }
+  __device__ void store(const Record& c, size_t r) const {
+    int* out = p.atom_out + kPoseAtomOut * r;
+    out[0] = c.n_clash; out[1] = c.n_contact; out[2] = c.near; out[3] = __float_as_int(c.best);
+  }
+  __device__ static void merge(Total& s, const Total& o) {
+    for (int k = 0; k < 4; ++k) s.sum[k] += o.sum[k];
+    s.nonfinite |= o.nonfinite;
+    if (o.min_d < s.min_d) s.min_d = o.min_d;
+  }
+  __device__ static void total(Total& w, const Record& c, const Atom& a) {
+    merge(w, {{c.n_clash, c.n_clash > 0, c.n_contact, c.n_contact > 0},
+              pose_nonfinite(a.x) || pose_nonfinite(a.y) || pose_nonfinite(a.z), c.best});
+  }
+  __device__ void finish(int b, int n, const Total& s) const {
     int* out = p.mol_out + (size_t)kPoseMolOut * b;
-    out[0] = n; out[1] = s[0]; out[2] = s[1]; out[3] = s[2]; out[4] = s[3]; out[5] = s[4];
-    out[6] = __float_as_int(dmin); out[7] = 0;
+    out[0] = n; out[1] = s.sum[0]; out[2] = s.sum[1]; out[3] = s.sum[2]; out[4] = s.sum[3]; out[5] = s.nonfinite;
+    out[6] = __float_as_int(s.min_d); out[7] = 0;
   }
+};
+
+__global__ __launch_bounds__(kThreads) void pose_check_kernel(PoseArgs p) {
+  __shared__ PosePolicy::Total part[kThreads / 64];
+  PosePolicy pol{p, part};
+  pair_sweep(p.pairs, pair_rows(p.pairs, blockIdx.x), pol);
 }
 
 }  // namespace dsbdd

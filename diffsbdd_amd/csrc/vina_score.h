@@ -8,26 +8,23 @@
 // atom code; a single bond whose ends both have degree >= 2 is a rotor unless its ends stay connected without it, which
 // a frontier expansion on the masks decides (each atom is expanded at most once per bond).
 //
-// vina_score_kernel: one workgroup per molecule, the loop structure of pose_check_kernel.  The pocket atoms of the
-// molecule's group pass through LDS in tiles of kVinaTile, one float4 {x, y, z, code bits} each; wave w takes the ligand
-// atoms w, w + 4, ..., its lanes stride over the tile, a fixed butterfly of wave shuffles folds the lanes, the running
-// record of an atom between tiles lives in its output row.  No atomics, no size limit below int32 on a molecule or a
-// group, and the order of every sum is a function of the molecule and its group alone: the outputs are bitwise
-// reproducible and do not depend on what else is in the batch.
+// vina_score_kernel: a scan of the molecule's coordinates (one that is not finite ends the workgroup: the flag, and NaN
+// in every float the molecule owns), then pair_sweep (pair_sweep.h: the tiles, the waves, the carry between tiles, the
+// order of every sum) under VinaPolicy; the fourth tile component is the bits of the pocket atom's code, and a ligand
+// atom without a class meets no pocket atom.
 //
-// Arithmetic: the distance r is float32 exactly as pose_distance rounds it, and the pair counts iff r < 8 (decided on
-// r^2 < 64 before the root: a correctly rounded root of a float32 below 64 is below 8).  From r on everything is float64
-// -- the surface distance, the five terms, the lane and wave sums -- and is rounded to float32 where it is stored, so the
-// only error against the float64 restatement (_vina_score_host) beyond those roundings is that of r.
+// Arithmetic: the distance r is the float32 root of pair_dist2, as the pose check rounds it, and the pair counts iff r < 8
+// (decided on r^2 < 64 before the root: a correctly rounded root of a float32 below 64 is below 8).  From r on everything
+// is float64 -- the surface distance, the five terms, the lane and wave sums -- and is rounded to float32 where it is
+// stored, so the only error against the float64 restatement (_vina_score_host) beyond those roundings is that of r.
 // Every offset, group id, type id and code read from device memory is range-checked before it is used.
 #pragma once
 #include "common.h"
 #include "mol_metrics.h"
-#include "pose_check.h"
+#include "pair_sweep.h"
 
 namespace dsbdd {
 
-constexpr int kVinaTile = 1024;     // pocket atoms per LDS tile (16 KiB)
 constexpr int kVinaTerms = 5;       // gauss1, gauss2, repulsion, hydrophobic, hbond
 constexpr int kVinaMolOut = 8;      // floats per molecule: the five sums, inter, score, 0
 constexpr int kVinaMolInt = 4;      // ints per molecule: typed atoms, untyped atoms, rotors, 0
@@ -186,15 +183,10 @@ __global__ __launch_bounds__(64) void vina_type_kernel(VinaTypeArgs p) {
 
 // ---- scoring -------------------------------------------------------------------------------------------------------------
 struct VinaScoreArgs {
-  const float* lig_x;      // [N][3] Angstrom
+  PairBatch pairs;
   const int* lig_code;     // [N]
-  const int* mol_off;      // [B+1]
-  const int* mol_group;    // [B]
   const int* mol_int;      // [B][kVinaMolInt]: the rotors are read
-  const float* poc_x;      // [M][3]
   const int* poc_code;     // [M]
-  const int* group_off;    // [G+1]
-  int batch, n_groups;
   float* atom_out;         // [N][kVinaTerms] unweighted terms
   float* mol_out;          // [B][kVinaMolOut]
   int* mol_flag;           // [B] nonfinite
@@ -213,90 +205,53 @@ __device__ inline void vina_pair_terms(double d, bool hydrophobic, bool hbond, d
   if (hbond) t[4] += d <= -0.7 ? 1.0 : (d < 0.0 ? -d / 0.7 : 0.0);
 }
 
-__global__ __launch_bounds__(kThreads) void vina_score_kernel(VinaScoreArgs p) {
-  constexpr int kWaves = kThreads / 64;
-  __shared__ float4 tile[kVinaTile];
-  __shared__ double part[kWaves][kVinaTerms];
-  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int n_total = p.mol_off[p.batch], m_total = p.group_off[p.n_groups];
-  const int lo = p.mol_off[b], hi = p.mol_off[b + 1];
-  const int n = (lo >= 0 && hi >= lo && hi <= n_total) ? hi - lo : 0;
-  const int g = p.mol_group[b];
-  int glo = 0, m = 0;
-  if (g >= 0 && g < p.n_groups) {
-    glo = p.group_off[g];
-    const int ghi = p.group_off[g + 1];
-    m = (glo >= 0 && ghi >= glo && ghi <= m_total) ? ghi - glo : 0;
+// every sum in float64, in the order pair_sweep fixes; the tiles before join before the store rounds, `inter` in term order
+struct VinaPolicy {
+  struct Atom { float x, y, z; int code, cls; double radius; };
+  struct Record { double t[kVinaTerms]; };     // walked by fully unrolled loops only: it stays in registers
+  using Total = Record;
+  const VinaScoreArgs& p;
+  Total* part;             // [kThreads / 64] in LDS
+
+  __device__ static Record zero() { return {{0, 0, 0, 0, 0}}; }
+  __device__ static Total zero_total() { return zero(); }
+  __device__ float tile_word(size_t r) const { return __int_as_float(p.poc_code[r]); }
+  __device__ Atom atom(size_t r, float x, float y, float z) const {
+    const int code = p.lig_code[r], cls = vina_class_of(code);
+    return {x, y, z, code, cls, vina_radius(cls)};
   }
-  float* mol = p.mol_out + (size_t)kVinaMolOut * b;
-  // a molecule with a coordinate that is not finite: the flag, and NaN in every float it owns
-  int bad = 0;
-  for (int k = tid; k < 3 * n; k += kThreads) bad |= pose_nonfinite(p.lig_x[3 * (size_t)lo + k]);
-  if (__syncthreads_or(bad)) {
-    const float nan = __builtin_nanf("");
-    for (int k = tid; k < kVinaTerms * n; k += kThreads) p.atom_out[kVinaTerms * (size_t)lo + k] = nan;
-    if (tid < kVinaMolOut) mol[tid] = nan;
-    if (tid == 0) p.mol_flag[b] = 1;
-    return;
+  __device__ static bool skip(const Atom& a) { return a.cls == kVinaNone; }
+  __device__ static void pair(Record& acc, const Atom& a, const float4 q, int) {
+    const int cj = __float_as_int(q.w), kj = vina_class_of(cj);
+    if (kj == kVinaNone) return;
+    const float s = pair_dist2(a.x, a.y, a.z, q.x, q.y, q.z);
+    if (!(s < 64.0f)) return;                                       // r < 8, strictly; false for NaN
+    const double d = (double)sqrtf(s) - a.radius - vina_radius(kj);
+    const bool hyd = (a.code & cj & kVinaHydrophobic) != 0;
+    const bool hb = ((a.code & kVinaDonor) && (cj & kVinaAcceptor)) || ((a.code & kVinaAcceptor) && (cj & kVinaDonor));
+    vina_pair_terms(d, hyd, hb, acc.t);
   }
-  double w_sum[kVinaTerms] = {0, 0, 0, 0, 0};                      // totals of the atoms this wave owns (lane 0 keeps them)
-  const int n_tiles = m > 0 ? (m - 1) / kVinaTile + 1 : 1;         // an empty group: one pass over an empty tile
-  for (int t = 0; t < n_tiles; ++t) {
-    const int base = t * kVinaTile, cnt = min(kVinaTile, m - base);
-    if (t) __syncthreads();                                        // the previous tile has been read
-    for (int j = tid; j < cnt; j += kThreads) {
-      const size_t r = (size_t)glo + base + j;
-      tile[j] = make_float4(p.poc_x[3 * r], p.poc_x[3 * r + 1], p.poc_x[3 * r + 2], __int_as_float(p.poc_code[r]));
-    }
-    __syncthreads();
-    const bool last = t == n_tiles - 1;
-    for (int a = wave; a < n; a += kWaves) {
-      const size_t r = (size_t)lo + a;
-      const float xi = p.lig_x[3 * r], yi = p.lig_x[3 * r + 1], zi = p.lig_x[3 * r + 2];
-      const int ci = p.lig_code[r], ki = vina_class_of(ci);
-      double acc[kVinaTerms] = {0, 0, 0, 0, 0};
-      if (ki != kVinaNone) {
-        const double ri = vina_radius(ki);
-        for (int j = lane; j < cnt; j += 64) {
-          const float4 q = tile[j];
-          const int cj = __float_as_int(q.w), kj = vina_class_of(cj);
-          if (kj == kVinaNone) continue;
-          float s;
-          {
-#pragma clang fp contract(off)
-            const float dx = xi - q.x, dy = yi - q.y, dz = zi - q.z;
-            const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-            s = (xx + yy) + zz;
-          }
-          if (!(s < 64.0f)) continue;                               // r < 8, strictly; false for NaN
-          const double d = (double)sqrtf(s) - ri - vina_radius(kj);
-          const bool hyd = (ci & cj & kVinaHydrophobic) != 0;
-          const bool hb = ((ci & kVinaDonor) && (cj & kVinaAcceptor)) || ((ci & kVinaAcceptor) && (cj & kVinaDonor));
-          vina_pair_terms(d, hyd, hb, acc);
-        }
-        for (int o = 32; o; o >>= 1)
-          for (int k = 0; k < kVinaTerms; ++k) acc[k] += __shfl_xor(acc[k], o);
-      }
-      if (lane == 0) {
-        float* out = p.atom_out + kVinaTerms * r;
-        for (int k = 0; k < kVinaTerms; ++k) {
-          if (t) acc[k] += (double)out[k];                          // the record of the tiles before this one
-          out[k] = (float)acc[k];
-          if (last) w_sum[k] += acc[k];
-        }
-      }
-    }
+  __device__ static void fold(Record& acc, int o) {
+    for (int k = 0; k < kVinaTerms; ++k) acc.t[k] += __shfl_xor(acc.t[k], o);
   }
-  if (lane == 0)
-    for (int k = 0; k < kVinaTerms; ++k) part[wave][k] = w_sum[k];
-  __syncthreads();
-  if (tid == 0) {
+  __device__ void carry(Record& acc, size_t r) const {
+    const float* out = p.atom_out + kVinaTerms * r;
+    for (int k = 0; k < kVinaTerms; ++k) acc.t[k] += (double)out[k];
+  }
+  __device__ void store(const Record& acc, size_t r) const {
+    float* out = p.atom_out + kVinaTerms * r;
+    for (int k = 0; k < kVinaTerms; ++k) out[k] = (float)acc.t[k];
+  }
+  __device__ static void merge(Total& s, const Total& o) {
+    for (int k = 0; k < kVinaTerms; ++k) s.t[k] += o.t[k];
+  }
+  __device__ static void total(Total& w, const Record& acc, const Atom&) { merge(w, acc); }
+  __device__ void finish(int b, int, const Total& s) const {
+    float* mol = p.mol_out + (size_t)kVinaMolOut * b;
     double inter = 0.0;
     for (int k = 0; k < kVinaTerms; ++k) {
-      double s = 0.0;
-      for (int w = 0; w < kWaves; ++w) s += part[w][k];
-      mol[k] = (float)s;
-      inter += kVinaWeight[k] * s;
+      mol[k] = (float)s.t[k];
+      inter += kVinaWeight[k] * s.t[k];
     }
     const int n_rot = max(p.mol_int[(size_t)kVinaMolInt * b + 2], 0);
     mol[5] = (float)inter;
@@ -304,6 +259,24 @@ __global__ __launch_bounds__(kThreads) void vina_score_kernel(VinaScoreArgs p) {
     mol[7] = 0.0f;
     p.mol_flag[b] = 0;
   }
+};
+
+__global__ __launch_bounds__(kThreads) void vina_score_kernel(VinaScoreArgs p) {
+  __shared__ VinaPolicy::Total part[kThreads / 64];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const PairRows rows = pair_rows(p.pairs, b);
+  // a molecule with a coordinate that is not finite: the flag, and NaN in every float it owns
+  int bad = 0;
+  for (int k = tid; k < 3 * rows.n; k += kThreads) bad |= pose_nonfinite(p.pairs.lig_x[3 * (size_t)rows.lo + k]);
+  if (__syncthreads_or(bad)) {
+    const float nan = __builtin_nanf("");
+    for (int k = tid; k < kVinaTerms * rows.n; k += kThreads) p.atom_out[kVinaTerms * (size_t)rows.lo + k] = nan;
+    if (tid < kVinaMolOut) p.mol_out[(size_t)kVinaMolOut * b + tid] = nan;
+    if (tid == 0) p.mol_flag[b] = 1;
+    return;
+  }
+  VinaPolicy pol{p, part};
+  pair_sweep(p.pairs, rows, pol);
 }
 
 }  // namespace dsbdd

@@ -208,10 +208,8 @@ class LigandGenerator:
         xh_lig, lig_mask = self.sample_for_pocket(pocket, n_samples, num_nodes_lig, timesteps,
                                                   n_nodes_bias, n_nodes_min, **kwargs)
         x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
-        stats = None if pose is None else self._pose_stats(x, atom_type, lig_mask, [residues], [n_samples], pose)
-        scores = None if vina is None else self._vina_stats(x, atom_type, lig_mask, [residues], [n_samples])
         return build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=n_samples,
-                               pose=stats, vina=scores)
+                               **self._annotate(x, atom_type, lig_mask, [residues], [n_samples], pose, vina))
 
     def _drop_virtual(self, xh_lig, lig_mask):
         """(x, atom_type, lig_mask) of the generated atoms; with virtual nodes the atoms of the virtual class are
@@ -239,29 +237,6 @@ class LigandGenerator:
         opts.setdefault("contact", pose_mod.CONTACT_CUTOFF)
         return opts
 
-    def _pose_pocket(self, residues):
-        """Heavy atoms of a job's residues as a one-group `pose.PocketAtoms` on the device: uploaded once per residue
-        list (a test-set job hands the same list to every one of its batches) and kept while the list lives here."""
-        from . import pose as pose_mod
-        cache = self.__dict__.setdefault("_pose_pockets", {})
-        hit = cache.get(id(residues))
-        if hit is None or hit[0] is not residues:
-            while len(cache) >= 256:
-                cache.pop(next(iter(cache)))
-            hit = (residues, pose_mod.PocketAtoms.upload([pose_mod.pocket_atoms(residues)], self.device))
-            cache[id(residues)] = hit
-        return hit[1]
-
-    def _pose_stats(self, x, atom_type, lig_mask, residue_sets, counts, opts):
-        """`pose.pose_check` of a sampled batch (after `_drop_virtual`): one group per job, `counts[k]` samples on group k."""
-        from . import pose as pose_mod
-        if "_pose_radii" not in self.__dict__:
-            self._pose_radii = torch.as_tensor(pose_mod.radius_table(self.lig_type_decoder), device=self.device)
-        pockets = pose_mod.PocketAtoms.concat([self._pose_pocket(r) for r in residue_sets])
-        groups = np.repeat(np.arange(len(counts)), counts)
-        return pose_mod.pose_check(x, self._pose_radii[atom_type], lig_mask, pockets, groups, batch=int(sum(counts)),
-                                   tol=opts["tol"], contact=opts["contact"])
-
     # -- Vina-type score of the sampled batch (vina.py): only with the samplers' `vina=` option -----------------------------
     @staticmethod
     def _vina_options(vina):
@@ -275,25 +250,50 @@ class LigandGenerator:
             raise ValueError(f"vina: unknown option(s) {sorted(unknown)}")
         return opts
 
-    def _vina_pocket(self, residues):
-        """Typed heavy atoms of a job's residues as a one-group `vina.VinaPocket` on the device: typed and uploaded once per
-        residue list, as `_pose_pocket`."""
-        from . import vina as vina_mod
-        cache = self.__dict__.setdefault("_vina_pockets", {})
-        hit = cache.get(id(residues))
-        if hit is None or hit[0] is not residues:
-            while len(cache) >= 256:
-                cache.pop(next(iter(cache)))
-            hit = (residues, vina_mod.VinaPocket.upload([vina_mod.type_pocket(residues)], self.device))
-            cache[id(residues)] = hit
-        return hit[1]
+    def _job_pockets(self, attr, residue_sets, kind, atoms_of):
+        """The heavy atoms of every job's residues as one `kind` (`pose.PocketAtoms` / `vina.VinaPocket`) on the device, one
+        group per job.  A residue list is read by `atoms_of` and uploaded once (a test-set job hands the same list to every
+        one of its batches) and kept in the dict `attr` while the list lives here."""
+        cache = self.__dict__.setdefault(attr, {})
+        parts = []
+        for residues in residue_sets:
+            hit = cache.get(id(residues))
+            if hit is None or hit[0] is not residues:
+                while len(cache) >= 256:
+                    cache.pop(next(iter(cache)))
+                hit = (residues, kind.upload([atoms_of(residues)], self.device))
+                cache[id(residues)] = hit
+            parts.append(hit[1])
+        return kind.concat(parts)
 
-    def _vina_stats(self, x, atom_type, lig_mask, residue_sets, counts):
-        """`vina.vina_score` of a sampled batch (after `_drop_virtual`): one group per job, `counts[k]` samples on group k."""
-        from . import vina as vina_mod
-        pockets = vina_mod.VinaPocket.concat([self._vina_pocket(r) for r in residue_sets])
-        groups = np.repeat(np.arange(len(counts)), counts)
-        return vina_mod.vina_score(x, atom_type, lig_mask, pockets, self.dataset_info, groups, batch=int(sum(counts)))
+    def _annotate(self, x, atom_type, lig_mask, residue_sets, counts, pose, vina):
+        """The records of a sampled batch (after `_drop_virtual`) that `build_molecules` attaches: `pose.pose_check` and
+        `vina.vina_score`, each only with its option; one group per job, `counts[k]` samples on group k.  `residue_sets`
+        None: the one list an option carries as 'residues'.  -> dict(pose=..., vina=...), None where off."""
+        out = dict(pose=None, vina=None)
+        groups, batch = np.repeat(np.arange(len(counts)), counts), int(sum(counts))
+        if pose is not None:
+            from . import pose as pose_mod
+            if "_pose_radii" not in self.__dict__:
+                self._pose_radii = torch.as_tensor(pose_mod.radius_table(self.lig_type_decoder), device=self.device)
+            sets = [pose["residues"]] if residue_sets is None else residue_sets
+            pockets = self._job_pockets("_pose_pockets", sets, pose_mod.PocketAtoms, pose_mod.pocket_atoms)
+            out["pose"] = pose_mod.pose_check(x, self._pose_radii[atom_type], lig_mask, pockets, groups, batch=batch,
+                                              tol=pose["tol"], contact=pose["contact"])
+        if vina is not None:
+            from . import vina as vina_mod
+            sets = [vina["residues"]] if residue_sets is None else residue_sets
+            pockets = self._job_pockets("_vina_pockets", sets, vina_mod.VinaPocket, vina_mod.type_pocket)
+            out["vina"] = vina_mod.vina_score(x, atom_type, lig_mask, pockets, self.dataset_info, groups, batch=batch)
+        return out
+
+    def _scope_residues(self, pdb_file, scope, pocket_ids, ref_ligand):
+        """scope 'protein': every ATOM residue of the file; 'pocket': the selection of `generate_ligands`."""
+        if scope == "pocket":
+            return self.select_pocket_residues(pdb_file, pocket_ids, ref_ligand)
+        if scope == "protein":
+            return pocket_io.read_pdb_residues(pdb_file)
+        raise ValueError("scope must be 'protein' or 'pocket'")
 
     @torch.no_grad()
     def vina_scores(self, pdb_file, molecules, pocket_ids=None, ref_ligand=None, scope="protein"):
@@ -302,12 +302,7 @@ class LigandGenerator:
         {'n_atoms', 'untyped', 'n_rot', 'nonfinite', 'gauss1', 'gauss2', 'repulsion', 'hydrophobic', 'hbond', 'inter',
         'score'} over heavy atoms.  Not smina output: see `vina.VINA_COVERAGE`."""
         from . import vina as vina_mod
-        if scope == "pocket":
-            residues = self.select_pocket_residues(pdb_file, pocket_ids, ref_ligand)
-        elif scope == "protein":
-            residues = pocket_io.read_pdb_residues(pdb_file)
-        else:
-            raise ValueError("scope must be 'protein' or 'pocket'")
+        residues = self._scope_residues(pdb_file, scope, pocket_ids, ref_ligand)
         pockets = vina_mod.VinaPocket.upload([vina_mod.type_pocket(residues)], self.device)
         return [r.as_dict() for r in vina_mod.score_molecules(molecules, pockets, self.dataset_info)]
 
@@ -319,12 +314,7 @@ class LigandGenerator:
         Returns one dict per molecule, in order: {'n_atoms', 'clash_pairs', 'clash_atoms', 'contact_pairs',
         'contact_atoms', 'nonfinite', 'min_distance'} over heavy atoms."""
         from . import pose as pose_mod
-        if scope == "pocket":
-            residues = self.select_pocket_residues(pdb_file, pocket_ids, ref_ligand)
-        elif scope == "protein":
-            residues = pocket_io.read_pdb_residues(pdb_file)
-        else:
-            raise ValueError("scope must be 'protein' or 'pocket'")
+        residues = self._scope_residues(pdb_file, scope, pocket_ids, ref_ligand)
         pockets = pose_mod.PocketAtoms.upload([pose_mod.pocket_atoms(residues)], self.device)
         records = pose_mod.check_molecules(molecules, pockets, tol=pose_mod.CLASH_TOLERANCE if tol is None else tol,
                                            contact=pose_mod.CONTACT_CUTOFF if contact is None else contact)
@@ -410,10 +400,8 @@ class LigandGenerator:
         xh_lig, lig_mask = self.sample_for_pocket(pocket, base, torch.cat(sizes), timesteps,
                                                   n_nodes_bias, n_nodes_min, **kwargs)
         x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
-        stats = None if pose is None else self._pose_stats(x, atom_type, lig_mask, [j[0] for j in jobs], counts, pose)
-        scores = None if vina is None else self._vina_stats(x, atom_type, lig_mask, [j[0] for j in jobs], counts)
-        mols = build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=base, pose=stats,
-                               vina=scores)
+        mols = build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=base,
+                               **self._annotate(x, atom_type, lig_mask, [j[0] for j in jobs], counts, pose, vina))
         out, o = [], 0
         for n in counts:
             out.append(mols[o:o + n])
@@ -567,10 +555,8 @@ class LigandGenerator:
         finally:
             self.ddpm.cone_mode, self.ddpm.edge_granule16 = saved
         x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
-        stats = None if pose is None else self._pose_stats(x, atom_type, lig_mask, [j[0] for j in jobs], counts, pose)
-        scores = None if vina is None else self._vina_stats(x, atom_type, lig_mask, [j[0] for j in jobs], counts)
-        mols = build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=base, pose=stats,
-                               vina=scores)
+        mols = build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=base,
+                               **self._annotate(x, atom_type, lig_mask, [j[0] for j in jobs], counts, pose, vina))
         out, o = [], 0
         for n in counts:
             out.append(mols[o:o + n])
@@ -616,10 +602,8 @@ class LigandGenerator:
             self.ddpm.seed(seed)
         xh_lig, lig_mask = self._diversify_chain(pocket, ligand, noising_steps)
         x, atom_type, lig_mask = self._drop_virtual(xh_lig, lig_mask)
-        stats = None if pose is None else self._pose_stats(x, atom_type, lig_mask, [pose["residues"]], [n], pose)
-        scores = None if vina is None else self._vina_stats(x, atom_type, lig_mask, [vina["residues"]], [n])
-        return build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=n, pose=stats,
-                               vina=scores)
+        return build_molecules(x, atom_type, lig_mask, self.dataset_info, largest_frag=largest_frag, batch=n,
+                               **self._annotate(x, atom_type, lig_mask, None, [n], pose, vina))
 
     # -- scoring given ligands (score.py) ---------------------------------------------------------------------
     @torch.no_grad()

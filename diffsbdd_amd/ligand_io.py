@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._pairs import sdf_records
 
 
 # --------------------------------------------------------------------------- files
@@ -29,19 +30,8 @@ def read_sdf_molecules(path):
 
     Like `Chem.SDMolSupplier(path, sanitize=False)` read for positions and symbols: no sanitisation, hydrogens stay,
     bonds and properties are ignored.  A record is the text up to a `$$$$` line; the counts line is its fourth."""
-    with open(path) as f:
-        lines = f.read().splitlines()
-    records, cur = [], []
-    for line in lines:
-        if line.startswith("$$$$"):
-            records.append(cur)
-            cur = []
-        else:
-            cur.append(line)
-    if any(l.strip() for l in cur):          # a single mol block without the record separator
-        records.append(cur)
     out = []
-    for k, rec in enumerate(records):
+    for k, rec in enumerate(sdf_records(path)):
         if len(rec) < 4 or "V2000" not in rec[3]:
             raise ValueError(f"{path}: record {k} is not a V2000 mol block")
         n_atoms = int(rec[3][0:3])

@@ -29,13 +29,13 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _pairs
+from ._pairs import HYDROGENS, _default_groups, _checked_groups, _np, _ptr, _symbol, select_residues  # noqa: F401
 
 # van-der-Waals radii in Angstrom: Bondi (1964); B from Mantina et al. (2009)
 VDW_RADII = {"C": 1.70, "N": 1.55, "O": 1.52, "F": 1.47, "P": 1.80, "S": 1.80, "Cl": 1.75, "Br": 1.85, "I": 1.98,
              "B": 1.92, "Se": 1.90}
 DEFAULT_RADIUS = 2.00                 # every other element
-HYDROGENS = ("H", "D")                # dropped on both sides
 CLASH_TOLERANCE = 0.5
 CONTACT_CUTOFF = 4.0
 
@@ -57,15 +57,6 @@ POSE_COVERAGE = (
     "4.0 A; "
     "NOT = a docking score, an energy or a strain measure, and NOT comparable with PoseBusters or PoseCheck numbers "
     "(different atoms, radii and hydrogens); ABSENT = RDKit/UFF relaxation and external docking (refused).")
-
-
-def _np(v):
-    return v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
-
-
-def _symbol(s):
-    s = str(s).strip()
-    return s[:1].upper() + s[1:].lower()
 
 
 def radii_of(symbols):
@@ -197,61 +188,9 @@ class PoseStats:
 
 
 # ---- the device path -------------------------------------------------------------------------------------------------------
-class PocketAtoms:
-    """Pocket heavy atoms on the device, one group per pocket: x [M,3] float32, r [M] float32, group_off int32 [G+1]
-    (`offsets`: the same on the host).  Upload once, use for many batches."""
-
-    def __init__(self, x, r, offsets):
-        self.x, self.r = x, r
-        self.offsets = np.asarray(offsets, np.int64).reshape(-1)
-        if self.offsets[0] != 0 or np.any(np.diff(self.offsets) < 0) or self.offsets[-1] != x.shape[0] or \
-                r.shape[0] != x.shape[0] or self.offsets[-1] >= 2 ** 31:
-            raise ValueError("PocketAtoms: offsets must ascend from 0 to the number of rows")
-        self.group_off = torch.as_tensor(self.offsets.astype(np.int32), device=x.device)
-
-    n_groups = property(lambda self: len(self.offsets) - 1)
-
-    @classmethod
-    def upload(cls, pockets, device):
-        """`pockets`: list of (xyz [m,3], radii [m]) host arrays, one per group."""
-        xs = [np.asarray(p[0], np.float32).reshape(-1, 3) for p in pockets]
-        rs = [np.asarray(p[1], np.float32).reshape(-1) for p in pockets]
-        if any(len(a) != len(b) for a, b in zip(xs, rs)):
-            raise ValueError("a pocket needs one radius per atom")
-        x = np.concatenate(xs) if xs else np.zeros((0, 3), np.float32)
-        r = np.concatenate(rs) if rs else np.zeros(0, np.float32)
-        return cls(torch.as_tensor(x, device=device), torch.as_tensor(r, device=device),
-                   np.concatenate([[0], np.cumsum([len(a) for a in xs])]))
-
-    @classmethod
-    def concat(cls, parts):
-        """The groups of several `PocketAtoms` one after the other (a copy on the device, no upload of atoms)."""
-        parts = list(parts)
-        if len(parts) == 1:
-            return parts[0]
-        sizes = np.concatenate([np.diff(p.offsets) for p in parts])
-        return cls(torch.cat([p.x for p in parts]), torch.cat([p.r for p in parts]), np.concatenate([[0], np.cumsum(sizes)]))
-
-
-def _n_molecules(lig_mask, batch):
-    return int(batch) if batch is not None else (int(lig_mask.max()) + 1 if len(lig_mask) else 0)
-
-
-def _default_groups(n_mols, n_groups):
-    if n_groups == 1:
-        return np.zeros(n_mols, np.int64)
-    if n_groups == n_mols:
-        return np.arange(n_mols, dtype=np.int64)
-    raise ValueError(f"mol_group is needed: {n_mols} molecules and {n_groups} pocket groups")
-
-
-def _checked_groups(mol_group, n_mols, n_groups):
-    g = np.asarray(_np(mol_group), np.int64).reshape(-1)
-    if len(g) != n_mols:
-        raise ValueError(f"{len(g)} group ids for {n_mols} molecules")
-    if len(g) and (g.min() < 0 or g.max() >= n_groups):
-        raise ValueError(f"mol_group outside [0, {n_groups})")
-    return g
+class PocketAtoms(_pairs.PocketGroups):
+    """`_pairs.PocketGroups` with the van-der-Waals radii r [M] float32; `upload` takes (xyz [m,3], radii [m]) per group."""
+    COLUMN, DTYPE, WHAT = "r", np.float32, "radius"
 
 
 def radius_table(atom_decoder):
@@ -259,11 +198,6 @@ def radius_table(atom_decoder):
     if any(_symbol(s) in HYDROGENS for s in atom_decoder):
         raise ValueError("the atom decoder holds hydrogens: pose checks are defined on heavy atoms (drop them and pass radii)")
     return radii_of(atom_decoder)
-
-
-def _ptr(t):
-    """data pointer of a tensor; an empty one gets a one-element stand-in (the C entry refuses null)."""
-    return (t if t.numel() else torch.zeros(4, dtype=t.dtype, device=t.device)).data_ptr()
 
 
 def pose_check(x, atom_type_or_radii, lig_mask, pockets, mol_group=None, batch=None, tol=CLASH_TOLERANCE,
@@ -300,19 +234,10 @@ def pose_check(x, atom_type_or_radii, lig_mask, pockets, mol_group=None, batch=N
         radii = table[torch.as_tensor(v, device=dev).to(torch.int64).reshape(-1)].contiguous()
     if radii.shape[0] != N or lig_mask.shape[0] != N:
         raise ValueError(f"{N} coordinates, {radii.shape[0]} radii / types, {lig_mask.shape[0]} mask entries")
-    B = _n_molecules(lig_mask, batch)
-    sizes = torch.bincount(lig_mask.to(dev), minlength=B)
-    off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-    off[1:] = torch.cumsum(sizes, 0).to(torch.int32)
+    B = _pairs._n_molecules(lig_mask, batch)
+    off = _pairs.mol_offsets(lig_mask, B, dev)
     G = pockets.n_groups
-    if mol_group is None:
-        mol_group = _default_groups(B, G)
-    if torch.is_tensor(mol_group) and mol_group.is_cuda:        # device data: the kernel range-checks it
-        if mol_group.numel() != B:
-            raise ValueError(f"{mol_group.numel()} group ids for {B} molecules")
-        groups = mol_group.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-    else:
-        groups = torch.as_tensor(_checked_groups(mol_group, B, G).astype(np.int32), device=dev)
+    groups = _pairs.device_groups(mol_group, B, G, dev)
     i32 = dict(dtype=torch.int32, device=dev)
     out = PoseStats(torch.zeros((N, ATOM_OUT), **i32), torch.zeros((B, MOL_OUT), **i32), off, x, tol, contact)
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -333,10 +258,8 @@ def as_ligands(molecules):
 
 def _pack(ligands):
     """list of (xyz, radii, ...) -> (x [N,3] float32, r [N] float32, lig_mask [N] int64) on the host."""
-    xs = [np.asarray(l[0], np.float32).reshape(-1, 3) for l in ligands]
-    x = np.concatenate(xs) if xs else np.zeros((0, 3), np.float32)
-    r = np.concatenate([np.asarray(l[1], np.float32).reshape(-1) for l in ligands]) if xs else np.zeros(0, np.float32)
-    mask = np.repeat(np.arange(len(xs), dtype=np.int64), [len(a) for a in xs])
+    x, mask, _ = _pairs.pack_ligands(ligands)
+    r = np.concatenate([np.asarray(l[1], np.float32).reshape(-1) for l in ligands]) if ligands else np.zeros(0, np.float32)
     return x, r, mask
 
 
@@ -443,52 +366,15 @@ CSV_COLUMNS = ("n_atoms", "clash_pairs", "clash_atoms", "contact_pairs", "contac
 
 def write_csv(path, rows):
     """rows: (source, index, MolPose or its dict); `path` None writes to stdout."""
-    lines = [",".join(("source", "index") + CSV_COLUMNS)]
-    for source, k, rec in rows:
-        rec = rec.as_dict() if hasattr(rec, "as_dict") else rec
-        lines.append(",".join([str(source), str(k)] + [repr(rec[c]) if c == "min_distance" else str(rec[c])
-                                                       for c in CSV_COLUMNS]))
-    if path is None:
-        sys.stdout.write("\n".join(lines) + "\n")
-        return
-    with open(path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-
-
-def select_residues(pdb_file, scope="protein", ref_ligand=None):
-    """The protein atoms to check: every ATOM residue of the file (`protein`), or the residues within 8 A of `ref_ligand`
-    (an SDF path or `<chain>:<resi>` of the file) as `generate_ligands` selects them (`pocket`)."""
-    from . import pocket as pocket_io
-    if scope == "protein":
-        return pocket_io.read_pdb_residues(pdb_file)
-    if scope != "pocket":
-        raise ValueError("scope must be 'protein' or 'pocket'")
-    if ref_ligand is None:
-        raise ValueError("scope 'pocket' needs ref_ligand")
-    residues = pocket_io.read_pdb_residues(pdb_file, hetero=True)
-    skip = None
-    if str(ref_ligand).endswith(".sdf"):
-        lig_xyz = pocket_io.read_sdf_coords(ref_ligand)
-    else:
-        from .ligand_io import ligand_atoms_from_pdb
-        lig_xyz, _ = ligand_atoms_from_pdb(residues, ref_ligand)
-        skip = int(str(ref_ligand).split(":")[1])
-    return pocket_io.pocket_residues_from_ligand([r for r in residues if r["resseq"] != skip], lig_xyz)
+    _pairs.write_csv(path, rows, CSV_COLUMNS)
 
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Clash and contact counts of written ligands against a protein (one row per molecule)")
-    p.add_argument("--pdbfile", required=True)
-    p.add_argument("--sdf", nargs="+", required=True)
-    p.add_argument("--scope", choices=("protein", "pocket"), default="protein")
-    p.add_argument("--ref_ligand", default=None, help="SDF file or <chain>:<resi>: the pocket of --scope pocket")
+    _pairs.add_complex_arguments(p)
     p.add_argument("--tol", type=float, default=CLASH_TOLERANCE)
     p.add_argument("--contact", type=float, default=CONTACT_CUTOFF)
-    p.add_argument("--out", default=None)
-    p.add_argument("--device", default="cuda")
-    a = p.parse_args(argv)
-    if a.scope == "pocket" and a.ref_ligand is None:
-        p.error("--scope pocket needs --ref_ligand")
+    a = _pairs.parse_complex_arguments(p, argv)
     try:
         _check_thresholds(a.tol, a.contact)
     except ValueError as exc:

@@ -37,8 +37,8 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
-from .pose import HYDROGENS, _checked_groups, _default_groups, _n_molecules, _np, _ptr, _symbol, select_residues
+from . import _lib, _pairs
+from ._pairs import HYDROGENS, _n_molecules, _np, _ptr, _symbol, select_residues
 
 # ---- constants -------------------------------------------------------------------------------------------------------------
 CLASSES = ("", "C", "N", "O", "P", "S", "F", "Cl", "Br", "I", "metal")           # class id = index; 0 = untyped
@@ -51,7 +51,7 @@ WEIGHTS = (-0.035579, -0.005156, 0.840245, -0.035069, -0.587439)                
 ROT_WEIGHT = 0.05846
 CUTOFF = 8.0
 TERMS = ("gauss1", "gauss2", "repulsion", "hydrophobic", "hbond")
-TILE = 1024                           # pocket atoms per LDS tile of vina_score_kernel (kVinaTile)
+TILE = 1024                           # pocket atoms per LDS tile of vina_score_kernel (kPairTile, csrc/pair_sweep.h)
 ATOM_OUT, MOL_OUT, MOL_INT = 5, 8, 4  # columns of the kernels' outputs
 M_INTER, M_SCORE = 5, 6
 I_TYPED, I_UNTYPED, I_ROT = 0, 1, 2
@@ -289,43 +289,26 @@ def type_pocket(residues):
     return TypedPocket(np.asarray(xyz, np.float32).reshape(-1, 3), np.asarray(codes, np.int32), untemplated)
 
 
-class VinaPocket:
-    """Typed pocket heavy atoms on the device, one group per pocket: x [M,3] float32, code [M] int32, group_off int32
-    [G+1] (`offsets`: the same on the host).  Upload once, use for many batches."""
+class VinaPocket(_pairs.PocketGroups):
+    """`_pairs.PocketGroups` with the atom codes code [M] int32 and, per group, how many atoms were typed by element alone
+    (`untemplated`)."""
+    COLUMN, DTYPE, WHAT = "code", np.int32, "code"
 
     def __init__(self, x, code, offsets, untemplated=()):
-        self.x, self.code = x, code
-        self.offsets = np.asarray(offsets, np.int64).reshape(-1)
-        if self.offsets[0] != 0 or np.any(np.diff(self.offsets) < 0) or self.offsets[-1] != x.shape[0] or \
-                code.shape[0] != x.shape[0] or self.offsets[-1] >= 2 ** 31:
-            raise ValueError("VinaPocket: offsets must ascend from 0 to the number of rows")
+        super().__init__(x, code, offsets)
         self.untemplated = list(untemplated)
-        self.group_off = torch.as_tensor(self.offsets.astype(np.int32), device=x.device)
-
-    n_groups = property(lambda self: len(self.offsets) - 1)
 
     @classmethod
     def upload(cls, pockets, device):
         """`pockets`: list of `TypedPocket` or (xyz [m,3], code [m]) host arrays, one per group."""
         pockets = list(pockets)
-        xs = [np.asarray(p[0] if not isinstance(p, TypedPocket) else p.x, np.float32).reshape(-1, 3) for p in pockets]
-        cs = [np.asarray(p[1] if not isinstance(p, TypedPocket) else p.code, np.int32).reshape(-1) for p in pockets]
-        if any(len(a) != len(b) for a, b in zip(xs, cs)):
-            raise ValueError("a pocket needs one code per atom")
-        x = np.concatenate(xs) if xs else np.zeros((0, 3), np.float32)
-        c = np.concatenate(cs) if cs else np.zeros(0, np.int32)
-        return cls(torch.as_tensor(x, device=device), torch.as_tensor(c, device=device),
-                   np.concatenate([[0], np.cumsum([len(a) for a in xs])]), [getattr(p, "untemplated", 0) for p in pockets])
+        return super().upload([(p.x, p.code) if isinstance(p, TypedPocket) else p for p in pockets], device,
+                              [getattr(p, "untemplated", 0) for p in pockets])
 
     @classmethod
     def concat(cls, parts):
-        """The groups of several `VinaPocket` one after the other (a copy on the device, no upload of atoms)."""
         parts = list(parts)
-        if len(parts) == 1:
-            return parts[0]
-        sizes = np.concatenate([np.diff(p.offsets) for p in parts])
-        return cls(torch.cat([p.x for p in parts]), torch.cat([p.code for p in parts]), np.concatenate([[0], np.cumsum(sizes)]),
-                   sum((p.untemplated for p in parts), []))
+        return super().concat(parts, sum((p.untemplated for p in parts), []))
 
 
 # ---- results -------------------------------------------------------------------------------------------------------------------
@@ -400,13 +383,6 @@ class VinaScores:
 
 
 # ---- the device path ---------------------------------------------------------------------------------------------------------
-def _offsets(lig_mask, B, dev):
-    sizes = torch.bincount(lig_mask.to(dev), minlength=B)
-    off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-    off[1:] = torch.cumsum(sizes, 0).to(torch.int32)
-    return off
-
-
 def type_ligands(x, atom_type, lig_mask, info, orders=None, batch=None):
     """Atom codes and rotor counts of a batch on the device: `molecules.bond_orders` (unless `orders` int8 [B, n_max, n_max]
     is given, n_max <= 128) then one launch of `dsbdd_vina_type`.  x [N,3], atom_type [N] class ids of `info`'s atom
@@ -425,7 +401,7 @@ def type_ligands(x, atom_type, lig_mask, info, orders=None, batch=None):
     if at.shape[0] != N or lig_mask.shape[0] != N:
         raise ValueError(f"{N} coordinates, {at.shape[0]} types, {lig_mask.shape[0]} mask entries")
     B = _n_molecules(lig_mask, batch)
-    off = _offsets(lig_mask, B, dev)
+    off = _pairs.mol_offsets(lig_mask, B, dev)
     i32 = dict(dtype=torch.int32, device=dev)
     code, mol_int = torch.zeros(N, **i32), torch.zeros((B, MOL_INT), **i32)
     if B == 0:
@@ -468,14 +444,7 @@ def vina_score(x, atom_type, lig_mask, pockets, info, mol_group=None, batch=None
     lig_mask = torch.as_tensor(lig_mask, device=dev).reshape(-1)
     B = _n_molecules(lig_mask, batch)
     G = pockets.n_groups
-    if mol_group is None:
-        mol_group = _default_groups(B, G)
-    if torch.is_tensor(mol_group) and mol_group.is_cuda:        # device data: the kernel range-checks it
-        if mol_group.numel() != B:
-            raise ValueError(f"{mol_group.numel()} group ids for {B} molecules")
-        groups = mol_group.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-    else:
-        groups = torch.as_tensor(_checked_groups(mol_group, B, G).astype(np.int32), device=dev)
+    groups = _pairs.device_groups(mol_group, B, G, dev)
     code, mol_int, off = type_ligands(x, atom_type, lig_mask, info, orders=orders, batch=B)
     f32 = dict(dtype=torch.float32, device=dev)
     out = VinaScores(torch.zeros((N, ATOM_OUT), **f32), torch.zeros((B, MOL_OUT), **f32), mol_int,
@@ -492,19 +461,8 @@ def read_sdf_records(path):
     """Every record of an SDF file -> list of (xyz float32 [n,3], element symbols, bonds [(i, j, order)], 0-based).  A
     small reader of its own: atom and bond blocks by the counts line's columns, with or without a version tag; bond type 4
     (aromatic) is refused -- the typing rules need Kekule orders."""
-    with open(path) as f:
-        lines = f.read().splitlines()
-    records, cur = [], []
-    for line in lines:
-        if line.startswith("$$$$"):
-            records.append(cur)
-            cur = []
-        else:
-            cur.append(line)
-    if any(l.strip() for l in cur):
-        records.append(cur)
     out = []
-    for k, rec in enumerate(records):
+    for k, rec in enumerate(_pairs.sdf_records(path)):
         if len(rec) < 4:
             raise ValueError(f"{path}: record {k} has no counts line")
         n_atoms, n_bonds = int(rec[3][0:3]), int(rec[3][3:6])
@@ -554,9 +512,7 @@ def score_molecules(molecules, pockets, info="crossdock", mol_group=None, device
     dev = pockets.x.device if isinstance(pockets, VinaPocket) else torch.device(device)
     if dev.type != "cuda":
         raise _lib.HipLibraryError("score_molecules needs a HIP device (no CPU fallback)")
-    sizes = [len(l[0]) for l in ligands]
-    x = np.concatenate([l[0] for l in ligands]) if ligands else np.zeros((0, 3), np.float32)
-    mask = np.repeat(np.arange(len(ligands), dtype=np.int64), sizes)
+    x, mask, sizes = _pairs.pack_ligands(ligands)
     symbols = [s for l in ligands for s in l[1]]
     orders = None
     if bonds == "file":
@@ -714,34 +670,17 @@ CSV_COLUMNS = ("n_atoms", "untyped", "n_rot", "nonfinite") + TERMS + ("inter", "
 
 def write_csv(path, rows):
     """rows: (source, index, MolVina or its dict); `path` None writes to stdout."""
-    lines = [",".join(("source", "index") + CSV_COLUMNS)]
-    for source, k, rec in rows:
-        rec = rec.as_dict() if hasattr(rec, "as_dict") else rec
-        lines.append(",".join([str(source), str(k)] + [repr(rec[c]) if isinstance(rec[c], float) else str(rec[c])
-                                                       for c in CSV_COLUMNS]))
-    if path is None:
-        sys.stdout.write("\n".join(lines) + "\n")
-        return
-    with open(path, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    _pairs.write_csv(path, rows, CSV_COLUMNS)
 
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Vina-type interaction score of written ligand poses against a protein "
                                             "(one row per molecule; not smina output)")
-    p.add_argument("--pdbfile", required=True)
-    p.add_argument("--sdf", nargs="+", required=True)
-    p.add_argument("--scope", choices=("protein", "pocket"), default="protein")
-    p.add_argument("--ref_ligand", default=None, help="SDF file or <chain>:<resi>: the pocket of --scope pocket")
+    _pairs.add_complex_arguments(p)
     p.add_argument("--bonds", choices=("distance", "file"), default="distance",
                    help="distance: perceive bonds as for generated molecules; file: read the SDF bond block")
     p.add_argument("--dataset", default="crossdock", help="the dataset whose bond-length tables --bonds distance uses")
-    p.add_argument("--out", default=None)
-    p.add_argument("--device", default="cuda")
-    a = p.parse_args(argv)
-    if a.scope == "pocket" and a.ref_ligand is None:
-        p.error("--scope pocket needs --ref_ligand")
-    return a
+    return _pairs.parse_complex_arguments(p, argv)
 
 
 def main(argv=None):

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from diffsbdd_amd import _lib, vina as V
+from diffsbdd_amd import _lib, pose, vina as V
 from tests import _vina_cases as C
 
 pytestmark = pytest.mark.gpu
@@ -182,6 +182,51 @@ def test_crystal_fixture_on_the_device_against_the_stored_float64_values():
 
 
 # 5 ---------------------------------------------------------------------------------------------------------------------------
+def test_pose_check_and_score_read_the_same_rows():
+    """dsbdd_pose_check and dsbdd_vina_score on the same coordinates, mol_off, mol_group and group_off (the score batch,
+    radii 1.75 everywhere): the two kernels share one range check (pair_rows, csrc/pair_sweep.h), so a molecule one of
+    them reads as empty, or as on an empty group, the other reads so too.  The expected sets are the batch's construction:
+    molecule `empty_mol` has no atoms; molecule 0 is on the group of size 0 and molecule 10 carries the group id 99;
+    molecules 2, 3, 4, 5, 6, 12, 13, 14 have 12 or more atoms on a group of TILE or more atoms at one per 60 cubic A."""
+    b = C.score_batch()
+    off, B = b["mol_off"], len(b["mol_off"]) - 1
+    empty, groupless, dense = [b["empty_mol"]], [0, 10], [2, 3, 4, 5, 6, 12, 13, 14]
+    assert np.diff(off)[empty].tolist() == [0] and np.diff(b["group_off"])[b["mol_group"][0]] == 0 and b["mol_group"][10] == 99
+    assert all(off[m + 1] - off[m] >= 12 and np.diff(b["group_off"])[b["mol_group"][m]] >= V.TILE for m in dense)
+    # the pose check through the C ABI, outputs in guarded buffers
+    N = len(b["lig_x"])
+    t = {k: torch.as_tensor(np.ascontiguousarray(b[k]), device=DEV) for k in ("lig_x", "mol_off", "mol_group", "poc_x", "group_off")}
+    lig_r, poc_r = torch.full((N,), 1.75, device=DEV), torch.full((len(b["poc_x"]),), 1.75, device=DEV)
+    p_atom, p_mol = _guarded(N, pose.ATOM_OUT), _guarded(B, pose.MOL_OUT)
+    rc = _lib.load().dsbdd_pose_check(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), t["lig_x"].data_ptr(),
+                                      lig_r.data_ptr(), t["mol_off"].data_ptr(), B, t["mol_group"].data_ptr(),
+                                      t["poc_x"].data_ptr(), poc_r.data_ptr(), t["group_off"].data_ptr(), len(b["group_off"]) - 1,
+                                      pose.CLASH_TOLERANCE, pose.CONTACT_CUTOFF, p_atom[GUARD:].data_ptr(), p_mol[GUARD:].data_ptr())
+    _lib.check(rc, "dsbdd_pose_check")
+    torch.cuda.synchronize()
+    assert _intact(p_atom, N) and _intact(p_mol, B)
+    p_atom, p_mol = p_atom.cpu().numpy()[GUARD:GUARD + N], p_mol.cpu().numpy()[GUARD:GUARD + B]
+    v_atom, v_mol, v_flag = launch_score(b)
+    rows = lambda m: slice(off[m], off[m + 1])
+    none = [0, 0, -1, int(np.float32(np.inf).view(np.int32))]
+    # empty for reason of size: the same molecules, and every other molecule has its atoms in both
+    assert np.nonzero(p_mol[:, pose.M_ATOMS] == 0)[0].tolist() == empty
+    assert p_mol[:, pose.M_ATOMS].tolist() == np.diff(off).tolist()
+    for m in empty:
+        assert not v_mol[m].any() and v_flag[m] == 0 and p_mol[m, pose.M_CONTACT_PAIRS] == 0
+    # on an empty group (a group of size 0, a group id out of range): no contact in one, no term in the other
+    for m in groupless:
+        assert off[m + 1] > off[m] and (p_atom[rows(m)] == none).all(), m
+        assert p_mol[m, pose.M_CONTACT_PAIRS] == 0 and p_mol[m, pose.M_DIST_BITS] == none[3], m
+        assert not v_atom[rows(m)].any() and not v_mol[m].any() and v_flag[m] == 0, m
+    # on a group both kernels read: every atom has a nearest pocket atom, the score has terms
+    for m in dense:
+        assert (p_atom[rows(m), pose.A_NEAREST] >= 0).all() and p_mol[m, pose.M_DIST_BITS] != none[3], m
+        assert (p_atom[rows(m), pose.A_NEAREST] < np.diff(b["group_off"])[b["mol_group"][m]]).all(), m
+        assert v_flag[m] == 0 and v_mol[m, 1] > 0, m
+
+
+# 6 ---------------------------------------------------------------------------------------------------------------------------
 def test_empty_batches_and_the_python_entry():
     pockets = V.VinaPocket.upload([V.TypedPocket(np.asarray([[3.8, 0, 0]], np.float32), np.asarray([17], np.int32))], DEV)
     none = V.vina_score(torch.zeros((0, 3), device=DEV), torch.zeros(0, dtype=torch.int64, device=DEV),
