@@ -16,6 +16,7 @@ import torch.nn.functional as F
 
 from oracle import egnn_oracle as eo
 from oracle import weights as W
+from tests._train64 import problem      # the inputs of every network-level test here and in test_gpu_train_degenerate.py
 
 pytestmark = pytest.mark.gpu
 
@@ -34,18 +35,6 @@ def make_dynamics(cfg, sd):
     m = EGNNDynamics(**cfg, device=dev())
     m.load_state_dict(sd)
     return m
-
-
-def problem(cfg, n_lig, n_poc, seed, spread=3.0):
-    g = torch.Generator().manual_seed(seed)
-    B = len(n_lig)
-    ml = torch.repeat_interleave(torch.arange(B), torch.tensor(n_lig))
-    mp = torch.repeat_interleave(torch.arange(B), torch.tensor(n_poc))
-    a, r = cfg["atom_nf"], cfg["residue_nf"]
-    xl = torch.cat([torch.randn(len(ml), 3, generator=g) * spread * 0.5, torch.randn(len(ml), a, generator=g)], 1)
-    xp = torch.cat([torch.randn(len(mp), 3, generator=g) * spread, torch.randn(len(mp), r, generator=g)], 1)
-    t = torch.rand(B, 1, generator=g)
-    return xl, xp, t, ml, mp
 
 
 @pytest.mark.parametrize("K,M,N", [(1000, 256, 256), (37, 20, 10), (5000, 256, 512), (513, 129, 256), (2, 4, 4),
