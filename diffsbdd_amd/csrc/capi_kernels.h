@@ -1,5 +1,5 @@
 // Thin C-ABI wrappers of the stand-alone kernels (included by engine.hip): DDPM steps (ddpm.h), keyed noise, node GEMM,
-// the node chain's row split (chain_split.h), bond orders (molecule.h), molecule graph statistics and fingerprint distances (mol_metrics.h), pose checks and the Vina-type score (pose_check.h, vina_score.h on pair_sweep.h), ligand packing (ligand_pack.h), the radius graph (radius_graph.h).
+// the node chain's row split (chain_split.h), bond orders (molecule.h), molecule graph statistics and fingerprint distances (mol_metrics.h), pose checks, the Vina-type score and its gradient (pose_check.h, vina_score.h, vina_grad.h on pair_sweep.h), ligand packing (ligand_pack.h), the radius graph (radius_graph.h).
 #pragma once
 
 extern "C" {
@@ -301,6 +301,23 @@ int dsbdd_vina_score(void* stream, const float* lig_x, const int32_t* lig_code, 
   VinaScoreArgs a{{lig_x, mol_off, mol_group, poc_x, group_off, (int)batch, (int)n_groups}, lig_code, mol_int, poc_code,
                   atom_out, mol_out, mol_flag};
   hipLaunchKernelGGL(vina_score_kernel, dim3((unsigned)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_vina_score_grad(void* stream, const float* lig_x, const int32_t* lig_code, const int32_t* mol_off, int64_t batch,
+                          const int32_t* mol_group, const int32_t* mol_int, const float* poc_x, const int32_t* poc_code,
+                          const int32_t* group_off, int64_t n_groups, float* atom_out, float* mol_out, int32_t* mol_flag,
+                          float* atom_grad, float* mol_grad) {
+  StreamDevice stream_device_(stream);
+  if (!lig_x || !lig_code || !mol_off || !mol_group || !mol_int || !poc_x || !poc_code || !group_off || !atom_out ||
+      !mol_out || !mol_flag || !atom_grad || !mol_grad)
+    return fail(DSBDD_ERR_ARG, "null argument");
+  if (int rc = check_pair_counts(batch, n_groups)) return rc;
+  if (batch == 0) return DSBDD_OK;
+  VinaGradArgs a{{{lig_x, mol_off, mol_group, poc_x, group_off, (int)batch, (int)n_groups}, lig_code, mol_int, poc_code,
+                  atom_out, mol_out, mol_flag}, atom_grad, mol_grad};
+  hipLaunchKernelGGL(vina_grad_kernel, dim3((unsigned)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
   HIP_TRY(hipGetLastError());
   return DSBDD_OK;
 }

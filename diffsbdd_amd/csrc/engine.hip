@@ -41,6 +41,7 @@
 #include "mol_metrics.h"
 #include "pose_check.h"
 #include "vina_score.h"
+#include "vina_grad.h"
 #include "node_chain.h"
 #include "node_linear.h"
 #include "train.h"

@@ -205,10 +205,17 @@ __device__ inline void vina_pair_terms(double d, bool hydrophobic, bool hbond, d
   if (hbond) t[4] += d <= -0.7 ? 1.0 : (d < 0.0 ? -d / 0.7 : 0.0);
 }
 
+// 1 + 0.05846 N_rot of molecule b (a negative N_rot as 0)
+__device__ inline double vina_rot_divisor(const int* mol_int, int b) {
+  const int n_rot = max(mol_int[(size_t)kVinaMolInt * b + 2], 0);
+  return 1.0 + kVinaRotWeight * (double)n_rot;
+}
+
 // every sum in float64, in the order pair_sweep fixes; the tiles before join before the store rounds, `inter` in term order
 struct VinaPolicy {
   struct Atom { float x, y, z; int code, cls; double radius; };
   struct Record { double t[kVinaTerms]; };     // walked by fully unrolled loops only: it stays in registers
+  struct Pair { float s, r; double d; bool hyd, hb; };
   using Total = Record;
   const VinaScoreArgs& p;
   Total* part;             // [kThreads / 64] in LDS
@@ -221,15 +228,21 @@ struct VinaPolicy {
     return {x, y, z, code, cls, vina_radius(cls)};
   }
   __device__ static bool skip(const Atom& a) { return a.cls == kVinaNone; }
-  __device__ static void pair(Record& acc, const Atom& a, const float4 q, int) {
+  // does the pair count?  then its float32 squared distance and root, its surface distance and the terms that apply
+  __device__ static bool counted(const Atom& a, const float4 q, Pair& v) {
     const int cj = __float_as_int(q.w), kj = vina_class_of(cj);
-    if (kj == kVinaNone) return;
-    const float s = pair_dist2(a.x, a.y, a.z, q.x, q.y, q.z);
-    if (!(s < 64.0f)) return;                                       // r < 8, strictly; false for NaN
-    const double d = (double)sqrtf(s) - a.radius - vina_radius(kj);
-    const bool hyd = (a.code & cj & kVinaHydrophobic) != 0;
-    const bool hb = ((a.code & kVinaDonor) && (cj & kVinaAcceptor)) || ((a.code & kVinaAcceptor) && (cj & kVinaDonor));
-    vina_pair_terms(d, hyd, hb, acc.t);
+    if (kj == kVinaNone) return false;
+    v.s = pair_dist2(a.x, a.y, a.z, q.x, q.y, q.z);
+    if (!(v.s < 64.0f)) return false;                               // r < 8, strictly; false for NaN
+    v.r = sqrtf(v.s);
+    v.d = (double)v.r - a.radius - vina_radius(kj);
+    v.hyd = (a.code & cj & kVinaHydrophobic) != 0;
+    v.hb = ((a.code & kVinaDonor) && (cj & kVinaAcceptor)) || ((a.code & kVinaAcceptor) && (cj & kVinaDonor));
+    return true;
+  }
+  __device__ static void pair(Record& acc, const Atom& a, const float4 q, int) {
+    Pair v;
+    if (counted(a, q, v)) vina_pair_terms(v.d, v.hyd, v.hb, acc.t);
   }
   __device__ static void fold(Record& acc, int o) {
     for (int k = 0; k < kVinaTerms; ++k) acc.t[k] += __shfl_xor(acc.t[k], o);
@@ -253,28 +266,32 @@ struct VinaPolicy {
       mol[k] = (float)s.t[k];
       inter += kVinaWeight[k] * s.t[k];
     }
-    const int n_rot = max(p.mol_int[(size_t)kVinaMolInt * b + 2], 0);
     mol[5] = (float)inter;
-    mol[6] = (float)(inter / (1.0 + kVinaRotWeight * (double)n_rot));
+    mol[6] = (float)(inter / vina_rot_divisor(p.mol_int, b));
     mol[7] = 0.0f;
     p.mol_flag[b] = 0;
   }
 };
 
-__global__ __launch_bounds__(kThreads) void vina_score_kernel(VinaScoreArgs p) {
-  __shared__ VinaPolicy::Total part[kThreads / 64];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const PairRows rows = pair_rows(p.pairs, b);
-  // a molecule with a coordinate that is not finite: the flag, and NaN in every float it owns
+// a molecule with a coordinate that is not finite: the flag, and NaN in every float it owns (the whole workgroup calls it
+// and gets the same answer)
+__device__ inline bool vina_nonfinite(const VinaScoreArgs& p, const PairRows& rows, int b) {
+  const int tid = threadIdx.x;
   int bad = 0;
   for (int k = tid; k < 3 * rows.n; k += kThreads) bad |= pose_nonfinite(p.pairs.lig_x[3 * (size_t)rows.lo + k]);
-  if (__syncthreads_or(bad)) {
-    const float nan = __builtin_nanf("");
-    for (int k = tid; k < kVinaTerms * rows.n; k += kThreads) p.atom_out[kVinaTerms * (size_t)rows.lo + k] = nan;
-    if (tid < kVinaMolOut) p.mol_out[(size_t)kVinaMolOut * b + tid] = nan;
-    if (tid == 0) p.mol_flag[b] = 1;
-    return;
-  }
+  if (!__syncthreads_or(bad)) return false;
+  const float nan = __builtin_nanf("");
+  for (int k = tid; k < kVinaTerms * rows.n; k += kThreads) p.atom_out[kVinaTerms * (size_t)rows.lo + k] = nan;
+  if (tid < kVinaMolOut) p.mol_out[(size_t)kVinaMolOut * b + tid] = nan;
+  if (tid == 0) p.mol_flag[b] = 1;
+  return true;
+}
+
+__global__ __launch_bounds__(kThreads) void vina_score_kernel(VinaScoreArgs p) {
+  __shared__ VinaPolicy::Total part[kThreads / 64];
+  const int b = blockIdx.x;
+  const PairRows rows = pair_rows(p.pairs, b);
+  if (vina_nonfinite(p, rows, b)) return;
   VinaPolicy pol{p, part};
   pair_sweep(p.pairs, rows, pol);
 }

@@ -307,6 +307,18 @@ class LigandGenerator:
         return [r.as_dict() for r in vina_mod.score_molecules(molecules, pockets, self.dataset_info)]
 
     @torch.no_grad()
+    def vina_gradients(self, pdb_file, molecules, pocket_ids=None, ref_ligand=None, scope="protein"):
+        """`vina_scores` with the gradient of the score's `inter` term with respect to the heavy-atom coordinates, from
+        the same launch (vina.py: `gradient_molecules`).  The same arguments.  Returns one dict per molecule, in order:
+        the keys of `vina_scores`, 'grad' (float32 [n, 3], kcal/mol/A; times 'rot_factor' = the gradient of 'score'),
+        'net', 'moment' (about the centroid), 'max_norm', 'rot_factor'.  See `vina.VINA_GRAD_COVERAGE`: ligand atoms only,
+        rigid protein, constant typing, no minimiser."""
+        from . import vina as vina_mod
+        residues = self._scope_residues(pdb_file, scope, pocket_ids, ref_ligand)
+        pockets = vina_mod.VinaPocket.upload([vina_mod.type_pocket(residues)], self.device)
+        return [dict(r.as_dict(), grad=r.grad) for r in vina_mod.gradient_molecules(molecules, pockets, self.dataset_info)]
+
+    @torch.no_grad()
     def check_poses(self, pdb_file, molecules, pocket_ids=None, ref_ligand=None, scope="protein", tol=None, contact=None):
         """Clash and contact counts of given molecules against the protein of `pdb_file` (pose.py; one launch).
         `molecules` as for `score_ligands`: `Molecule` objects, (xyz, elements) pairs or an SDF path.  scope 'protein':

@@ -24,8 +24,18 @@ bond of order >= 2; O acceptor, donor iff s < 2; S, P none; metal donor.  N_rot:
 both have heavy degree >= 2.  Pocket atoms: RESIDUE_TABLE (the 20 standard residues typed by the same rules from their
 covalent topology), by element outside it.
 
+Gradient (`vina_gradient`, `vina_energy`; one launch of `dsbdd_vina_score_grad`, csrc/vina_grad.h, in place of
+`dsbdd_vina_score`: the same sweep writes the score's outputs bit for bit and the gradient; `_vina_grad_host` restates it):
+
+    u           = (x_i - x_j) / r              the three float32 differences the distance is formed from, over r
+    gauss1'     = -8 d exp(-4 d^2)             gauss2' = -c exp(-c^2), c = (d - 3) / 2
+    repulsion'  = 2 d if d < 0, else 0
+    hydrophobic'= -1 if 0.5 < d < 1.5, else 0  hbond' = -1 / 0.7 if -0.7 < d < 0, else 0     one-sided as the terms are
+    g_i         = sum_j (sum_k WEIGHTS[k] T_k'(d_ij)) u_ij          d inter / d x_i, kcal/mol/A; a pair with r = 0 adds 0
+    d score / d x_i = g_i / (1 + ROT_WEIGHT N_rot)                  typing (codes, N_rot) is constant in x
+
   python -m diffsbdd_amd.vina --pdbfile P.pdb --sdf L.sdf [L2.sdf ...] [--scope protein|pocket --ref_ligand ...]
-                              [--bonds distance|file] [--dataset crossdock] [--out scores.csv]
+                              [--bonds distance|file] [--dataset crossdock] [--out scores.csv] [--grad_out atoms.csv]
 """
 from __future__ import annotations
 
@@ -55,6 +65,8 @@ TILE = 1024                           # pocket atoms per LDS tile of vina_score_
 ATOM_OUT, MOL_OUT, MOL_INT = 5, 8, 4  # columns of the kernels' outputs
 M_INTER, M_SCORE = 5, 6
 I_TYPED, I_UNTYPED, I_ROT = 0, 1, 2
+ATOM_GRAD, MOL_GRAD = 3, 8            # columns of the gradient outputs of dsbdd_vina_score_grad
+G_NET, G_MOMENT, G_MAX, G_ROT = slice(0, 3), slice(3, 6), 6, 7
 EPS32 = 2.0 ** -24
 _RADIUS = np.asarray([0.0] + [XS_RADII[c] for c in CLASSES[1:]], np.float64)
 _LIPSCHITZ = (1.716, 0.429, None, 1.0, 1.0 / 0.7)                                # of the five terms in d (repulsion: 2 |d| + 2 dd)
@@ -75,6 +87,21 @@ VINA_COVERAGE = (
     "pose as given, against a rigid protein, and only the residues given (an atom outside the selection is not seen); "
     "ligand bonds are perceived from distances (the tables of the samplers) unless given (--bonds file); "
     "ABSENT = the external docking binaries (refused).")
+
+VINA_GRAD_COVERAGE = (
+    "Vina-type gradient: PRESENT = the analytic gradient of the intermolecular term `inter` of the Vina-type score with "
+    "respect to the coordinates of the ligand heavy atoms only, in kcal/mol/A, from the GPU sweep that also scores (the score's "
+    "outputs come out unchanged), per atom, with its sum, its moment about the ligand's centroid, its largest norm and the "
+    "factor 1 / (1 + 0.05846 N_rot) that turns it into the gradient of `score`, and as a torch autograd function of the "
+    "coordinates; "
+    "DEFINED AS = the sum over the pairs counted at the given pose of the terms' derivatives in the surface distance times "
+    "the unit vector from the pocket atom to the ligand atom; a ligand atom exactly on a pocket atom adds nothing; at the "
+    "kinks of the piecewise-linear terms the derivative is that of the branch the term takes there; "
+    "NOT = a gradient with respect to protein coordinates (rigid protein); NOT a gradient of the typing: atom codes and "
+    "N_rot are constants, so a bond made or broken by moving atoms is not seen; NOT smooth: it is discontinuous where the score "
+    "is, at the 8 A cutoff (a jump of the score that the gradient ignores) and at the kinks of the repulsion, hydrophobic and "
+    "hbond terms; NOT smina's minimiser and not a minimiser at all: no search, no line search, no pose is changed; "
+    "no intramolecular term.")
 
 
 def class_of(symbol):
@@ -382,6 +409,59 @@ class VinaScores:
                         int(flag[b])) for b in range(len(mol))]
 
 
+@dataclass
+class MolVinaGrad(MolVina):
+    """`MolVina` with the gradient of `inter` of one molecule (host arrays)."""
+    grad: np.ndarray = None       # float32 [n, 3]: d inter / d x_i, kcal/mol/A
+    mol_grad: np.ndarray = None   # float32 [8]: net (3), moment about the centroid (3), max |g_i|, 1 / (1 + ROT_WEIGHT N_rot)
+
+    net = property(lambda self: self.mol_grad[G_NET])
+    moment = property(lambda self: self.mol_grad[G_MOMENT])
+    max_norm = property(lambda self: float(self.mol_grad[G_MAX]))
+    rot_factor = property(lambda self: float(self.mol_grad[G_ROT]))
+    score_grad = property(lambda self: self.mol_grad[G_ROT] * self.grad)
+
+    def as_dict(self):
+        out = super().as_dict()
+        out.update(max_norm=self.max_norm, rot_factor=self.rot_factor, net=[float(v) for v in self.net],
+                   moment=[float(v) for v in self.moment])
+        return out
+
+
+@dataclass
+class VinaGradients(VinaScores):
+    """`VinaScores` with the outputs of the fused launch (device tensors from `vina_gradient`, numpy arrays from
+    `_vina_grad_host`)."""
+    grad: object = None      # float [N, 3]: d inter / d x_i
+    mol_grad: object = None  # float [B, 8]
+    kink_margin: float = float("inf")   # `_vina_grad_host` only: the smallest |d - kink| over the pairs a kink of hydrophobic' / hbond' applies to
+
+    net = property(lambda self: self.mol_grad[:, G_NET])
+    moment = property(lambda self: self.mol_grad[:, G_MOMENT])
+    max_norm = property(lambda self: self.mol_grad[:, G_MAX])
+    rot_factor = property(lambda self: self.mol_grad[:, G_ROT])
+
+    @property
+    def atom_mol(self):
+        """[N] the molecule of every atom (from `mol_off`; no read-back)."""
+        off = self.mol_off
+        if torch.is_tensor(off):
+            return torch.repeat_interleave(torch.arange(len(off) - 1, device=off.device), (off[1:] - off[:-1]).long(),
+                                           output_size=int(self.grad.shape[0]))
+        return np.repeat(np.arange(len(off) - 1), np.diff(off))
+
+    @property
+    def score_grad(self):
+        """[N, 3] d score / d x_i = rot_factor[mol] grad."""
+        return self.rot_factor[self.atom_mol][:, None] * self.grad
+
+    def molecules(self):
+        """One `MolVinaGrad` per molecule, in order (one copy of each tensor to the host)."""
+        grad, mol_grad, off = _np(self.grad), _np(self.mol_grad), _np(self.mol_off)
+        return [MolVinaGrad(m.mol, m.ints, m.atom, m.code, m.nonfinite, grad[off[b]:off[b + 1]].copy(), mol_grad[b].copy())
+                for b, m in enumerate(VinaScores.molecules(self))]
+
+
 # ---- the device path ---------------------------------------------------------------------------------------------------------
 def type_ligands(x, atom_type, lig_mask, info, orders=None, batch=None):
     """Atom codes and rotor counts of a batch on the device: `molecules.bond_orders` (unless `orders` int8 [B, n_max, n_max]
@@ -433,8 +513,14 @@ def vina_score(x, atom_type, lig_mask, pockets, info, mol_group=None, batch=None
     read-back inside.  x, atom_type, lig_mask, info, orders, batch as for `type_ligands`; `pockets`: a `VinaPocket`
     (uploaded before) or a list of `TypedPocket` / (xyz, code) host arrays, one per group; `mol_group` [B] as for
     `pose.pose_check`.  -> VinaScores of device tensors."""
+    return _scored("vina_score", VinaScores, x, atom_type, lig_mask, pockets, info, mol_group, batch, orders)
+
+
+def _scored(what, kind, x, atom_type, lig_mask, pockets, info, mol_group, batch, orders):
+    """The launches behind `vina_score` (kind VinaScores: `dsbdd_vina_score`) and `vina_gradient` (kind VinaGradients:
+    `dsbdd_vina_score_grad`, two more outputs) after the typing both share."""
     if not (torch.is_tensor(x) and x.is_cuda):
-        raise _lib.HipLibraryError("vina_score needs device tensors (HIP path; no CPU fallback)")
+        raise _lib.HipLibraryError(f"{what} needs device tensors (HIP path; no CPU fallback)")
     lib = _lib.load()
     dev = x.device
     if not isinstance(pockets, VinaPocket):
@@ -447,13 +533,63 @@ def vina_score(x, atom_type, lig_mask, pockets, info, mol_group=None, batch=None
     groups = _pairs.device_groups(mol_group, B, G, dev)
     code, mol_int, off = type_ligands(x, atom_type, lig_mask, info, orders=orders, batch=B)
     f32 = dict(dtype=torch.float32, device=dev)
-    out = VinaScores(torch.zeros((N, ATOM_OUT), **f32), torch.zeros((B, MOL_OUT), **f32), mol_int,
-                     torch.zeros(B, dtype=torch.int32, device=dev), code, off)
+    out = kind(torch.zeros((N, ATOM_OUT), **f32), torch.zeros((B, MOL_OUT), **f32), mol_int,
+               torch.zeros(B, dtype=torch.int32, device=dev), code, off)
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    rc = lib.dsbdd_vina_score(stream, _ptr(x), _ptr(code), off.data_ptr(), B, _ptr(groups), _ptr(mol_int), _ptr(pockets.x),
-                              _ptr(pockets.code), pockets.group_off.data_ptr(), G, _ptr(out.atom), _ptr(out.mol), _ptr(out.flag))
-    _lib.check(rc, "dsbdd_vina_score")
+    args = (stream, _ptr(x), _ptr(code), off.data_ptr(), B, _ptr(groups), _ptr(mol_int), _ptr(pockets.x), _ptr(pockets.code),
+            pockets.group_off.data_ptr(), G, _ptr(out.atom), _ptr(out.mol), _ptr(out.flag))
+    if kind is VinaScores:
+        rc = lib.dsbdd_vina_score(*args)
+    else:
+        out.grad, out.mol_grad = torch.zeros((N, ATOM_GRAD), **f32), torch.zeros((B, MOL_GRAD), **f32)
+        rc = lib.dsbdd_vina_score_grad(*args, _ptr(out.grad), _ptr(out.mol_grad))
+    _lib.check(rc, "dsbdd_vina_score" if kind is VinaScores else "dsbdd_vina_score_grad")
     return out
+
+
+def vina_gradient(x, atom_type, lig_mask, pockets, info, mol_group=None, batch=None, orders=None):
+    """The score of a batch and the gradient of its `inter` term with respect to x, on device tensors: the launches of
+    `vina_score` with `dsbdd_vina_score_grad` in place of `dsbdd_vina_score` (one sweep writes both; the score's outputs
+    are bit for bit those of `vina_score`).  Arguments as for `vina_score`.  -> VinaGradients of device tensors: `grad`
+    [N,3] = d inter / d x_i in kcal/mol/A (0 for untyped atoms), `mol_grad` [B,8] with the properties `net`, `moment` (about
+    the centroid), `max_norm`, `rot_factor`, and `score_grad` = rot_factor[mol] grad.  See `VINA_GRAD_COVERAGE`."""
+    return _scored("vina_gradient", VinaGradients, x, atom_type, lig_mask, pockets, info, mol_group, batch, orders)
+
+
+def _chain(grad_out, grad, rot_factor, mol, which):
+    """d (sum_b grad_out[b] E_b) / d x from the saved gradient of `inter`: E = score carries the rotor factor."""
+    scale = grad_out[mol] * rot_factor[mol] if which == "score" else grad_out[mol]
+    return scale[:, None] * grad
+
+
+class VinaScoreFunction(torch.autograd.Function):
+    """`score` or `inter` [B] as a differentiable function of the ligand coordinates x (the only input with a gradient):
+    forward = one fused launch (`vina_gradient`), which saves d inter / d x and the rotor factors; backward = the chain rule
+    on them in plain torch.  Once differentiable: the saved gradient is a constant, a second derivative is refused.  A
+    molecule with a coordinate that is not finite has a NaN energy and NaN gradient rows."""
+
+    @staticmethod
+    def forward(ctx, x, atom_type, lig_mask, pockets, info, mol_group, batch, orders, which):
+        if which not in ("score", "inter"):
+            raise ValueError("which must be 'score' or 'inter'")
+        st = vina_gradient(x, atom_type, lig_mask, pockets, info, mol_group, batch, orders)
+        ctx.save_for_backward(st.grad, st.rot_factor.contiguous(), st.atom_mol)
+        ctx.which, ctx.x_shape, ctx.x_dtype = which, x.shape, x.dtype
+        return (st.score if which == "score" else st.inter).clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        grad, rot_factor, mol = ctx.saved_tensors
+        gx = _chain(grad_out.to(torch.float32), grad, rot_factor, mol, ctx.which)
+        return (gx.reshape(ctx.x_shape).to(ctx.x_dtype),) + (None,) * 8
+
+
+def vina_energy(x, atom_type, lig_mask, pockets, info, mol_group=None, batch=None, orders=None, which="score"):
+    """`score` (which='score') or `inter` (which='inter') of every molecule, float32 [B] on the device, differentiable in x
+    through `VinaScoreFunction`: `vina_energy(x, ...).sum().backward()` leaves d score / d x in `x.grad`.  The other
+    arguments as for `vina_score`; none of them receives a gradient."""
+    return VinaScoreFunction.apply(x, atom_type, lig_mask, pockets, info, mol_group, batch, orders, which)
 
 
 # ---- written molecules -------------------------------------------------------------------------------------------------------
@@ -506,12 +642,22 @@ def score_molecules(molecules, pockets, info="crossdock", mol_group=None, device
     pockets): upload, then the launches of `vina_score`.  bonds 'distance': perceived from the coordinates with the
     tables of the dataset `info`, as for generated molecules (every element must be in its decoder); 'file': the bond
     lists the molecules carry.  -> list of `MolVina`."""
+    return _molecule_records(vina_score, "score_molecules", molecules, pockets, info, mol_group, device, bonds)
+
+
+def gradient_molecules(molecules, pockets, info="crossdock", mol_group=None, device="cuda", bonds="distance"):
+    """`score_molecules` through the launches of `vina_gradient`: the same arguments, the same score records, and the
+    gradient of `inter` with them.  -> list of `MolVinaGrad`."""
+    return _molecule_records(vina_gradient, "gradient_molecules", molecules, pockets, info, mol_group, device, bonds)
+
+
+def _molecule_records(entry, what, molecules, pockets, info, mol_group, device, bonds):
     if bonds not in ("distance", "file"):
         raise ValueError("bonds must be 'distance' or 'file'")
     ligands = as_ligands(molecules)
     dev = pockets.x.device if isinstance(pockets, VinaPocket) else torch.device(device)
     if dev.type != "cuda":
-        raise _lib.HipLibraryError("score_molecules needs a HIP device (no CPU fallback)")
+        raise _lib.HipLibraryError(f"{what} needs a HIP device (no CPU fallback)")
     x, mask, sizes = _pairs.pack_ligands(ligands)
     symbols = [s for l in ligands for s in l[1]]
     orders = None
@@ -532,8 +678,8 @@ def score_molecules(molecules, pockets, info="crossdock", mol_group=None, device
         raise ValueError(f"elements {missing} are outside the atom decoder of the dataset: bonds cannot be perceived from "
                          "distances (bonds='file' reads them from the molecules)")
     at = np.asarray([decoder.index(s) for s in symbols], np.int64)
-    st = vina_score(torch.as_tensor(x, device=dev), torch.as_tensor(at, device=dev), torch.as_tensor(mask, device=dev), pockets,
-                    info, mol_group, batch=len(ligands), orders=None if orders is None else torch.as_tensor(orders, device=dev))
+    st = entry(torch.as_tensor(x, device=dev), torch.as_tensor(at, device=dev), torch.as_tensor(mask, device=dev), pockets,
+               info, mol_group, batch=len(ligands), orders=None if orders is None else torch.as_tensor(orders, device=dev))
     return st.molecules()
 
 
@@ -664,6 +810,154 @@ def error_bound(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_code, g
     return atom_bound, mol_bound
 
 
+# ---- the gradient: float64 restatement and error bound -----------------------------------------------------------------------------
+_CURVATURE = (8.0, 0.5, 2.0)          # sup |T_k''| of gauss1, gauss2 and (where d < 0) repulsion
+_KINKS = ((0.5, 1.5), (-0.7, 0.0))    # of hydrophobic', hbond': where the piecewise-constant derivative jumps
+_JUMPS = (1.0, 1.0 / 0.7)
+EPS64 = 2.0 ** -53
+
+
+def pair_slopes(d, hydrophobic=True, hbond=True):
+    """The derivatives of the five terms in the surface distance at `d` (any shape) in d's dtype -> [..., 5], one-sided at
+    the kinks as `pair_terms` is: at d = 0.5, 1.5, -0.7, 0 the value of the constant branch the term takes there."""
+    d = np.asarray(d)
+    t = d.dtype.type
+    zero = t(0)
+    a, c = d / t(0.5), (d - t(3)) / t(2)
+    out = np.stack([t(-8) * d * np.exp(-(a * a)), -c * np.exp(-(c * c)), np.where(d < 0, t(2) * d, zero),
+                    np.where((d > t(0.5)) & (d < t(1.5)), t(-1), zero),
+                    np.where((d > t(-0.7)) & (d < 0), t(-1) / t(0.7), zero)], -1)
+    out[..., 3] = np.where(hydrophobic, out[..., 3], zero)
+    out[..., 4] = np.where(hbond, out[..., 4], zero)
+    return out
+
+
+def _vina_grad_host(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_code, group_off, dtype=np.float64, eps=None):
+    """`dsbdd_vina_score_grad` in numpy: the arguments of `_vina_score_host`, float32 coordinates, the counted pairs decided
+    by the float32 distance (and a pair whose float32 distance is 0 adds nothing to the gradient), everything else in
+    `dtype` from differences and a root formed in `dtype` (float64: the specification; its differences of float32
+    coordinates are exact).  -> VinaGradients of arrays in `dtype`: the fields of `_vina_score_host`'s result, grad [N, 3],
+    mol_grad [B, 8].  With `eps` also the forward error bound of `grad_error_bound`: (result, grad_bound [N, 3],
+    mol_grad_bound [B, 8]), and the smallest distance |d - kink| over the pairs a kink of hydrophobic' / hbond' applies to
+    as `result.kink_margin`."""
+    st, _ = _vina_score_host(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_code, group_off, dtype=dtype)
+    x = np.asarray(_np(lig_x), np.float32).reshape(-1, 3)
+    q = np.asarray(_np(poc_x), np.float32).reshape(-1, 3)
+    code, qcode = st.lig_code, np.asarray(_np(poc_code), np.int32).reshape(-1)
+    off, goff = st.mol_off.astype(np.int64), np.asarray(_np(group_off), np.int64).reshape(-1)
+    groups = np.asarray(_np(mol_group), np.int64).reshape(-1)
+    B, G = len(off) - 1, len(goff) - 1
+    grad, mol_grad = np.zeros((len(x), ATOM_GRAD), dtype), np.zeros((B, MOL_GRAD), dtype)
+    grad_bound, mol_bound = np.zeros((len(x), ATOM_GRAD)), np.zeros((B, MOL_GRAD))
+    kink_margin = np.inf
+    w = np.asarray(WEIGHTS, dtype)
+    aw = np.abs(np.asarray(WEIGHTS, np.float64))
+    for b in range(B):
+        lo, hi = int(off[b]), int(off[b + 1])
+        if not (lo >= 0 and hi >= lo and hi <= off[B]):
+            lo = hi = 0
+        g = int(groups[b])
+        glo, ghi = (int(goff[g]), int(goff[g + 1])) if 0 <= g < G else (0, 0)
+        if not (glo >= 0 and ghi >= glo and ghi <= goff[G]):
+            glo = ghi = 0
+        if st.flag[b]:
+            grad[lo:hi], mol_grad[b], grad_bound[lo:hi], mol_bound[b] = np.nan, np.nan, np.nan, np.nan
+            continue
+        n, n_rot = hi - lo, max(int(st.mol_int[b, I_ROT]), 0)
+        mol_grad[b, G_ROT] = dtype(1.0) / dtype(1.0 + ROT_WEIGHT * n_rot)
+        if eps is not None:
+            mol_bound[b, G_ROT] = 3 * eps * float(mol_grad[b, G_ROT])
+        if n == 0 or ghi == glo:
+            continue
+        r, r32, d, counted, hyd, hb = _molecule_pairs(x[lo:hi], code[lo:hi], q[glo:ghi], qcode[glo:ghi], dtype)
+        live = counted & (r32 > 0)                                              # coincident atoms have no direction
+        xd = x[lo:hi].astype(dtype)
+        e = xd[:, None, :] - q[glo:ghi].astype(dtype)[None, :, :]
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            slopes = np.where(live[..., None], pair_slopes(d, hyd, hb), dtype(0)) * w          # [n, m, 5] weighted
+            S = slopes.sum(-1)
+            u = np.where(live[..., None], e / np.where(live, r, dtype(1))[..., None], dtype(0))
+        f = S[..., None] * u                                                    # [n, m, 3]
+        gm = f.sum(1)
+        grad[lo:hi] = gm
+        c = xd.sum(0) / dtype(n)
+        y = xd - c
+        norms = np.sqrt((gm[:, 0] * gm[:, 0] + gm[:, 1] * gm[:, 1]) + gm[:, 2] * gm[:, 2])
+        mol_grad[b, G_NET], mol_grad[b, G_MOMENT], mol_grad[b, G_MAX] = gm.sum(0), np.cross(y, gm).sum(0), norms.max()
+        if eps is None:
+            continue
+        rr, dd = np.where(live, r, 0.0).astype(np.float64), np.where(live, d, 0.0).astype(np.float64)
+        delta = np.where(live, 4 * eps * rr + 16 * eps, 0.0)
+        arg = np.stack([(dd / 0.5) ** 2, ((dd - 3) / 2) ** 2], -1)
+        sl = np.abs(slopes.astype(np.float64))
+        # the slope: curvature times the error of d, the jumps of the piecewise-constant derivatives inside it, evaluation
+        lip = aw[0] * _CURVATURE[0] + aw[1] * _CURVATURE[1] + np.where(dd <= delta, aw[2] * _CURVATURE[2], 0.0)
+        jump = np.zeros_like(dd)
+        for flagged, kinks, size, weight in ((hyd, _KINKS[0], _JUMPS[0], aw[3]), (hb, _KINKS[1], _JUMPS[1], aw[4])):
+            near = np.minimum(np.abs(dd - kinks[0]), np.abs(dd - kinks[1]))
+            jump += np.where(live & flagged & (near <= delta), weight * size, 0.0)
+            if (live & flagged).any():
+                kink_margin = min(kink_margin, float(near[live & flagged].min()))
+        evaluation = eps * ((10 + 3 * arg[..., 0]) * sl[..., 0] + (10 + 3 * arg[..., 1]) * sl[..., 1] + 6 * sl[..., 2:].sum(-1))
+        dS = np.where(live, lip * delta + jump + evaluation, 0.0)
+        au, af = np.abs(u.astype(np.float64)), np.abs(f.astype(np.float64))
+        pair = dS[..., None] * au + 7 * eps * af
+        n_atom = live.sum(1).astype(np.float64)
+        ab = pair.sum(1) + n_atom[:, None] * eps * af.sum(1)
+        grad_bound[lo:hi] = ab
+        ag, ay, ax = np.abs(gm.astype(np.float64)), np.abs(y.astype(np.float64)), np.abs(xd.astype(np.float64))
+        mol_bound[b, G_NET] = ab.sum(0) + n * eps * ag.sum(0)
+        dy = (n + 1) * eps * ax.mean(0)[None, :] + eps * ay
+        ac = np.abs(c.astype(np.float64))
+        for k in range(3):
+            i, j = (k + 1) % 3, (k + 2) % 3
+            mol_bound[b, 3 + k] = (dy[:, i] * ag[:, j] + ay[:, i] * ab[:, j] + dy[:, j] * ag[:, i] + ay[:, j] * ab[:, i]).sum() + \
+                (n + 2) * eps * (ay[:, i] * ag[:, j] + ay[:, j] * ag[:, i]).sum() + \
+                (n + 4) * EPS64 * ((ax[:, i] + ac[i]) * ag[:, j] + (ax[:, j] + ac[j]) * ag[:, i]).sum()
+        mol_bound[b, G_MAX] = float(np.sqrt((ab * ab).sum(1)).max()) + 3 * eps * float(norms.max())
+    out = VinaGradients(st.atom, st.mol, st.mol_int, st.flag, st.lig_code, st.mol_off, grad, mol_grad, kink_margin)
+    return out if eps is None else (out, grad_bound, mol_bound)
+
+
+def grad_error_bound(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_code, group_off, eps=EPS32):
+    """Forward error bound of a float32 evaluation of the gradient (and so of the kernel, which rounds less: it works in
+    float64 from the float32 r on) against the float64 restatement `_vina_grad_host`, evaluated in float64, first order in
+    eps.  -> (grad_bound [N, 3], mol_grad_bound [B, 8]); NaN where the molecule is not finite.  Derivation, per counted
+    pair with r > 0, f = S u its contribution, S = sum_k w_k T_k'(d):
+
+    d:  dd = 4 eps r + 16 eps, as in `error_bound` (3.5 eps r from the five roundings of r^2 and the root, 16 eps from the
+        two subtractions of radii at |values| <= 8).
+    S:  |dT_k'| <= sup |T_k''| dd with sup |T''| = 8 (gauss1: |64 d^2 - 8| exp(-4 d^2) peaks at d = 0), 0.5 (gauss2:
+        |4 c^2 - 2| exp(-c^2) / 4 peaks at c = 0), 2 (repulsion, where d < 0; counted where d <= dd, since beyond that both
+        sides evaluate the branch 0 exactly).  hydrophobic' and hbond' are piecewise constant: a flagged pair
+        with |d - kink| <= dd (kinks 0.5 and 1.5, -0.7 and 0) may sit on the other branch, which adds the full jump, 1 or
+        1 / 0.7; every other pair adds 0.  The repulsion's kink at d = 0 is a jump of at most 2 dd of a continuous
+        derivative: the Lipschitz term above covers it.  Evaluation in float32: a gaussian derivative -8 d E or -c E has
+        the relative error of c (eps), of its square (3 eps, on the argument: 3 |arg| eps on E), of the exponential
+        (2 eps), of the product (eps) and of the weight (eps) <= (6 + 3 |arg|) eps; the other terms one or two roundings,
+        <= 2 eps; the sum of the five, four additions: 4 eps sum_k |w_k T_k'|.  Together
+        dS = sum_k |w_k| sup|T_k''| dd + jumps + eps sum_k ((6 + 3 |arg_k|) or 2, + 4) |w_k T_k'|.
+    u:  each float32 difference carries eps (one rounding of an exact difference), r carries 3.5 eps, the division eps:
+        |du_k| <= 6 eps |u_k| including the second-order terms.
+    f:  |df_k| <= dS |u_k| + 6 eps |S u_k| + eps |S u_k| (the product).
+    g_i: the sum of the n_i pair terms adds n_i eps sum_j |f_jk| (a float32 running sum; for the kernel, whose sums are
+        float64, the float32 carry between tiles: one rounding per tile that holds a counted pair, at most n_i of them,
+        and the stored value's own).
+    net: sum_i bound(g_i) + n eps sum_i |g_ik| (n atoms; a float32 sum, the kernel's one final rounding).
+    moment: with y = x - c, c the mean: |dc_k| <= (n + 1) eps mean_i |x_ik| (a float32 mean), |dy_ik| <= |dc_k| + eps
+        |y_ik|; a component y_a g_b - y_b g_a has the error |dy_a| |g_b| + |y_a| bound(g_b) + (a <-> b), its two
+        products and the difference 2 eps (|y_a g_b| + |y_b g_a|), and the sum over atoms n eps of the same.  The kernel
+        forms sum x_i x g_i - c x sum g_i in float64 instead: the cancellation between the two is exact algebra, its
+        roundings are (n + 4) 2^-53 sum_i (|x_ia| + |c_a|) |g_ib| + (a <-> b), the only float64 term kept (it does not
+        shrink with y; everywhere else float64 roundings are 2^-29 of a float32 term already counted in full).
+    max_norm: |max_i |g_i| - max_i |g_i|'| <= max_i |dg_i| <= max_i |bound(g_i)|_2, and 3 eps max |g_i| for the norm's
+        own evaluation and the store.
+    rot_factor: a product, a sum, a division: 3 eps |value|."""
+    _, grad_bound, mol_bound = _vina_grad_host(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_code, group_off,
+                                               eps=float(eps))
+    return grad_bound, mol_bound
+
+
 # ---- command line ----------------------------------------------------------------------------------------------------------
 CSV_COLUMNS = ("n_atoms", "untyped", "n_rot", "nonfinite") + TERMS + ("inter", "score")
 
@@ -673,6 +967,21 @@ def write_csv(path, rows):
     _pairs.write_csv(path, rows, CSV_COLUMNS)
 
 
+GRAD_CSV_COLUMNS = ("source", "index", "atom", "gx", "gy", "gz", "norm")
+
+
+def write_grad_csv(path, rows):
+    """rows: (source, index, MolVinaGrad) -> one line per heavy atom: source, molecule index, atom index, the gradient of
+    `inter` (kcal/mol/A, floats by repr) and its norm."""
+    lines = [",".join(GRAD_CSV_COLUMNS)]
+    for source, k, rec in rows:
+        for a, g in enumerate(np.asarray(rec.grad, np.float64)):
+            lines.append(",".join([str(source), str(k), str(a)] + [repr(float(v)) for v in g] +
+                                  [repr(float(np.sqrt((g * g).sum())))]))
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Vina-type interaction score of written ligand poses against a protein "
                                             "(one row per molecule; not smina output)")
@@ -680,6 +989,9 @@ def parse_args(argv=None):
     p.add_argument("--bonds", choices=("distance", "file"), default="distance",
                    help="distance: perceive bonds as for generated molecules; file: read the SDF bond block")
     p.add_argument("--dataset", default="crossdock", help="the dataset whose bond-length tables --bonds distance uses")
+    p.add_argument("--grad_out", default=None,
+                   help="also write the gradient of `inter` with respect to the ligand coordinates, one row per heavy atom "
+                        "(kcal/mol/A; the scores then come from the same launch, unchanged)")
     return _pairs.parse_complex_arguments(p, argv)
 
 
@@ -689,10 +1001,16 @@ def main(argv=None):
     typed = type_pocket(select_residues(a.pdbfile, a.scope, a.ref_ligand))
     print(f"[vina] {len(typed.code)} protein heavy atoms, {typed.untemplated} typed by element alone", file=sys.stderr)
     pockets = VinaPocket.upload([typed], torch.device(a.device))
+    records_of = score_molecules
+    if a.grad_out is not None:
+        print(VINA_GRAD_COVERAGE, file=sys.stderr)
+        records_of = gradient_molecules
     rows = []
     for path in a.sdf:
-        rows += [(path, k, rec) for k, rec in enumerate(score_molecules(path, pockets, a.dataset, bonds=a.bonds))]
+        rows += [(path, k, rec) for k, rec in enumerate(records_of(path, pockets, a.dataset, bonds=a.bonds))]
     write_csv(a.out, rows)
+    if a.grad_out is not None:
+        write_grad_csv(a.grad_out, rows)
     return rows
 
 

@@ -880,6 +880,34 @@ int dsbdd_vina_score(void* stream, const float* lig_x, const int32_t* lig_code, 
                      const int32_t* mol_group, const int32_t* mol_int, const float* poc_x, const int32_t* poc_code,
                      const int32_t* group_off, int64_t n_groups, float* atom_out, float* mol_out, int32_t* mol_flag);
 
+/* dsbdd_vina_score and the analytic gradient of `inter` with respect to the ligand coordinates from one sweep
+ * (csrc/vina_grad.h), one launch, one workgroup per molecule.  Every input, convention and check of dsbdd_vina_score;
+ * atom_out, mol_out and mol_flag are bit for bit what dsbdd_vina_score writes for the same inputs.
+ * Per counted pair (i ligand atom, j pocket atom; counted as above: both typed, float32 r < 8): e = (dx, dy, dz) the three
+ * float32 differences x_i - x_j the distance is formed from, r their float32 root, and from here on float64:
+ * d = r - R_i - R_j, u = e / r (the float32 values converted, then divided), and the derivatives of the terms in d,
+ *   gauss1' = -8 d exp(-4 d^2);  gauss2' = -c exp(-c^2) with c = (d - 3) / 2;  repulsion' = 2 d if d < 0, else 0;
+ *   hydrophobic' (both atoms hydrophobic) = -1 if 0.5 < d < 1.5, else 0;
+ *   hbond' (donor / acceptor pair) = -1 / 0.7 if -0.7 < d < 0, else 0,
+ * one-sided at the kinks exactly as the terms are: at d = 0.5, 1.5, -0.7 and 0 the derivative is the 0 (or, for the
+ * repulsion at d = 0, the 2 d = 0) of the branch the term itself takes there.  A pair with r == 0 (the atoms coincide) adds
+ * to the five terms as in dsbdd_vina_score and adds ZERO to the gradient: its direction is undefined.  The cutoff at 8 A is
+ * a jump of the score itself, as in Vina; the gradient ignores it (it is the gradient of the sum over the pairs counted at
+ * x).  Typing is constant: codes and N_rot do not depend on x here.
+ * atom_grad [N][3]: g_i = sum_j (sum_k w_k T_k'(d_ij)) u_ij = d inter / d x_i in kcal/mol/A, w the weights of `inter`;
+ * 0 for an untyped atom and for the atoms of a molecule on an empty or invalid group.
+ * mol_grad [batch][8]: [0:3] F = sum_i g_i;  [3:6] the moment about the centroid sum_i (x_i - c) x g_i, c the mean of all
+ * n atoms of the molecule (sum x_i, sum g_i and sum x_i x g_i carried in float64, M - c x F formed once);  [6] max_i |g_i|
+ * (the maximum of the float64 norms, then rounded);  [7] 1 / (1 + 0.05846 N_rot), the factor that turns d inter / d x into
+ * d score / d x.  A molecule with a NaN or +-inf coordinate: NaN in every float of its rows of atom_grad and mol_grad, and
+ * the flag.  Sums in float64 in the order of dsbdd_vina_score's, stored as float32; no atomics, bitwise reproducible,
+ * independent of the rest of the batch; the same range checks.  batch = 0 launches nothing; null pointers and negative
+ * counts are DSBDD_ERR_ARG. */
+int dsbdd_vina_score_grad(void* stream, const float* lig_x, const int32_t* lig_code, const int32_t* mol_off, int64_t batch,
+                          const int32_t* mol_group, const int32_t* mol_int, const float* poc_x, const int32_t* poc_code,
+                          const int32_t* group_off, int64_t n_groups, float* atom_out, float* mol_out, int32_t* mol_flag,
+                          float* atom_grad, float* mol_grad);
+
 /* ---- ligands as input: the packed batch of the design front ends -------------*/
 /* One launch that writes the ligand batch of substructure inpainting and of
  * diversification (inpaint.py:114-141, optimize.py:39-62 of the reference build
