@@ -1,5 +1,5 @@
-// The parts that the graph and geometry kernels share (radius_graph.h, level_list.h, geometry.h; ddpm.h, loss_head.h,
-// score.h and train.h take single pieces): the constants of the edge-list layout, the integer wave / workgroup scans,
+// The parts that the graph and geometry kernels share (radius_graph.h, level_list.h, geometry.h; ddpm.h, loss_parts.h,
+// loss_head.h, score.h and train.h take single pieces): the constants of the edge-list layout, the integer wave / workgroup scans,
 // the three-component workgroup reduction with the per-sample mean built on it, a sample's row ranges, the pad fill
 // of a list segment and the zero fill.  One definition each: "the same bits" and "the same layout" hold by
 // construction at every site.

@@ -16,13 +16,11 @@
 //   score_cond_post_kernel  one workgroup per state: error_t (time slots), loss_0_x and loss_0_h (zero slots);
 //   score_reduce_kernel     once per call, one thread per ligand: loss_t = sum_k (k ascending) and the bound.
 //
-// Formulas and their order are those of loss_cond_pre_kernel / loss_cond_post_kernel (loss_head.h); every sum is a
-// fixed-order reduction inside the state's workgroup or a serial loop, no atomics.  Virtual atoms are not supported.
+// The formulas are those of loss_cond_pre_kernel / loss_cond_post_kernel (loss_head.h), written once in loss_parts.h; a
+// kernel here is the sequence of those steps over a state's rows.  Every sum is a fixed-order reduction inside the state's
+// workgroup or a serial loop, no atomics.  Virtual atoms are not supported.
 #pragma once
-#include "common.h"
-#include "ddpm.h"
-#include "graph_parts.h"   // lower_bound_i64
-#include "loss_head.h"
+#include "loss_parts.h"    // LossCfg, kLossThreads and every formula
 
 namespace dsbdd {
 
@@ -55,6 +53,28 @@ __device__ __forceinline__ ScoreRows score_rows_of(const LossCfg& c, const Score
   return r;
 }
 
+// the "state fits the chunk" predicate: workgroup-uniform, and in front of every block_sum of the four kernels
+__device__ __forceinline__ bool score_rows_fit(const ScoreChunk& s, const ScoreRows& r) {
+  return r.ol >= 0 && r.op >= 0 && r.ol + r.nl <= s.cap_lig && r.op + r.np <= s.cap_pocket;
+}
+
+// one thread of a pre kernel: the state's t and its rows SS_T .. SS_SNR_W (the joint kernels' SJ_T .. SJ_SNR_W are the same
+// rows); a state that does not fit gets NaN in gamma_t and SNR_weight
+__device__ __forceinline__ void write_state_scalars(const Schedule& sc, bool zero_slot, bool fits, int S, int g, int j, float* t_out,
+                                                    float* ps) {
+  const float bad = fits ? 0.0f : NAN;
+  t_out[j] = sc.tt;
+  ps[SS_T * S + g] = sc.tt; ps[SS_GAMMA_T * S + g] = sc.g_t + bad;
+  ps[SS_ALPHA_T * S + g] = sc.alpha_t; ps[SS_SIGMA_T * S + g] = sc.sigma_t;
+  ps[SS_SNR_W * S + g] = zero_slot ? 0.0f : snr_weight(sc) + bad;
+}
+// one thread of a pre kernel, on a ligand's slot 0: the per-ligand rows
+__device__ __forceinline__ void write_ligand_terms(const LossCfg& c, int b, float dof, float g_0, float kl, float lpn, float* pl) {
+  const int B = c.batch;
+  pl[SL_NEG_LOG_C * B + b] = neg_log_constants(dof, g_0); pl[SL_KL * B + b] = kl;
+  pl[SL_LOG_PN * B + b] = lpn; pl[SL_DELTA_LOG_PX * B + b] = delta_log_px(dof, c.nv0);
+}
+
 __global__ __launch_bounds__(kLossThreads) void score_cond_pre_kernel(
     LossCfg c, ScoreChunk s, const float* lig_x, const float* lig_h, const long long* lig_mask, const float* poc_x,
     const float* poc_h, const long long* poc_mask, const float* eps, const float* t_int, const float* gamma_table,
@@ -66,39 +86,26 @@ __global__ __launch_bounds__(kLossThreads) void score_cond_pre_kernel(
   const int a = c.atom_nf, r = c.residue_nf, ldl = 3 + a, ldp = 3 + r;
   if (t == 0) rows = score_rows_of(c, s, g, lig_mask, poc_mask);
   __syncthreads();
-  const int b = rows.b, l0 = rows.l0, nl = rows.nl, p0 = rows.p0, np = rows.np, ol = rows.ol, op = rows.op;
-  const int l1 = l0 + nl, p1 = p0 + np, S = s.n_states;
+  const int l0 = rows.l0, nl = rows.nl, p0 = rows.p0, np = rows.np, ol = rows.ol, op = rows.op;
+  const int l1 = l0 + nl, p1 = p0 + np;
   const bool zero_slot = rows.k == s.n_slots - 1;
   const float inv0 = 1.0f / c.nv0, inv1 = 1.0f / c.nv1;          // normalize(): a division by a python scalar multiplies by its inverse
-  const float cnt = (float)(nl > 1 ? nl : 1);                     // seg_mean: count clamped to >= 1
-
-  // per-state scalars (forward(): t, s, gamma; alpha / sigma); the zero slot is the separate pass at t = 0 (:285-302)
-  const float ti = zero_slot ? 0.0f : t_int[g];
-  const float tt = ti / (float)c.T, ss = (ti - 1.0f) / (float)c.T;
-  const float g_t = gamma_at(gamma_table, c.T, tt), g_s = gamma_at(gamma_table, c.T, ss);
-  const float alpha_t = sqrtf(sigmoid_ref(-g_t)), sigma_t = sqrtf(sigmoid_ref(g_t));
-  const bool fits = ol >= 0 && op >= 0 && ol + nl <= s.cap_lig && op + np <= s.cap_pocket;
-  if (t == 0) {
-    const float bad = fits ? 0.0f : NAN;
-    t_out[j] = tt;
-    ps[SS_T * S + g] = tt; ps[SS_GAMMA_T * S + g] = g_t + bad;
-    ps[SS_ALPHA_T * S + g] = alpha_t; ps[SS_SIGMA_T * S + g] = sigma_t;
-    ps[SS_SNR_W * S + g] = zero_slot ? 0.0f : (1.0f - expf(-(g_s - g_t))) + bad;         // 1 - SNR(gamma_s - gamma_t)
-  }
+  const float cnt = seg_count(nl);
+  // the zero slot is the separate pass at t = 0 (:285-302)
+  const Schedule sc = schedule_at(gamma_table, c.T, zero_slot ? 0.0f : t_int[g]);
+  const bool fits = score_rows_fit(s, rows);
+  if (t == 0) write_state_scalars(sc, zero_slot, fits, s.n_states, g, j, t_out, ps);
   if (!fits) return;
 
   // 1. ligand centre of mass of the normalised coordinates (_remove_lig_com)
-  float m1[3] = {0.f, 0.f, 0.f};
-  if (c.remove_com) {
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    for (int i = l0 + t; i < l1; i += kLossThreads) { s0 += lig_x[3 * i] * inv0; s1 += lig_x[3 * i + 1] * inv0; s2 += lig_x[3 * i + 2] * inv0; }
-    m1[0] = block_sum(s0, red) / cnt; m1[1] = block_sum(s1, red) / cnt; m1[2] = block_sum(s2, red) / cnt;
-  }
+  float m1[3];
+  cond_lig_centre(c, inv0, lig_x, l0, l1, cnt, red, m1);
   // 2. the centre of mass of the noised coordinates (noised_representation)
   float m2[3] = {0.f, 0.f, 0.f};
   if (c.remove_com) {
     float z0 = 0.f, z1 = 0.f, z2 = 0.f;
-    for (int i = l0 + t; i < l1; i += kLossThreads) {
+    const float alpha_t = sc.alpha_t, sigma_t = sc.sigma_t;
+    for (int i = l0 + t; i < l1; i += kLossThreads) {             // (written out: see pass 2 of loss_cond_pre_kernel)
       const float* er = eps + (size_t)(ol + i - l0) * ldl;
 #pragma unroll
       for (int d = 0; d < 3; ++d) {
@@ -107,64 +114,30 @@ __global__ __launch_bounds__(kLossThreads) void score_cond_pre_kernel(
         if (d == 0) z0 += v; else if (d == 1) z1 += v; else z2 += v;
       }
     }
-    m2[0] = block_sum(z0, red) / cnt; m2[1] = block_sum(z1, red) / cnt; m2[2] = block_sum(z2, red) / cnt;
+    block_mean3(z0, z1, z2, cnt, red, m2);
   }
   // 3. z of the state, its mask rows
   for (int i = l0 + t; i < l1; i += kLossThreads) {
     const size_t o = (size_t)(ol + i - l0);
-    const float* er = eps + o * ldl;
-    float* zr = z + o * ldl;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      const float x = lig_x[3 * i + d] * inv0 - m1[d];
-      zr[d] = (alpha_t * x + sigma_t * er[d]) - m2[d];
-    }
-    for (int k = 0; k < a; ++k) {
-      const float h = (lig_h[(size_t)i * a + k] - c.nb1) * inv1;
-      zr[3 + k] = alpha_t * h + sigma_t * er[3 + k];
-    }
+    cond_z_row<false>(c, inv0, inv1, lig_x + 3 * i, lig_h + (size_t)i * a, eps + o * ldl, a, m1, m2, sc.alpha_t, sc.sigma_t,
+                      z + o * ldl, nullptr, nullptr);
     mask_l[o] = j;
   }
   // 4. the state's own copy of the pocket: normalised, shifted by both ligand centres
   for (int i = p0 + t; i < p1; i += kLossThreads) {
     const size_t o = (size_t)(op + i - p0);
-    float* pr = xh_pocket + o * ldp;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) pr[d] = ((poc_x[3 * i + d] * inv0) - m1[d]) - m2[d];
-    for (int k = 0; k < r; ++k) pr[3 + k] = (poc_h[(size_t)i * r + k] - c.nb1) * inv1;
+    cond_pocket_row(c, inv0, inv1, poc_x + 3 * i, poc_h + (size_t)i * r, r, m1, m2, xh_pocket + o * ldp, nullptr, nullptr);
     mask_p[o] = j;
   }
   // 5. the per-ligand terms, once per ligand: on its slot 0
   if (rows.k != 0) return;
-  const float g_T = gamma_table[c.T], g_0 = gamma_table[0];
-  const float alpha_T = sqrtf(sigmoid_ref(-g_T)), sigma_T = sqrtf(sigmoid_ref(g_T));
+  const PriorEnds e = prior_ends(gamma_table, c.T);
   float sx = 0.f, sh = 0.f;
-  for (int i = l0 + t; i < l1; i += kLossThreads) {
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      const float x = lig_x[3 * i + d] * inv0 - m1[d];
-      const float mu = alpha_T * x;
-      sx += mu * mu;
-    }
-    for (int k = 0; k < a; ++k) {
-      const float h = (lig_h[(size_t)i * a + k] - c.nb1) * inv1;
-      const float mu = alpha_T * h;
-      sh += mu * mu;
-    }
-  }
+  for (int i = l0 + t; i < l1; i += kLossThreads) kl_row(c, inv0, inv1, lig_x + 3 * i, lig_h + (size_t)i * a, a, m1, e.alpha_T, sx, sh);
   sx = block_sum(sx, red); sh = block_sum(sh, red);
   if (t == 0) {
-    const int B = c.batch;
-    const float dof = c.remove_com ? (float)((nl - 1) * 3) : (float)(nl * 3);       // subspace_dimensionality
-    pl[SL_NEG_LOG_C * B + b] = -(dof * (-(0.5f * g_0) - 0.91893853320467274178f));    // -log_constants_p_x_given_z0
-    // gaussian_KL(mu2, sigma_T, 1, d) = d log(1 / sigma_T) + 0.5 (d sigma_T^2 + mu2) - 0.5 d;  d = dof for x, 1 for h
-    const float lq = logf(1.0f / sigma_T), q2 = sigma_T * sigma_T;
-    const float kl_x = dof * lq + 0.5f * (dof * q2 + sx) - 0.5f * dof;
-    const float kl_h = lq + 0.5f * (q2 + sh) - 0.5f;
-    pl[SL_KL * B + b] = kl_x + kl_h;
-    // log p(N_lig | N_pocket); the host refuses sizes outside the table before any launch (no clamp: NaN here)
-    pl[SL_LOG_PN * B + b] = (nl < c.n1_tab && np < c.n2_tab) ? logpn_table[(size_t)nl * c.n2_tab + np] : NAN;
-    pl[SL_DELTA_LOG_PX * B + b] = -dof * logf(c.nv0);
+    const float dof = cond_dof(c, nl);
+    write_ligand_terms(c, rows.b, dof, e.g_0, kl_prior_contracted(sx, sh, e.sigma_T, dof), log_pn_or_nan(c, logpn_table, nl, np), pl);
   }
 }
 
@@ -176,36 +149,37 @@ __global__ __launch_bounds__(kLossThreads) void score_cond_post_kernel(
     const float* eps, const float* z, float* ps) {
   __shared__ float red[kLossThreads];
   __shared__ ScoreRows rows;
-  const int j = blockIdx.x, t = threadIdx.x, g = s.first + j, a = c.atom_nf, ld = 3 + a, S = s.n_states;
+  const int j = blockIdx.x, t = threadIdx.x, g = s.first + j, a = c.atom_nf, S = s.n_states;
   if (t == 0) rows = score_rows_of(c, s, g, lig_mask, poc_mask);
   __syncthreads();
-  const int l0 = rows.l0, nl = rows.nl, ol = rows.ol;
+  const int nl = rows.nl, ol = rows.ol;
   const bool zero_slot = rows.k == s.n_slots - 1;
-  const bool fits = ol >= 0 && rows.op >= 0 && ol + nl <= s.cap_lig && rows.op + rows.np <= s.cap_pocket;
-  if (!fits) {
+  if (!score_rows_fit(s, rows)) {
     if (t == 0) { ps[SS_ERR_T * S + g] = NAN; ps[SS_L0_X * S + g] = NAN; ps[SS_L0_H * S + g] = NAN; }
     return;
   }
-  const float inv1 = 1.0f / c.nv1, sig_cat = ps[SS_SIGMA_T * S + g] * c.nv1;
-  float e_all = 0.f, e_x = 0.f, lh = 0.f;
-  for (int i = t; i < nl; i += kLossThreads) {
-    const size_t o = (size_t)(ol + i) * ld;
-    float sx_ = 0.f, sa = 0.f;
-    for (int k = 0; k < ld; ++k) {
-      const float d = eps[o + k] - net[o + k];
-      const float sq = d * d;
-      sa += sq;
-      if (k < 3) sx_ += sq;
-    }
-    e_all += sa; e_x += sx_;
-    if (zero_slot) lh += joint_cat_row(z + o + 3, lig_h + (size_t)(l0 + i) * a, a, c.nv1, c.nb1, inv1, sig_cat);
-  }
-  e_all = block_sum(e_all, red); e_x = block_sum(e_x, red); lh = block_sum(lh, red);
+  ErrorSums e{0.f, 0.f, 0.f, 0.f};
+  error_rows<false>(c, ol, ol + nl, a, net, eps, nullptr, e);
+  float lh = zero_slot ? cat_rows(c, rows.l0, nl, ol, a, z, lig_h, ps[SS_SIGMA_T * S + g] * c.nv1) : 0.f;
+  const float e_all = block_sum(e.all, red), e_x = block_sum(e.x, red);
+  lh = block_sum(lh, red);
   if (t == 0) {
     ps[SS_ERR_T * S + g] = zero_slot ? 0.0f : e_all;
     ps[SS_L0_X * S + g] = zero_slot ? 0.5f * e_x : 0.0f;
     ps[SS_L0_H * S + g] = zero_slot ? -lh : 0.0f;
   }
+}
+
+// the tail of the two reduce kernels (callers and this: every operation rounded on its own): the four per-ligand rows pass
+// through to out_tail = the rows of out from neg_log_constants on; returns
+// nll = (((loss_t + (l0 + neg_log_constants)) + kl_prior) - delta_log_px) - log_pN, left to right
+static_assert(SO_KL == SO_NEG_LOG_C + 1 && SO_DELTA_LOG_PX == SO_NEG_LOG_C + 2 && SO_LOG_PN == SO_NEG_LOG_C + 3, "out_tail");
+__device__ __forceinline__ float reduce_tail(float loss_t, float l0, const float* pl, int B, int b, float* out_tail) {
+#pragma clang fp contract(off)
+  const float nlc = pl[SL_NEG_LOG_C * B + b], kl = pl[SL_KL * B + b], dlp = pl[SL_DELTA_LOG_PX * B + b], lpn = pl[SL_LOG_PN * B + b];
+  const float loss_0 = l0 + nlc;
+  out_tail[b] = nlc; out_tail[B + b] = kl; out_tail[2 * B + b] = dlp; out_tail[3 * B + b] = lpn;
+  return (((loss_t + loss_0) + kl) - dlp) - lpn;
 }
 
 // loss_t(b) = sum_k w[b][k] (-0.5 SNR_weight error_t)  (k ascending, float32; a term is ((-0.5 w) SNR_weight) error_t, the
@@ -222,13 +196,9 @@ __global__ void score_reduce_kernel(int B, int n_slots, const float* weights, co
     loss_t += ((-0.5f * weights[g]) * ps[SS_SNR_W * S + g]) * ps[SS_ERR_T * S + g];
   }
   const float l0x = ps[SS_L0_X * S + gz], l0h = ps[SS_L0_H * S + gz];
-  const float nlc = pl[SL_NEG_LOG_C * B + b], kl = pl[SL_KL * B + b], dlp = pl[SL_DELTA_LOG_PX * B + b], lpn = pl[SL_LOG_PN * B + b];
-  const float loss_0 = (l0x + l0h) + nlc;
-  out[SO_NLL * B + b] = (((loss_t + loss_0) + kl) - dlp) - lpn;
+  out[SO_NLL * B + b] = reduce_tail(loss_t, l0x + l0h, pl, B, b, out + SO_NEG_LOG_C * B);
   out[SO_LOSS_T * B + b] = loss_t;
   out[SO_L0_X * B + b] = l0x; out[SO_L0_H * B + b] = l0h;
-  out[SO_NEG_LOG_C * B + b] = nlc; out[SO_KL * B + b] = kl;
-  out[SO_DELTA_LOG_PX * B + b] = dlp; out[SO_LOG_PN * B + b] = lpn;
 }
 
 }  // namespace dsbdd

@@ -1,6 +1,6 @@
 // C-ABI entry points of training (included by engine.hip): argument checks around the building blocks (train_blocks.h)
 // and the network walk (train_net.h), then the native training loop around the network call: the loss terms of the
-// pocket-conditioned step (loss_head.h), the likelihood bound of given ligands (score.h, score_joint.h), the fused clipping + AdamW step (optim.h), the auxiliary LJ loss (lj_loss.h).
+// pocket-conditioned step (loss_head.h), the likelihood bound of given ligands (score.h, score_joint.h; all three over loss_parts.h), the fused clipping + AdamW step (optim.h), the auxiliary LJ loss (lj_loss.h).
 #pragma once
 
 static LossCfg loss_cfg_of(const dsbdd_loss_cfg* c) {
@@ -291,12 +291,16 @@ int dsbdd_loss_joint_post_backward(void* stream, const dsbdd_loss_cfg* cfg, cons
 }
 
 // ---- likelihood bound of given ligands (score.h) --------------------------------------------------------------------------
-static bool score_chunk_ok(const dsbdd_loss_cfg* c, int32_t n_slots, int64_t first_state, int64_t chunk_states, int64_t cap_lig,
-                           int64_t cap_pocket) {
-  if (!loss_cfg_ok(c) || c->vnode_idx >= 0 || n_slots < 2) return false;
-  const int64_t n_states = (int64_t)c->batch * n_slots;
-  return n_states < (1ll << 31) && first_state >= 0 && chunk_states >= 1 && first_state + chunk_states <= n_states &&
-         cap_lig >= 0 && cap_pocket >= 0 && cap_lig < (1ll << 24) && cap_pocket < (1ll << 24);
+// the chunk of the four score entry points: DSBDD_OK and *ch, or the error
+static int score_chunk_of(const dsbdd_loss_cfg* c, int32_t n_slots, int64_t first_state, int64_t chunk_states, int64_t cap_lig,
+                          int64_t cap_pocket, ScoreChunk* ch) {
+  const int64_t n_states = loss_cfg_ok(c) ? (int64_t)c->batch * n_slots : 0;
+  if (!loss_cfg_ok(c) || c->vnode_idx >= 0 || n_slots < 2 || n_states >= (1ll << 31) || first_state < 0 || chunk_states < 1 ||
+      first_state + chunk_states > n_states || cap_lig < 0 || cap_pocket < 0 || cap_lig >= (1ll << 24) || cap_pocket >= (1ll << 24))
+    return fail(DSBDD_ERR_ARG, "bad configuration or chunk (virtual atoms are not supported; n_slots >= 2; the chunk lies inside "
+                               "the batch * n_slots states)");
+  *ch = ScoreChunk{n_slots, (int)first_state, (int)n_states, (int)cap_lig, (int)cap_pocket};
+  return DSBDD_OK;
 }
 
 int dsbdd_score_rows(int32_t which) { return which == 0 ? SS_ROWS : which == 1 ? SL_ROWS : which == 2 ? SO_ROWS : 0; }
@@ -307,14 +311,12 @@ int dsbdd_score_cond_pre(void* stream, const dsbdd_loss_cfg* cfg, int32_t n_slot
                          const float* t_int, const float* gamma_table, const float* logpn_table, float* z, float* xh_pocket,
                          int64_t* mask_lig_out, int64_t* mask_pocket_out, float* t_out, float* per_state, float* per_ligand) {
   StreamDevice stream_device_(stream);
-  if (!score_chunk_ok(cfg, n_slots, first_state, chunk_states, cap_lig, cap_pocket))
-    return fail(DSBDD_ERR_ARG, "bad configuration or chunk (virtual atoms are not supported; n_slots >= 2; the chunk lies inside "
-                               "the batch * n_slots states)");
+  ScoreChunk ch;
+  if (const int err = score_chunk_of(cfg, n_slots, first_state, chunk_states, cap_lig, cap_pocket, &ch)) return err;
   if (!t_int || !gamma_table || !logpn_table || cfg->n1_tab < 1 || cfg->n2_tab < 1 || !t_out || !per_state || !per_ligand ||
       (cfg->n_lig > 0 && (!lig_x || !lig_h || !lig_mask || !eps || !z || !mask_lig_out)) ||
       (cfg->n_pocket > 0 && (!pocket_x || !pocket_h || !pocket_mask || !xh_pocket || !mask_pocket_out)))
     return fail(DSBDD_ERR_ARG, "null argument");
-  const ScoreChunk ch{n_slots, (int)first_state, cfg->batch * n_slots, (int)cap_lig, (int)cap_pocket};
   hipLaunchKernelGGL(score_cond_pre_kernel, dim3((unsigned)chunk_states), dim3(kLossThreads), 0, static_cast<hipStream_t>(stream),
                      loss_cfg_of(cfg), ch, lig_x, lig_h, reinterpret_cast<const long long*>(lig_mask), pocket_x, pocket_h,
                      reinterpret_cast<const long long*>(pocket_mask), eps, t_int, gamma_table, logpn_table, z, xh_pocket,
@@ -328,12 +330,10 @@ int dsbdd_score_cond_post(void* stream, const dsbdd_loss_cfg* cfg, int32_t n_slo
                           int64_t cap_lig, int64_t cap_pocket, const float* lig_h, const int64_t* lig_mask,
                           const int64_t* pocket_mask, const float* net, const float* eps, const float* z, float* per_state) {
   StreamDevice stream_device_(stream);
-  if (!score_chunk_ok(cfg, n_slots, first_state, chunk_states, cap_lig, cap_pocket))
-    return fail(DSBDD_ERR_ARG, "bad configuration or chunk (virtual atoms are not supported; n_slots >= 2; the chunk lies inside "
-                               "the batch * n_slots states)");
+  ScoreChunk ch;
+  if (const int err = score_chunk_of(cfg, n_slots, first_state, chunk_states, cap_lig, cap_pocket, &ch)) return err;
   if (!per_state || (cfg->n_lig > 0 && (!lig_h || !lig_mask || !net || !eps || !z)) || (cfg->n_pocket > 0 && !pocket_mask))
     return fail(DSBDD_ERR_ARG, "null argument");
-  const ScoreChunk ch{n_slots, (int)first_state, cfg->batch * n_slots, (int)cap_lig, (int)cap_pocket};
   hipLaunchKernelGGL(score_cond_post_kernel, dim3((unsigned)chunk_states), dim3(kLossThreads), 0, static_cast<hipStream_t>(stream),
                      loss_cfg_of(cfg), ch, lig_h, reinterpret_cast<const long long*>(lig_mask),
                      reinterpret_cast<const long long*>(pocket_mask), net, eps, z, per_state);
@@ -362,15 +362,13 @@ int dsbdd_score_joint_pre(void* stream, const dsbdd_loss_cfg* cfg, int32_t n_slo
                           const float* logpn_table, float* eps_lig, float* eps_pocket, float* z_lig, float* z_pocket,
                           int64_t* mask_lig_out, int64_t* mask_pocket_out, float* t_out, float* per_state, float* per_ligand) {
   StreamDevice stream_device_(stream);
-  if (!score_chunk_ok(cfg, n_slots, first_state, chunk_states, cap_lig, cap_pocket))
-    return fail(DSBDD_ERR_ARG, "bad configuration or chunk (virtual atoms are not supported; n_slots >= 2; the chunk lies inside "
-                               "the batch * n_slots states)");
+  ScoreChunk ch;
+  if (const int err = score_chunk_of(cfg, n_slots, first_state, chunk_states, cap_lig, cap_pocket, &ch)) return err;
   if (!t_int || !gamma_table || !logpn_table || cfg->n1_tab < 1 || cfg->n2_tab < 1 || !t_out || !per_state || !per_ligand ||
       (cfg->n_lig > 0 && (!lig_x || !lig_h || !lig_mask || !noise_lig || !eps_lig || !z_lig || !mask_lig_out)) ||
       (cfg->n_pocket > 0 && (!pocket_x || !pocket_h || !pocket_mask || !noise_pocket || !eps_pocket || !z_pocket ||
                              !mask_pocket_out)))
     return fail(DSBDD_ERR_ARG, "null argument");
-  const ScoreChunk ch{n_slots, (int)first_state, cfg->batch * n_slots, (int)cap_lig, (int)cap_pocket};
   hipLaunchKernelGGL(score_joint_pre_kernel, dim3((unsigned)chunk_states), dim3(kLossThreads), 0, static_cast<hipStream_t>(stream),
                      loss_cfg_of(cfg), ch, (int)(center != 0), lig_x, lig_h, reinterpret_cast<const long long*>(lig_mask), pocket_x,
                      pocket_h, reinterpret_cast<const long long*>(pocket_mask), noise_lig, noise_pocket, t_int, gamma_table,
@@ -385,13 +383,11 @@ int dsbdd_score_joint_post(void* stream, const dsbdd_loss_cfg* cfg, int32_t n_sl
                            const int64_t* pocket_mask, const float* net_lig, const float* net_pocket, const float* eps_lig,
                            const float* eps_pocket, const float* z_lig, const float* z_pocket, float* per_state) {
   StreamDevice stream_device_(stream);
-  if (!score_chunk_ok(cfg, n_slots, first_state, chunk_states, cap_lig, cap_pocket))
-    return fail(DSBDD_ERR_ARG, "bad configuration or chunk (virtual atoms are not supported; n_slots >= 2; the chunk lies inside "
-                               "the batch * n_slots states)");
+  ScoreChunk ch;
+  if (const int err = score_chunk_of(cfg, n_slots, first_state, chunk_states, cap_lig, cap_pocket, &ch)) return err;
   if (!per_state || (cfg->n_lig > 0 && (!lig_h || !lig_mask || !net_lig || !eps_lig || !z_lig)) ||
       (cfg->n_pocket > 0 && (!pocket_h || !pocket_mask || !net_pocket || !eps_pocket || !z_pocket)))
     return fail(DSBDD_ERR_ARG, "null argument");
-  const ScoreChunk ch{n_slots, (int)first_state, cfg->batch * n_slots, (int)cap_lig, (int)cap_pocket};
   hipLaunchKernelGGL(score_joint_post_kernel, dim3((unsigned)chunk_states), dim3(kLossThreads), 0, static_cast<hipStream_t>(stream),
                      loss_cfg_of(cfg), ch, lig_h, reinterpret_cast<const long long*>(lig_mask), pocket_h,
                      reinterpret_cast<const long long*>(pocket_mask), net_lig, net_pocket, eps_lig, eps_pocket, z_lig, z_pocket,
