@@ -1,5 +1,5 @@
 // Thin C-ABI wrappers of the stand-alone kernels (included by engine.hip): DDPM steps (ddpm.h), keyed noise, node GEMM,
-// the node chain's row split (chain_split.h), bond orders (molecule.h), molecule graph statistics and fingerprint distances (mol_metrics.h), pose checks, the Vina-type score and its gradient (pose_check.h, vina_score.h, vina_grad.h on pair_sweep.h), ligand packing (ligand_pack.h), the radius graph (radius_graph.h).
+// the node chain's row split (chain_split.h), bond orders (molecule.h), molecule graph statistics and fingerprint distances (mol_metrics.h), pose checks, the Vina-type score, its gradient and the rigid-body minimiser (pose_check.h, vina_score.h, vina_grad.h, vina_minimize.h on pair_sweep.h), ligand packing (ligand_pack.h), the radius graph (radius_graph.h).
 #pragma once
 
 extern "C" {
@@ -318,6 +318,31 @@ int dsbdd_vina_score_grad(void* stream, const float* lig_x, const int32_t* lig_c
   VinaGradArgs a{{{lig_x, mol_off, mol_group, poc_x, group_off, (int)batch, (int)n_groups}, lig_code, mol_int, poc_code,
                   atom_out, mol_out, mol_flag}, atom_grad, mol_grad};
   hipLaunchKernelGGL(vina_grad_kernel, dim3((unsigned)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_vina_minimize(void* stream, const float* lig_x, const int32_t* lig_code, const int32_t* mol_off, int64_t batch,
+                        const int32_t* mol_group, const int32_t* mol_int, const float* poc_x, const int32_t* poc_code,
+                        const int32_t* group_off, int64_t n_groups, float* atom_out, float* mol_out, int32_t* mol_flag,
+                        float* atom_grad, float* mol_grad, float step, float tol, int32_t max_evals, float* x_out,
+                        float* mol_pose, float* mol_min, int32_t* mol_stat) {
+  StreamDevice stream_device_(stream);
+  if (!lig_x || !lig_code || !mol_off || !mol_group || !mol_int || !poc_x || !poc_code || !group_off || !atom_out ||
+      !mol_out || !mol_flag || !atom_grad || !mol_grad || !x_out || !mol_pose || !mol_min || !mol_stat)
+    return fail(DSBDD_ERR_ARG, "null argument");
+  if (int rc = check_pair_counts(batch, n_groups)) return rc;
+  if (!std::isfinite(step) || !(step > 0.f) || !std::isfinite(tol) || !(tol > 0.f))
+    return fail(DSBDD_ERR_ARG, "step and tol must be finite and positive");
+  if (max_evals < 1 || max_evals > kVinaMaxEvals)
+    return fail(DSBDD_ERR_ARG, "max_evals must be in [1, " + std::to_string(kVinaMaxEvals) + "]");
+  if (batch == 0) return DSBDD_OK;                                  // nothing is read or written
+  if (lig_x == x_out) return fail(DSBDD_ERR_ARG, "lig_x and x_out must not alias");
+  // the sweep reads the pose under evaluation from x_out
+  VinaMinArgs a{{{{x_out, mol_off, mol_group, poc_x, group_off, (int)batch, (int)n_groups}, lig_code, mol_int, poc_code,
+                  atom_out, mol_out, mol_flag}, atom_grad, mol_grad}, lig_x, step, tol, max_evals, x_out, mol_pose, mol_min,
+                mol_stat};
+  hipLaunchKernelGGL(vina_minimize_kernel, dim3((unsigned)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
   HIP_TRY(hipGetLastError());
   return DSBDD_OK;
 }

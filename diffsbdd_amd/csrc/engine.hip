@@ -42,6 +42,7 @@
 #include "pose_check.h"
 #include "vina_score.h"
 #include "vina_grad.h"
+#include "vina_minimize.h"
 #include "node_chain.h"
 #include "node_linear.h"
 #include "train.h"

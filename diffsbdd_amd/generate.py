@@ -241,13 +241,21 @@ class LigandGenerator:
     @staticmethod
     def _vina_options(vina):
         """The samplers' `vina` keyword: None / False = off (nothing runs); True = on; a dict may carry 'residues' where the
-        sampler is not given any (`diversify_ligands`)."""
+        sampler is not given any (`diversify_ligands`) and 'minimize': True, or a dict of `step` / `tol` / `max_evals`, also
+        relaxes every sample as a rigid body (vina.vina_minimize) and attaches that record as `m.vina_min`."""
         if vina is None or vina is False:
             return None
         opts = {} if vina is True else dict(vina)
-        unknown = set(opts) - {"residues"}
+        unknown = set(opts) - {"residues", "minimize"}
         if unknown:
             raise ValueError(f"vina: unknown option(s) {sorted(unknown)}")
+        minimize = opts.pop("minimize", None)
+        if minimize is not None and minimize is not False:
+            settings = {} if minimize is True else dict(minimize)
+            unknown = set(settings) - {"step", "tol", "max_evals"}
+            if unknown:
+                raise ValueError(f"vina: unknown minimize setting(s) {sorted(unknown)}")
+            opts["minimize"] = settings
         return opts
 
     def _job_pockets(self, attr, residue_sets, kind, atoms_of):
@@ -284,7 +292,14 @@ class LigandGenerator:
             from . import vina as vina_mod
             sets = [vina["residues"]] if residue_sets is None else residue_sets
             pockets = self._job_pockets("_vina_pockets", sets, vina_mod.VinaPocket, vina_mod.type_pocket)
-            out["vina"] = vina_mod.vina_score(x, atom_type, lig_mask, pockets, self.dataset_info, groups, batch=batch)
+            if "minimize" not in vina:
+                out["vina"] = vina_mod.vina_score(x, atom_type, lig_mask, pockets, self.dataset_info, groups, batch=batch)
+            else:                                                    # m.vina_min; x and m.vina stay as they are
+                orders = vina_mod.perceive_orders(x, atom_type, lig_mask, self.dataset_info, batch)     # once, for both entries
+                out["vina"] = vina_mod.vina_score(x, atom_type, lig_mask, pockets, self.dataset_info, groups, batch=batch,
+                                                  orders=orders)
+                out["vina_min"] = vina_mod.vina_minimize(x, atom_type, lig_mask, pockets, self.dataset_info, groups, batch=batch,
+                                                         orders=orders, **vina["minimize"])
         return out
 
     def _scope_residues(self, pdb_file, scope, pocket_ids, ref_ligand):
@@ -317,6 +332,20 @@ class LigandGenerator:
         residues = self._scope_residues(pdb_file, scope, pocket_ids, ref_ligand)
         pockets = vina_mod.VinaPocket.upload([vina_mod.type_pocket(residues)], self.device)
         return [dict(r.as_dict(), grad=r.grad) for r in vina_mod.gradient_molecules(molecules, pockets, self.dataset_info)]
+
+    @torch.no_grad()
+    def vina_minimize(self, pdb_file, molecules, pocket_ids=None, ref_ligand=None, scope="protein", **settings):
+        """`vina_gradients` after a rigid-body relaxation of every molecule in the protein under the score's `inter` term,
+        one launch for all of them (vina.py: `minimize_molecules`; `settings`: `step`, `tol`, `max_evals`).  The same
+        arguments.  Returns one dict per molecule, in order: the keys of `vina_gradients` at the returned pose, 'x'
+        (float32 [n, 3], its heavy-atom coordinates), 'inter_start', 'score_start', 'status' (index into `vina.STATUS`),
+        'evals', 'accepted', 'rmsd'.  See `vina.VINA_MIN_COVERAGE`: rigid ligand, rigid protein, a local search, not smina
+        or qvina output."""
+        from . import vina as vina_mod
+        residues = self._scope_residues(pdb_file, scope, pocket_ids, ref_ligand)
+        pockets = vina_mod.VinaPocket.upload([vina_mod.type_pocket(residues)], self.device)
+        return [dict(r.as_dict(), grad=r.grad, x=r.x)
+                for r in vina_mod.minimize_molecules(molecules, pockets, self.dataset_info, **settings)]
 
     @torch.no_grad()
     def check_poses(self, pdb_file, molecules, pocket_ids=None, ref_ligand=None, scope="protein", tol=None, contact=None):

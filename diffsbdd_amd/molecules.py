@@ -67,6 +67,8 @@ class Molecule:
             m.pose = self.pose.subset(keep)
         if hasattr(self, "vina"):                     # score record (vina.MolVina): the kept atoms' rows, sums and rotors recomputed
             m.vina = self.vina.subset(keep, bonds)
+        if hasattr(self, "vina_min"):                 # relaxation record (vina.MolVinaMin) of the whole sample, as it is
+            m.vina_min = self.vina_min
         return m
 
     def valences(self):
@@ -173,17 +175,19 @@ def bond_orders(x, atom_type, lig_mask, info, n_max=None, batch=None):
     return out, sizes
 
 
-def build_molecules(x, atom_type, lig_mask, info, largest_frag=False, batch=None, pose=None, vina=None):
+def build_molecules(x, atom_type, lig_mask, info, largest_frag=False, batch=None, pose=None, vina=None, vina_min=None):
     """Batch version of `build_molecule(..., use_openbabel=False)` +
     `process_molecule(largest_frag=...)` (molecule_builder.py:140-160, 162-214):
     list of `Molecule`, one per sample, in sample order.  `pose`: the `pose.PoseStats` of the same batch; every
     molecule then carries its record as `m.pose` (a fragment: the record of its atoms).  `vina`: the `vina.VinaScores` of
-    the same batch, attached as `m.vina` in the same way."""
+    the same batch, attached as `m.vina` in the same way.  `vina_min`: the `vina.VinaMinimized` of the same batch, attached
+    as `m.vina_min` (a fragment keeps the record of the whole sample: the relaxation moved the sample as one rigid body)."""
     if isinstance(info, str):
         info = dataset_info(info)
     orders, sizes = bond_orders(x, atom_type, lig_mask, info, batch=batch)
     poses = None if pose is None else pose.molecules()
     scores = None if vina is None else vina.molecules()
+    relaxed = None if vina_min is None else vina_min.molecules()
     orders = orders.cpu().numpy()
     sizes = sizes.cpu().numpy()
     xs = x.detach().float().cpu().numpy()
@@ -199,6 +203,8 @@ def build_molecules(x, atom_type, lig_mask, info, largest_frag=False, batch=None
             m.pose = poses[b]
         if scores is not None:
             m.vina = scores[b]
+        if relaxed is not None:
+            m.vina_min = relaxed[b]
         mols.append(m.largest_fragment() if largest_frag else m)
         o += n
     return mols

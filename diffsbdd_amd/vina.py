@@ -34,8 +34,15 @@ Gradient (`vina_gradient`, `vina_energy`; one launch of `dsbdd_vina_score_grad`,
     g_i         = sum_j (sum_k WEIGHTS[k] T_k'(d_ij)) u_ij          d inter / d x_i, kcal/mol/A; a pair with r = 0 adds 0
     d score / d x_i = g_i / (1 + ROT_WEIGHT N_rot)                  typing (codes, N_rot) is constant in x
 
+Minimiser (`vina_minimize`; one launch of `dsbdd_vina_minimize`, csrc/vina_minimize.h: one workgroup per molecule iterates the
+gradient's sweep, every decision on the device; `_vina_minimize_host` states the iteration): the ligand moves as a rigid
+body, pose (T, q) from (0, identity), x_i = float32((c0 + T) + R(q) (x0_i - c0)) always from the input x0; steepest descent in
+the metric u = |F| + rho_max |M| / rho^2 with a backtracking step L (0.25 A, halved on a trial that does not lower `inter`,
+doubled back after one that does) until L < 0.001 A or 200 evaluations.  Rigid ligand, rigid protein, local: VINA_MIN_COVERAGE.
+
   python -m diffsbdd_amd.vina --pdbfile P.pdb --sdf L.sdf [L2.sdf ...] [--scope protein|pocket --ref_ligand ...]
                               [--bonds distance|file] [--dataset crossdock] [--out scores.csv] [--grad_out atoms.csv]
+                              [--minimize relaxed.sdf [--step 0.25] [--tol 0.001] [--max_evals 200]]
 """
 from __future__ import annotations
 
@@ -67,6 +74,12 @@ M_INTER, M_SCORE = 5, 6
 I_TYPED, I_UNTYPED, I_ROT = 0, 1, 2
 ATOM_GRAD, MOL_GRAD = 3, 8            # columns of the gradient outputs of dsbdd_vina_score_grad
 G_NET, G_MOMENT, G_MAX, G_ROT = slice(0, 3), slice(3, 6), 6, 7
+MOL_POSE, MOL_MIN, MOL_STAT = 8, 4, 4  # columns of the minimiser's outputs (dsbdd_vina_minimize)
+P_SHIFT, P_QUAT, P_RHO2 = slice(0, 3), slice(3, 7), 7
+E_START, E_FINAL, E_STEP, E_SLOPE = range(4)
+S_STATUS, S_EVALS, S_ACCEPTED = range(3)
+STATUS = ("budget", "converged", "no gradient", "nonfinite")
+MIN_STEP, MIN_TOL, MIN_EVALS, MAX_EVALS = 0.25, 1e-3, 200, 4096
 EPS32 = 2.0 ** -24
 _RADIUS = np.asarray([0.0] + [XS_RADII[c] for c in CLASSES[1:]], np.float64)
 _LIPSCHITZ = (1.716, 0.429, None, 1.0, 1.0 / 0.7)                                # of the five terms in d (repulsion: 2 |d| + 2 dd)
@@ -102,6 +115,20 @@ VINA_GRAD_COVERAGE = (
     "is, at the 8 A cutoff (a jump of the score that the gradient ignores) and at the kinks of the repulsion, hydrophobic and "
     "hbond terms; NOT smina's minimiser and not a minimiser at all: no search, no line search, no pose is changed; "
     "no intramolecular term.")
+
+VINA_MIN_COVERAGE = (
+    "Vina-type minimiser: PRESENT = a rigid-body relaxation of every given pose under the intermolecular term `inter` of the "
+    "Vina-type score, one GPU launch per batch (one workgroup per molecule, every evaluation and decision on the device): the "
+    "pose moves by a translation and a rotation about its centroid, and the score, its terms and its gradient are reported at "
+    "the returned pose together with the score at the start, the number of evaluations, a status and the RMSD moved; "
+    "DEFINED AS = steepest descent in a scaled metric (the net force and the moment about the centroid divided by the "
+    "ligand's mean squared radius) with a backtracking step: from 0.25 A (--step) the step halves when a trial does not lower "
+    "`inter` and doubles back after one that does, until it falls below 0.001 A (--tol) or 200 evaluations (--max_evals) "
+    "are spent; "
+    "NOT = a docking run: the ligand is rigid (no torsions), the protein is rigid, the search is local (one start, the "
+    "nearest minimum downhill, no global search, no multiple starts), steepest descent and not BFGS, no intramolecular "
+    "term; NOT the output of smina or qvina and NOT comparable with their minimised or docked scores; typing is done once, "
+    "on the input pose.")
 
 
 def class_of(symbol):
@@ -462,6 +489,68 @@ class VinaGradients(VinaScores):
                 for b, m in enumerate(VinaScores.molecules(self))]
 
 
+@dataclass
+class MolVinaMin(MolVinaGrad):
+    """`MolVinaGrad` at the pose the minimiser returned for one molecule (host arrays), with that pose."""
+    x: np.ndarray = None          # float32 [n, 3]: the returned coordinates
+    pose: np.ndarray = None       # float [8]: T (3), q (4, w first), rho^2
+    energies: np.ndarray = None   # float [4]: inter at the start, at the end, the last accepted step (0 if none), u at the end
+    stat: np.ndarray = None       # int32 [4]: status (index into STATUS), evaluations, accepted steps, 0
+    rmsd: float = 0.0             # heavy-atom RMSD between the input and the returned coordinates
+
+    status = property(lambda self: int(self.stat[S_STATUS]))
+    evals = property(lambda self: int(self.stat[S_EVALS]))
+    accepted = property(lambda self: int(self.stat[S_ACCEPTED]))
+    inter_start = property(lambda self: float(self.energies[E_START]))
+    score_start = property(lambda self: float(self.energies[E_START]) * self.rot_factor)
+
+    def as_dict(self):
+        out = super().as_dict()
+        out.update(inter_start=self.inter_start, score_start=self.score_start, status=self.status, evals=self.evals,
+                   accepted=self.accepted, rmsd=float(self.rmsd))
+        return out
+
+
+@dataclass
+class VinaMinimized(VinaGradients):
+    """`VinaGradients` at the poses the minimiser returned (device tensors from `vina_minimize`, numpy arrays from
+    `_vina_minimize_host`), with the poses."""
+    x: object = None         # float32 [N, 3]: the returned coordinates
+    pose: object = None      # float [B, 8]: T (3), q (4, w first), rho^2
+    energies: object = None  # float [B, 4]: inter at the start, at the end, the last accepted step (0 if none), u at the end
+    stat: object = None      # int32 [B, 4]: status (index into STATUS), evaluations, accepted steps, 0
+    x_in: object = None      # float32 [N, 3]: the input coordinates
+
+    status = property(lambda self: self.stat[:, S_STATUS])
+    evals = property(lambda self: self.stat[:, S_EVALS])
+    accepted = property(lambda self: self.stat[:, S_ACCEPTED])
+    inter_start = property(lambda self: self.energies[:, E_START])
+    score_start = property(lambda self: self.energies[:, E_START] * self.rot_factor)
+
+    @property
+    def rmsd(self):
+        """[B] the heavy-atom RMSD between input and returned coordinates (0 for a molecule without atoms; torch on the
+        device for device tensors, no read-back)."""
+        off, mol = self.mol_off, self.atom_mol
+        if torch.is_tensor(self.x):
+            d2 = ((self.x.double() - self.x_in.double()) ** 2).sum(1)
+            total = torch.zeros(len(off) - 1, dtype=torch.float64, device=d2.device).index_add_(0, mol, d2)
+            return torch.sqrt(total / (off[1:] - off[:-1]).clamp(min=1).double())
+        with np.errstate(invalid="ignore", over="ignore"):
+            d2 = ((self.x.astype(np.float64) - self.x_in.astype(np.float64)) ** 2).sum(1)
+        total = np.zeros(len(off) - 1)
+        np.add.at(total, mol, d2)
+        return np.sqrt(total / np.maximum(np.diff(off), 1))
+
+    def molecules(self):
+        """One `MolVinaMin` per molecule, in order (one copy of each tensor to the host)."""
+        x, pose, energies, stat, rmsd, off = (_np(v) for v in (self.x, self.pose, self.energies, self.stat, self.rmsd,
+                                                               self.mol_off))
+        return [MolVinaMin(m.mol, m.ints, m.atom, m.code, m.nonfinite, m.grad, m.mol_grad, x[off[b]:off[b + 1]].copy(),
+                           pose[b].copy(), energies[b].copy(), stat[b].copy(), float(rmsd[b]))
+                for b, m in enumerate(VinaGradients.molecules(self))]
+
+
 # ---- the device path ---------------------------------------------------------------------------------------------------------
 def type_ligands(x, atom_type, lig_mask, info, orders=None, batch=None):
     """Atom codes and rotor counts of a batch on the device: `molecules.bond_orders` (unless `orders` int8 [B, n_max, n_max]
@@ -486,15 +575,8 @@ def type_ligands(x, atom_type, lig_mask, info, orders=None, batch=None):
     code, mol_int = torch.zeros(N, **i32), torch.zeros((B, MOL_INT), **i32)
     if B == 0:
         return code, mol_int, off
-    if orders is None and N == 0:
-        orders = torch.zeros((B, 1, 1), dtype=torch.int8, device=dev)
     if orders is None:
-        if not isinstance(info, dict) or "bonds1" not in info:
-            raise ValueError("bond perception needs the dataset (its name or dict), not the decoder alone")
-        from .molecules import bond_orders
-        orders, _ = bond_orders(x, at, lig_mask, info, batch=B)
-        if orders.shape[1] > _lib.MOL_MAX_ATOMS:                    # the block of the first 128 atoms of every molecule
-            orders = orders[:, :_lib.MOL_MAX_ATOMS, :_lib.MOL_MAX_ATOMS].contiguous()
+        orders = _perceived_orders(x, at, lig_mask, info, B)
     else:
         orders = torch.as_tensor(orders, device=dev).to(torch.int8).contiguous()
     if orders.dim() != 3 or orders.shape[0] != B or orders.shape[1] != orders.shape[2] or \
@@ -508,6 +590,31 @@ def type_ligands(x, atom_type, lig_mask, info, orders=None, batch=None):
     return code, mol_int, off
 
 
+def _perceived_orders(x, at, lig_mask, info, B):
+    """The bond-order matrices `type_ligands` types from when none are given: `molecules.bond_orders` with the tables of the
+    dataset `info` (its dict), cut to the block of the first 128 atoms of every molecule; [B, 1, 1] zeros without atoms."""
+    if x.shape[0] == 0:
+        return torch.zeros((B, 1, 1), dtype=torch.int8, device=x.device)
+    if not isinstance(info, dict) or "bonds1" not in info:
+        raise ValueError("bond perception needs the dataset (its name or dict), not the decoder alone")
+    from .molecules import bond_orders
+    orders, _ = bond_orders(x, at, lig_mask, info, batch=B)
+    if orders.shape[1] > _lib.MOL_MAX_ATOMS:                        # the block of the first 128 atoms of every molecule
+        orders = orders[:, :_lib.MOL_MAX_ATOMS, :_lib.MOL_MAX_ATOMS].contiguous()
+    return orders
+
+
+def perceive_orders(x, atom_type, lig_mask, info, batch=None):
+    """The `orders` that `vina_score`, `vina_gradient` and `vina_minimize` perceive for themselves when none are given, for a
+    caller that runs more than one of them on a batch: int8 [B, n_max, n_max] on the device.  Arguments as for `type_ligands`."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise _lib.HipLibraryError("perceive_orders needs device tensors (HIP path; no CPU fallback)")
+    x = x.detach().to(torch.float32).reshape(-1, 3).contiguous()
+    at = torch.as_tensor(atom_type, device=x.device).to(torch.int32).reshape(-1).contiguous()
+    lig_mask = torch.as_tensor(lig_mask, device=x.device).reshape(-1)
+    return _perceived_orders(x, at, lig_mask, _decoder(info)[1], _n_molecules(lig_mask, batch))
+
+
 def vina_score(x, atom_type, lig_mask, pockets, info, mol_group=None, batch=None, orders=None):
     """The score of a batch on device tensors: bond orders (unless given), `dsbdd_vina_type`, `dsbdd_vina_score`; no
     read-back inside.  x, atom_type, lig_mask, info, orders, batch as for `type_ligands`; `pockets`: a `VinaPocket`
@@ -516,9 +623,10 @@ def vina_score(x, atom_type, lig_mask, pockets, info, mol_group=None, batch=None
     return _scored("vina_score", VinaScores, x, atom_type, lig_mask, pockets, info, mol_group, batch, orders)
 
 
-def _scored(what, kind, x, atom_type, lig_mask, pockets, info, mol_group, batch, orders):
-    """The launches behind `vina_score` (kind VinaScores: `dsbdd_vina_score`) and `vina_gradient` (kind VinaGradients:
-    `dsbdd_vina_score_grad`, two more outputs) after the typing both share."""
+def _scored(what, kind, x, atom_type, lig_mask, pockets, info, mol_group, batch, orders, settings=None):
+    """The launches behind `vina_score` (kind VinaScores: `dsbdd_vina_score`), `vina_gradient` (kind VinaGradients:
+    `dsbdd_vina_score_grad`, two more outputs) and `vina_minimize` (kind VinaMinimized: `dsbdd_vina_minimize` with
+    `settings` = (step, tol, max_evals), four more) after the typing all share."""
     if not (torch.is_tensor(x) and x.is_cuda):
         raise _lib.HipLibraryError(f"{what} needs device tensors (HIP path; no CPU fallback)")
     lib = _lib.load()
@@ -542,8 +650,19 @@ def _scored(what, kind, x, atom_type, lig_mask, pockets, info, mol_group, batch,
         rc = lib.dsbdd_vina_score(*args)
     else:
         out.grad, out.mol_grad = torch.zeros((N, ATOM_GRAD), **f32), torch.zeros((B, MOL_GRAD), **f32)
-        rc = lib.dsbdd_vina_score_grad(*args, _ptr(out.grad), _ptr(out.mol_grad))
-    _lib.check(rc, "dsbdd_vina_score" if kind is VinaScores else "dsbdd_vina_score_grad")
+        if kind is VinaGradients:
+            rc = lib.dsbdd_vina_score_grad(*args, _ptr(out.grad), _ptr(out.mol_grad))
+        else:
+            step, tol, max_evals = settings
+            out.x_in, out.x = x, x.clone()                             # x_out must not alias the input
+            out.pose, out.energies = torch.zeros((B, MOL_POSE), **f32), torch.zeros((B, MOL_MIN), **f32)
+            out.stat = torch.zeros((B, MOL_STAT), dtype=torch.int32, device=dev)
+            # without atoms both pointers are stand-ins (`_ptr`); held here together, so that they are two addresses
+            x_arg, x_out_arg = (x, out.x) if N else (torch.zeros(4, **f32), torch.zeros(4, **f32))
+            rc = lib.dsbdd_vina_minimize(stream, x_arg.data_ptr(), *args[2:], _ptr(out.grad), _ptr(out.mol_grad), float(step),
+                                         float(tol), int(max_evals), x_out_arg.data_ptr(), _ptr(out.pose), _ptr(out.energies),
+                                         _ptr(out.stat))
+    _lib.check(rc, {VinaScores: "dsbdd_vina_score", VinaGradients: "dsbdd_vina_score_grad"}.get(kind, "dsbdd_vina_minimize"))
     return out
 
 
@@ -554,6 +673,30 @@ def vina_gradient(x, atom_type, lig_mask, pockets, info, mol_group=None, batch=N
     [N,3] = d inter / d x_i in kcal/mol/A (0 for untyped atoms), `mol_grad` [B,8] with the properties `net`, `moment` (about
     the centroid), `max_norm`, `rot_factor`, and `score_grad` = rot_factor[mol] grad.  See `VINA_GRAD_COVERAGE`."""
     return _scored("vina_gradient", VinaGradients, x, atom_type, lig_mask, pockets, info, mol_group, batch, orders)
+
+
+def _settings(step, tol, max_evals):
+    """(step, tol, max_evals) as the C entry takes them (float32, float32, int), refused here as it refuses them."""
+    step, tol = float(np.float32(step)), float(np.float32(tol))
+    if not (np.isfinite(step) and step > 0 and np.isfinite(tol) and tol > 0):
+        raise ValueError("step and tol must be finite and positive")
+    if int(max_evals) != max_evals or not 1 <= int(max_evals) <= MAX_EVALS:
+        raise ValueError(f"max_evals must be an integer in [1, {MAX_EVALS}]")
+    return step, tol, int(max_evals)
+
+
+def vina_minimize(x, atom_type, lig_mask, pockets, info, mol_group=None, batch=None, orders=None, step=MIN_STEP, tol=MIN_TOL,
+                  max_evals=MIN_EVALS):
+    """Rigid-body relaxation of every pose of a batch under `inter`, on device tensors: the typing of `vina_score` (once, on
+    the input pose), then one launch of `dsbdd_vina_minimize` (csrc/vina_minimize.h; one workgroup per molecule iterates
+    the sweep of `vina_gradient`, every decision on the device); no read-back inside.  Arguments as for `vina_score`;
+    `step` the first and largest step (A; no atom moves further in one trial), `tol` the step below which it stops,
+    `max_evals` the evaluation budget (1 ... 4096).  x is not written.  -> VinaMinimized of device tensors: the fields of
+    `vina_gradient` at the returned pose (bit for bit what `vina_gradient` gives on `x`), `x` [N,3], `pose` [B,8], `energies`
+    [B,4], `stat` [B,4] and the properties `status` (index into STATUS), `evals`, `accepted`, `inter_start`, `score_start`,
+    `rmsd`.  `_vina_minimize_host` states the iteration; see `VINA_MIN_COVERAGE` for what this is not."""
+    return _scored("vina_minimize", VinaMinimized, x, atom_type, lig_mask, pockets, info, mol_group, batch, orders,
+                   _settings(step, tol, max_evals))
 
 
 def _chain(grad_out, grad, rot_factor, mol, which):
@@ -649,6 +792,15 @@ def gradient_molecules(molecules, pockets, info="crossdock", mol_group=None, dev
     """`score_molecules` through the launches of `vina_gradient`: the same arguments, the same score records, and the
     gradient of `inter` with them.  -> list of `MolVinaGrad`."""
     return _molecule_records(vina_gradient, "gradient_molecules", molecules, pockets, info, mol_group, device, bonds)
+
+
+def minimize_molecules(molecules, pockets, info="crossdock", mol_group=None, device="cuda", bonds="distance", step=MIN_STEP,
+                       tol=MIN_TOL, max_evals=MIN_EVALS):
+    """`gradient_molecules` through the launches of `vina_minimize`: the same arguments and the minimiser's settings.
+    -> list of `MolVinaMin`: the records of `gradient_molecules` at the returned pose, with its coordinates `x`."""
+    def entry(*args, **kwargs):
+        return vina_minimize(*args, step=step, tol=tol, max_evals=max_evals, **kwargs)
+    return _molecule_records(entry, "minimize_molecules", molecules, pockets, info, mol_group, device, bonds)
 
 
 def _molecule_records(entry, what, molecules, pockets, info, mol_group, device, bonds):
@@ -958,13 +1110,182 @@ def grad_error_bound(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_co
     return grad_bound, mol_bound
 
 
+# ---- the minimiser: float64 restatement ------------------------------------------------------------------------------------------
+def pose_frame(q):
+    """R(q) float64 [3, 3] of a unit quaternion (w first), by the formula the kernel uses."""
+    w, x, y, z = (float(v) for v in q)
+    return np.asarray([[1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)],
+                       [2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x)],
+                       [2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)]], np.float64)
+
+
+def pose_coordinates(x0, shift, q):
+    """float32((c0 + T) + R(q) s) of the float32 input coordinates x0 [n, 3] (c0 their float64 mean, s = x0 - c0): formed
+    in float64, rounded once."""
+    x64 = np.asarray(x0, np.float32).reshape(-1, 3).astype(np.float64)
+    if not len(x64):
+        return x64.astype(np.float32)
+    c0 = x64.sum(0) / len(x64)
+    s, R = x64 - c0, pose_frame(q)
+    origin = c0 + np.asarray(shift, np.float64)
+    return np.stack([origin[k] + ((R[k, 0] * s[:, 0] + R[k, 1] * s[:, 1]) + R[k, 2] * s[:, 2]) for k in range(3)], 1).astype(np.float32)
+
+
+def pose_step(shift, q, F, M, rho2, alpha):
+    """The trial pose of one step: T' = T - alpha F, q' = normalise(dq q) with dq the rotation by -alpha M / rho^2 (a
+    rotation about the current centroid in world axes; the identity if that vector is 0).  float64."""
+    shift, q = np.asarray(shift, np.float64), np.asarray(q, np.float64)
+    th = -(alpha * np.asarray(M, np.float64)) / rho2
+    angle = float(np.sqrt((th[0] * th[0] + th[1] * th[1]) + th[2] * th[2]))
+    dq = np.asarray([1.0, 0.0, 0.0, 0.0])
+    if angle > 0.0:
+        dq = np.concatenate([[np.cos(0.5 * angle)], (np.sin(0.5 * angle) / angle) * th])
+    r = np.asarray([dq[0] * q[0] - dq[1] * q[1] - dq[2] * q[2] - dq[3] * q[3],
+                    dq[0] * q[1] + dq[1] * q[0] + dq[2] * q[3] - dq[3] * q[2],
+                    dq[0] * q[2] - dq[1] * q[3] + dq[2] * q[0] + dq[3] * q[1],
+                    dq[0] * q[3] + dq[1] * q[2] - dq[2] * q[1] + dq[3] * q[0]])
+    return shift - alpha * np.asarray(F, np.float64), r / np.sqrt((r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3]))
+
+
+def _norm3(v):
+    return float(np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]))
+
+
+def _minimize_one(evaluate, x0, step, tol, max_evals):
+    """The iteration on one molecule.  `evaluate(x float32 [n, 3])` -> (E float32, F float64 [3], M float64 [3], record):
+    inter, the net gradient and its moment about the centroid, rounded to float32 before they are used.  -> (x float32,
+    pose [8], energies [4], stat [4], the record of the returned pose)."""
+    x0 = np.asarray(x0, np.float32).reshape(-1, 3)
+    n = len(x0)
+    s = x0.astype(np.float64) - (x0.astype(np.float64).sum(0) / n if n else 0.0)
+    rho2 = max(float((s * s).sum() / n), 1.0) if n else 1.0
+    rho_max = float(np.sqrt((s * s).sum(1).max())) if n else 0.0
+    shift, q = np.zeros(3), np.asarray([1.0, 0.0, 0.0, 0.0])
+    x = pose_coordinates(x0, shift, q)
+    E, F, M, kept = evaluate(x)                                                  # 1
+    evals, accepted, E_start, L, last_L, rejected = 1, 0, E, step, 0.0, False
+    while True:
+        u = _norm3(F) + rho_max * _norm3(M) / rho2                               # 2
+        if not u > 0.0:
+            status = 2
+            break
+        moved = False
+        while True:                                                              # 3
+            if L < tol:
+                status = 1
+                break
+            if evals >= max_evals:
+                status = 0
+                break
+            trial = pose_step(shift, q, F, M, rho2, L / u)
+            xt = pose_coordinates(x0, *trial)
+            Et, Ft, Mt, rec = evaluate(xt)
+            evals += 1
+            if Et < E:                                                           # float32, strict
+                (shift, q), x, E, F, M, kept = trial, xt, Et, Ft, Mt, rec
+                last_L, L, accepted, rejected, moved = L, min(2.0 * L, step), accepted + 1, False, True
+                break
+            L, rejected = 0.5 * L, True
+        if not moved:
+            break
+    if rejected:                                                                 # 4: the rows describe the returned pose
+        E, F, M, kept = evaluate(x)
+        evals += 1
+    pose = np.concatenate([shift, q, [rho2]])
+    return x, pose, np.asarray([E_start, E, last_L, u], np.float64), np.asarray([status, evals, accepted, 0], np.int32), kept
+
+
+def _vina_minimize_host(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_code, group_off, step=MIN_STEP, tol=MIN_TOL,
+                        max_evals=MIN_EVALS, trace=None):
+    """`dsbdd_vina_minimize` in numpy, the specification of its iteration: the arguments of `_vina_grad_host` and the three
+    settings (step and tol rounded to float32 as the C entry takes them).  Per molecule, with x0 its float32 input
+    coordinates, c0 their mean, s = x0 - c0, rho^2 = max(sum |s|^2 / n, 1), rho_max = max |s| and the pose (T, q) from (0,
+    identity), all float64; an evaluation is `_vina_grad_host` in float64 on the float32-rounded coordinates
+    `pose_coordinates(x0, T, q)`, and E = inter, F = net, M = moment are rounded to float32 before any decision:
+      1. evaluate the input pose; E_start = E, L = step
+      2. u = |F| + rho_max |M| / rho^2; unless u > 0 stop, status 2
+      3. L < tol: stop, status 1; max_evals evaluations made: stop, status 0; else the trial `pose_step` with alpha = L / u
+         (no atom moves more than L); evaluate; E' < E (float32, strict): take it, L = min(2 L, step), go to 2; else
+         L = L / 2, repeat 3
+      4. after a stop on a rejected trial the accepted pose is evaluated once more (counted; the only evaluation beyond
+         max_evals)
+    A molecule with a coordinate that is not finite: status 3, x the input, NaN in its other floats, the flag.  Only the pocket
+    atoms inside the ligand's bounding box widened by 8.5 A are handed to an evaluation (no other can be within the cutoff).
+    -> VinaMinimized of arrays: the fields of `_vina_grad_host` (float64) at the returned pose, x float32 [N, 3] (rows of
+    no molecule: the input), pose [B, 8] and energies [B, 4] float64, stat int32 [B, 4], x_in; the inherited `kink_margin` is
+    not evaluated here (it stays inf: `_vina_grad_host` forms it only with its error bound, on `x` if it is wanted).  `trace`: a list that
+    receives (molecule, E float32) for every evaluation, in order."""
+    step, tol, max_evals = _settings(step, tol, max_evals)
+    x_in = np.asarray(_np(lig_x), np.float32).reshape(-1, 3)
+    code = np.asarray(_np(lig_code), np.int32).reshape(-1)
+    q_all = np.asarray(_np(poc_x), np.float32).reshape(-1, 3)
+    qcode = np.asarray(_np(poc_code), np.int32).reshape(-1)
+    off = np.asarray(_np(mol_off), np.int64).reshape(-1)
+    goff = np.asarray(_np(group_off), np.int64).reshape(-1)
+    ints = np.asarray(_np(mol_int), np.int32).reshape(-1, MOL_INT)
+    groups = np.asarray(_np(mol_group), np.int64).reshape(-1)
+    B, G, N = len(off) - 1, len(goff) - 1, len(x_in)
+    if len(code) != N or len(qcode) != len(q_all) or len(groups) != B or len(ints) != B:
+        raise ValueError("one code per atom, one group and one mol_int row per molecule")
+    out = VinaMinimized(np.zeros((N, ATOM_OUT)), np.zeros((B, MOL_OUT)), ints, np.zeros(B, np.int32), code, off.astype(np.int32),
+                        np.zeros((N, ATOM_GRAD)), np.zeros((B, MOL_GRAD)), float("inf"), x_in.copy(), np.zeros((B, MOL_POSE)),
+                        np.zeros((B, MOL_MIN)), np.zeros((B, MOL_STAT), np.int32), x_in)
+    for b in range(B):
+        lo, hi = int(off[b]), int(off[b + 1])
+        if not (lo >= 0 and hi >= lo and hi <= off[B]):
+            lo = hi = 0
+        g = int(groups[b])
+        glo, ghi = (int(goff[g]), int(goff[g + 1])) if 0 <= g < G else (0, 0)
+        if not (glo >= 0 and ghi >= glo and ghi <= goff[G]):
+            glo = ghi = 0
+        x0, c, one = x_in[lo:hi], code[lo:hi], np.asarray([0, hi - lo], np.int64)
+        qg, qc = q_all[glo:ghi], qcode[glo:ghi]
+
+        def evaluate(x):
+            near = np.ones(len(qg), bool)
+            if len(x) and len(qg) and np.isfinite(x).all():
+                low, high = x.astype(np.float64).min(0) - (CUTOFF + 0.5), x.astype(np.float64).max(0) + (CUTOFF + 0.5)
+                near = ((qg >= low) & (qg <= high)).all(1)
+            st = _vina_grad_host(x, c, one, [0], ints[b:b + 1], qg[near], qc[near], [0, int(near.sum())])
+            E = np.float32(st.mol[0, M_INTER])
+            if trace is not None:
+                trace.append((b, E))
+            return E, st.mol_grad[0, G_NET].astype(np.float32).astype(np.float64), \
+                st.mol_grad[0, G_MOMENT].astype(np.float32).astype(np.float64), st
+
+        if not np.isfinite(x0).all():
+            st = evaluate(x0)[3]
+            pose, energies, stat = np.full(MOL_POSE, np.nan), np.full(MOL_MIN, np.nan), np.asarray([3, 0, 0, 0], np.int32)
+        else:
+            x, pose, energies, stat, st = _minimize_one(evaluate, x0, step, tol, max_evals)
+            out.x[lo:hi] = x
+        out.atom[lo:hi], out.grad[lo:hi] = st.atom, st.grad
+        out.mol[b], out.flag[b], out.mol_grad[b] = st.mol[0], st.flag[0], st.mol_grad[0]
+        out.pose[b], out.energies[b], out.stat[b] = pose, energies, stat
+    return out
+
+
 # ---- command line ----------------------------------------------------------------------------------------------------------
 CSV_COLUMNS = ("n_atoms", "untyped", "n_rot", "nonfinite") + TERMS + ("inter", "score")
+MIN_CSV_COLUMNS = CSV_COLUMNS + ("inter_start", "score_start", "status", "evals", "rmsd")      # with --minimize
 
 
-def write_csv(path, rows):
+def write_csv(path, rows, columns=CSV_COLUMNS):
     """rows: (source, index, MolVina or its dict); `path` None writes to stdout."""
-    _pairs.write_csv(path, rows, CSV_COLUMNS)
+    _pairs.write_csv(path, rows, columns)
+
+
+def write_minimized_sdf(path, sources, rows):
+    """The relaxed molecules of `rows` = (source, index, MolVinaMin) as one SDF file, in row order: the heavy atoms and bonds
+    of record `index` of the SDF file `source` (`sources`: {path: `as_ligands(path)`}) at the returned coordinates."""
+    from .molecules import Molecule, write_sdf
+    mols, names = [], []
+    for source, k, rec in rows:
+        _, elements, bonds = sources[source][k]
+        # `to_sdf_block` writes a bond (i, j) as "j i": handed over reversed, the bond block repeats the source's columns
+        mols.append(Molecule(np.asarray(rec.x, np.float32), list(elements), [(j, i, o) for i, j, o in bonds or []]))
+        names.append(f"{source}:{k} status={STATUS[rec.status]} score={rec.score:.4f} score_start={rec.score_start:.4f}")
+    write_sdf(path, mols, names)
 
 
 GRAD_CSV_COLUMNS = ("source", "index", "atom", "gx", "gy", "gz", "norm")
@@ -992,6 +1313,13 @@ def parse_args(argv=None):
     p.add_argument("--grad_out", default=None,
                    help="also write the gradient of `inter` with respect to the ligand coordinates, one row per heavy atom "
                         "(kcal/mol/A; the scores then come from the same launch, unchanged)")
+    p.add_argument("--minimize", default=None, metavar="OUT.sdf",
+                   help="relax every pose as a rigid body under `inter` on the device first (rigid ligand, rigid protein, a "
+                        "local search; not smina or qvina output): the relaxed molecules go to this file, the rows of --out "
+                        "(and of --grad_out) describe them and gain the columns inter_start, score_start, status, evals, rmsd")
+    p.add_argument("--step", type=float, default=MIN_STEP, help="--minimize: the first and largest step, A")
+    p.add_argument("--tol", type=float, default=MIN_TOL, help="--minimize: stop when the step falls below this, A")
+    p.add_argument("--max_evals", type=int, default=MIN_EVALS, help=f"--minimize: evaluation budget per molecule (1 ... {MAX_EVALS})")
     return _pairs.parse_complex_arguments(p, argv)
 
 
@@ -1005,12 +1333,20 @@ def main(argv=None):
     if a.grad_out is not None:
         print(VINA_GRAD_COVERAGE, file=sys.stderr)
         records_of = gradient_molecules
+    if a.minimize is not None:
+        print(VINA_MIN_COVERAGE, file=sys.stderr)
+        step, tol, max_evals = _settings(a.step, a.tol, a.max_evals)
+
+        def records_of(path, *args, **kwargs):
+            return minimize_molecules(path, *args, step=step, tol=tol, max_evals=max_evals, **kwargs)
     rows = []
     for path in a.sdf:
         rows += [(path, k, rec) for k, rec in enumerate(records_of(path, pockets, a.dataset, bonds=a.bonds))]
-    write_csv(a.out, rows)
+    write_csv(a.out, rows, CSV_COLUMNS if a.minimize is None else MIN_CSV_COLUMNS)
     if a.grad_out is not None:
         write_grad_csv(a.grad_out, rows)
+    if a.minimize is not None:
+        write_minimized_sdf(a.minimize, {path: as_ligands(path) for path in a.sdf}, rows)
     return rows
 
 

@@ -908,6 +908,39 @@ int dsbdd_vina_score_grad(void* stream, const float* lig_x, const int32_t* lig_c
                           const int32_t* group_off, int64_t n_groups, float* atom_out, float* mol_out, int32_t* mol_flag,
                           float* atom_grad, float* mol_grad);
 
+/* Rigid-body minimisation of every pose of such a batch under `inter` of dsbdd_vina_score, one launch (csrc/vina_minimize.h):
+ * one workgroup per molecule runs the sweep of dsbdd_vina_score_grad once per evaluation and takes every decision on the
+ * device.  Rigid ligand (no torsions), rigid protein, a local search by steepest descent in a scaled metric with
+ * backtracking; no intramolecular term; NOT smina or qvina output.  Every input, convention and check of
+ * dsbdd_vina_score_grad; lig_x is the input pose and is not written; lig_x and x_out MUST NOT alias (with batch > 0 the same
+ * pointer is DSBDD_ERR_ARG; overlapping ranges are the caller's error).  Typing is done once, on the input pose, by dsbdd_vina_type.
+ * Pose: c0 the mean of the molecule's n input coordinates, s_i = x0_i - c0 (float64), (T, q) a translation and a unit
+ * quaternion (w first) from (0, identity); x_i = float32((c0 + T) + R(q) s_i), formed in float64 from the INPUT
+ * coordinates at every evaluation and rounded once.  rho^2 = max(sum |s_i|^2 / n, 1), rho_max = max |s_i|.
+ * An evaluation writes x(T, q) to x_out, sweeps, and reads back the stored float32 E = inter (mol_out[5]), F = net
+ * gradient and M = its moment about the centroid (mol_grad[0..5]); every decision is a function of those and the pose:
+ *   1. evaluate the input pose: E_start = E, L = step;
+ *   2. u = |F| + rho_max |M| / rho^2; unless u > 0 stop with status 2;
+ *   3. if L < tol stop with status 1; if max_evals evaluations were made stop with status 0; else alpha = L / u,
+ *      T' = T - alpha F, q' = normalise(dq q) with dq the rotation by the vector -alpha M / rho^2 (about the centroid, in
+ *      world axes; no atom moves more than L); evaluate; if E' < E (float32, strict) take the trial, L = min(2 L, step)
+ *      and go to 2, else L = L / 2 and repeat 3;
+ *   4. on a stop after a rejected trial the accepted pose is evaluated once more (counted in the evaluations; the only
+ *      one beyond max_evals).
+ * Outputs: atom_out, mol_out, mol_flag, atom_grad, mol_grad as dsbdd_vina_score_grad writes them for x_out, bit for bit;
+ * x_out [N][3] the returned pose; mol_pose [B][8] = T (3), q (4), rho^2; mol_min [B][4] = E_start, E_final, the last accepted
+ * L (0 if none), u at the returned pose; mol_stat [B][4] int32 = status (0 budget, 1 converged, 2 no gradient: no atoms, an
+ * empty group, nothing typed, or a flat score; 3 not finite), evaluations, accepted steps, 0.  A molecule with a NaN or
+ * +-inf coordinate: status 3, its x_out rows are the input's bit for bit, NaN in every other float it owns, mol_flag 1.
+ * No atomics, bitwise reproducible, independent of the rest of the batch; the same range checks.  batch = 0 launches
+ * nothing; null pointers, negative counts, step or tol not finite or <= 0 and max_evals outside [1, 4096] are
+ * DSBDD_ERR_ARG. */
+int dsbdd_vina_minimize(void* stream, const float* lig_x, const int32_t* lig_code, const int32_t* mol_off, int64_t batch,
+                        const int32_t* mol_group, const int32_t* mol_int, const float* poc_x, const int32_t* poc_code,
+                        const int32_t* group_off, int64_t n_groups, float* atom_out, float* mol_out, int32_t* mol_flag,
+                        float* atom_grad, float* mol_grad, float step, float tol, int32_t max_evals, float* x_out,
+                        float* mol_pose, float* mol_min, int32_t* mol_stat);
+
 /* ---- ligands as input: the packed batch of the design front ends -------------*/
 /* One launch that writes the ligand batch of substructure inpainting and of
  * diversification (inpaint.py:114-141, optimize.py:39-62 of the reference build
