@@ -29,7 +29,7 @@ GCL_NAMES = ["E1_WT", "E1_WD", "E1_WD0", "E1_TAB", "E2_WT", "E2_B", "ATT_W", "AT
              "N1_WT", "N1_B", "N2_WT", "N2_B"]
 EQ_NAMES = ["C1_WT", "C_WD", "C_WD0", "C_TAB", "C_W2T", "C_B2",
             "X_WD", "X_WD0", "X_TAB", "X_W2T", "X_B2", "W3"]
-OPT_PRUNE, OPT_CONE, OPT_GRANULE16, OPT_EMU, OPT_SPLITK, OPT_SHELL, OPT_TAIL = 0, 1, 2, 3, 4, 5, 6
+OPT_PRUNE, OPT_CONE, OPT_GRANULE16, OPT_EMU, OPT_SPLITK, OPT_SHELL, OPT_TAIL, OPT_CHAIN_DEAL = 0, 1, 2, 3, 4, 5, 6, 7
 (BUF_EDGE_ROW, BUF_EDGE_COL, BUF_EDGE_D0, BUF_ROW_PTR, BUF_H, BUF_X, BUF_NODE_BATCH, BUF_DEG,
  BUF_LEVEL, BUF_LEVEL_LIST, BUF_LEVEL_COUNT, BUF_LEVEL_END, BUF_LROW_PTR, BUF_LEDGE_ROW, BUF_LEDGE_COL,
  BUF_LEDGE_D0, BUF_LEVEL_STATS) = range(17)
@@ -126,6 +126,8 @@ SIGNATURES = {
                                     _P, _I32, _I64, _I32, _I32]),
     "dsbdd_chain_split_host": (_I64, [_I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I64]),
     "dsbdd_chain_split_probe": (C.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I64, _P]),
+    "dsbdd_chain_deal_host": (_I64, [_I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I64]),
+    "dsbdd_chain_deal_probe": (C.c_int, [_P, _I32, _P, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I64, _P]),
     "dsbdd_build_edges": (C.c_int, [_P, _P, _P, _P, _I64, _I64, _I64, C.POINTER(Config),
                                     _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "dsbdd_bond_orders": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _P, C.c_float, C.c_float,

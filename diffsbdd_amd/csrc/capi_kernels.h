@@ -171,33 +171,65 @@ static bool chain_split_args_ok(int32_t M, int32_t n_proj, const void* proj_N, c
 static const char* const kChainSplitBadArg =
     "bad argument (null output, grid < 1, H not 64 / 128 / 192 / 256, more than 3 projections or more than 8 M rows)";
 
-int64_t dsbdd_chain_split_host(int32_t M, int32_t do_mlp, int32_t n_proj, const int32_t* proj_N,
-                               const int32_t* proj_first, const int32_t* proj_count, int32_t H, int32_t grid,
-                               uint32_t* header, int32_t* pieces, int64_t capacity) {
+// both policies (Split = ChainSplit / ChainDealt) behind one body each
+extern "C++" {
+template <class Split>
+static int64_t chain_split_host(int32_t M, int32_t do_mlp, int32_t n_proj, const int32_t* proj_N, const int32_t* proj_first,
+                                const int32_t* proj_count, int32_t H, int32_t grid, uint32_t* header, int32_t* pieces,
+                                int64_t capacity) {
   if (!chain_split_args_ok(M, n_proj, proj_N, proj_first, proj_count, H, grid, header, pieces, capacity))
     return fail(DSBDD_ERR_ARG, kChainSplitBadArg);
   ChainSplitIn in{};
   in.M = M; in.do_mlp = do_mlp; in.n_proj = n_proj; in.H = H; in.grid = grid;
   for (int q = 0; q < n_proj; ++q) { in.N[q] = proj_N[q]; in.first[q] = proj_first[q]; in.count[q] = proj_count[q]; }
-  const ChainSplit sp(in);
+  const Split sp(in);
   sp.report(header);
   return chain_split_list(sp, grid, grid, ~0u, pieces, capacity);
 }
 
-int dsbdd_chain_split_probe(void* stream, int32_t M, const int32_t* m_count, int32_t do_mlp, int32_t n_proj,
-                            const int32_t* proj_N, const int32_t* proj_first, const int32_t* const* proj_count,
-                            int32_t H, int32_t grid, uint32_t* header, int32_t* pieces, int64_t capacity,
-                            int64_t* n_pieces) {
+template <class Split>
+static int chain_split_probe(void* stream, int32_t M, const int32_t* m_count, int32_t do_mlp, int32_t n_proj,
+                             const int32_t* proj_N, const int32_t* proj_first, const int32_t* const* proj_count, int32_t H,
+                             int32_t grid, uint32_t* header, int32_t* pieces, int64_t capacity, int64_t* n_pieces) {
   StreamDevice stream_device_(stream);
   if (!n_pieces || !chain_split_args_ok(M, n_proj, proj_N, proj_first, proj_count, H, grid, header, pieces, capacity))
     return fail(DSBDD_ERR_ARG, kChainSplitBadArg);
   NodeChainArgs a{};
   a.M = M; a.m_count = m_count; a.do_mlp = do_mlp; a.n_proj = n_proj;
   for (int q = 0; q < n_proj; ++q) { a.proj[q].N = proj_N[q]; a.proj[q].first = proj_first[q]; a.proj[q].count = proj_count[q]; }
-  hipLaunchKernelGGL(chain_split_probe_kernel, dim3(grid), dim3(64), 0, static_cast<hipStream_t>(stream), a, (int)H, header,
-                     pieces, (long long)capacity, reinterpret_cast<long long*>(n_pieces));
+  hipLaunchKernelGGL(chain_split_probe_kernel<Split>, dim3(grid), dim3(64), 0, static_cast<hipStream_t>(stream), a, (int)H,
+                     header, pieces, (long long)capacity, reinterpret_cast<long long*>(n_pieces));
   HIP_TRY(hipGetLastError());
   return DSBDD_OK;
+}
+}  // extern "C++"
+
+int64_t dsbdd_chain_split_host(int32_t M, int32_t do_mlp, int32_t n_proj, const int32_t* proj_N,
+                               const int32_t* proj_first, const int32_t* proj_count, int32_t H, int32_t grid,
+                               uint32_t* header, int32_t* pieces, int64_t capacity) {
+  return chain_split_host<ChainSplit>(M, do_mlp, n_proj, proj_N, proj_first, proj_count, H, grid, header, pieces, capacity);
+}
+
+int dsbdd_chain_split_probe(void* stream, int32_t M, const int32_t* m_count, int32_t do_mlp, int32_t n_proj,
+                            const int32_t* proj_N, const int32_t* proj_first, const int32_t* const* proj_count,
+                            int32_t H, int32_t grid, uint32_t* header, int32_t* pieces, int64_t capacity,
+                            int64_t* n_pieces) {
+  return chain_split_probe<ChainSplit>(stream, M, m_count, do_mlp, n_proj, proj_N, proj_first, proj_count, H, grid, header,
+                                       pieces, capacity, n_pieces);
+}
+
+int64_t dsbdd_chain_deal_host(int32_t M, int32_t do_mlp, int32_t n_proj, const int32_t* proj_N,
+                              const int32_t* proj_first, const int32_t* proj_count, int32_t H, int32_t grid,
+                              uint32_t* header, int32_t* pieces, int64_t capacity) {
+  return chain_split_host<ChainDealt>(M, do_mlp, n_proj, proj_N, proj_first, proj_count, H, grid, header, pieces, capacity);
+}
+
+int dsbdd_chain_deal_probe(void* stream, int32_t M, const int32_t* m_count, int32_t do_mlp, int32_t n_proj,
+                           const int32_t* proj_N, const int32_t* proj_first, const int32_t* const* proj_count,
+                           int32_t H, int32_t grid, uint32_t* header, int32_t* pieces, int64_t capacity,
+                           int64_t* n_pieces) {
+  return chain_split_probe<ChainDealt>(stream, M, m_count, do_mlp, n_proj, proj_N, proj_first, proj_count, H, grid, header,
+                                      pieces, capacity, n_pieces);
 }
 
 int dsbdd_bond_orders(void* stream, const float* x, const int32_t* atom_type, const int32_t* mol_off,

@@ -209,6 +209,173 @@ struct ChainSplit {
   }
 };
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Second policy (DSBDD_OPT_CHAIN_DEAL, DESIGN.md §5 "Min-max deal"): the same inputs, dealt by the load a workgroup EXECUTES.
+// chain_range multiplies all tiles of a piece for every projection the piece touches, so the tile list is cut at every
+// problem's start (rounded down to a tile) and end (rounded up) at every launch size, and inside a segment between two cuts
+// every tile costs the same: u = 48 (node MLP) + N_p * 16 / H for every problem whose tile range holds the segment, x 16
+// rows.  Every range is k_s consecutive tiles of one segment (the segment's last range: what is left).
+//   * FALLBACK, a pure function of the launch's counts (Tt tiles, S segments with tiles, grid): with 8 S > grid and
+//     Tt >= 3 grid ChainSplit deals the launch (its forced path: the same cuts, several ranges per workgroup).  One range
+//     per workgroup cannot balance S segments over fewer than 8 S workgroups as well as that does (measured on the listed
+//     cases of tests/_chain_split_cases.py: up to 2.5 x its slowest load at grid 2 / 3 / 8, never above it from grid 104);
+//     no engine launch is that narrow;
+//   * at most `grid` tiles: every tile is a range of its own.  The same where the segments outnumber the workgroups
+//     (S > grid, so grid < 8) in a launch too small for the fallback: workgroup w then takes the tiles w, w + grid, ...;
+//   * else the smallest bottleneck b for which sum_s ceil(T_s / floor(b / u_s)) ranges fit the grid: b starts at the
+//     lower bound max(u_max, ceil(sum T_s u_s / grid)) and steps through the values at which some floor(b / u_s) grows --
+//     the only values at which the sum can change -- so the first b that fits is the optimum (1 + 2 S divisions to start,
+//     one per step; about S^2 Tt / grid^2 + S steps).  One range per workgroup; ranges of more than kChainRowsMax rows go
+//     on as pieces (chain_pieces);
+//   * ranges that do not fill the grid leave workgroups idle: by the minimality of b no further cut lowers the bottleneck.
+// 32-bit arithmetic on wave-uniform values: sum T_s u_s <= tiles x 240 < 2^32 up to 17.8 M tiles (286 M rows; the entry
+// points and launch_node_chain stop at 8 M rows).  The tables are only indexed by fully unrolled loops.
+constexpr int kDealCuts = 2 * kChainMaxProj + 2;      // 0, the problems' starts and ends, the last tile's end
+constexpr int kChainSegs = kDealCuts - 1;
+
+struct ChainDeal {
+  int cnt[kChainMaxProj];         // the clamped counts, as ChainSplit has them (chain_range needs them)
+  int Mw, Tt;                     // rows with work (as ChainSplit::Mw) and their tiles
+  int cut[kDealCuts];             // the cuts in tiles, sorted
+  unsigned k[kChainSegs];         // tiles per range of the segment that starts at cut a
+  unsigned nrg[kChainSegs];       // its ranges
+  unsigned B;                     // the slowest range's executed load (units of H*H/16 MAC)
+  unsigned Vs;                    // ranges dealt out
+  bool fallback;                  // nothing is dealt out here: ChainSplit deals this launch (ChainDealt)
+
+  CHAIN_SPLIT_FN explicit ChainDeal(const ChainSplitIn& in) {
+    Mw = 0; Tt = 0; B = 0; Vs = 0; fallback = false;
+#pragma unroll
+    for (int q = 0; q < kChainMaxProj; ++q) cnt[q] = 0;
+    const int M = in.M;
+    if (M <= 0) return;
+    const unsigned w_mlp = in.do_mlp ? 48u : 0u;
+    int M_work = in.do_mlp ? M : 0;
+    bool work = in.do_mlp != 0;
+    unsigned wgt[kChainMaxProj];
+    int lo[kChainMaxProj];
+#pragma unroll
+    for (int q = 0; q < kChainMaxProj; ++q) {              // (an unused slot: an empty problem of weight 0 at row 0)
+      const bool on = q < in.n_proj;
+      lo[q] = on ? chain_max(in.first[q], 0) : 0;
+      const int fst = chain_min(M, lo[q]);
+      cnt[q] = on ? chain_max(chain_min(M - fst, in.count[q]), 0) : 0;
+      wgt[q] = on ? (unsigned)(in.N[q] * 16 / in.H) : 0u;
+      M_work = chain_max(M_work, fst + cnt[q]);
+      work = work || (wgt[q] > 0 && cnt[q] > 0);
+    }
+    if (M_work <= 0 || !work) return;                      // (no row has work: nothing is dealt out, as in ChainSplit)
+    Mw = M_work;
+    Tt = (Mw + 15) >> 4;
+    // the tiles chain_range multiplies for problem q: those that touch [first, first + cnt) -- for an EMPTY problem whose
+    // first is no multiple of 16 still the tile around it (chain_range does not look at the count alone)
+    int t0[kChainMaxProj], t1[kChainMaxProj];
+#pragma unroll
+    for (int q = 0; q < kChainMaxProj; ++q) {
+      const int l = chain_min(lo[q], Tt << 4);
+      t0[q] = chain_min(Tt, l >> 4);
+      t1[q] = chain_min(Tt, (l + cnt[q] + 15) >> 4);
+    }
+    {
+      int nb = 0;
+      cut[nb++] = 0;
+#pragma unroll
+      for (int q = 0; q < kChainMaxProj; ++q) { cut[nb++] = t0[q]; cut[nb++] = t1[q]; }
+      cut[nb++] = Tt;
+#pragma unroll
+      for (int a2 = 1; a2 < kDealCuts; ++a2)               // insertion sort, fully unrolled (the array stays in registers)
+#pragma unroll
+        for (int b2 = kDealCuts - 1; b2 > 0; --b2)
+          if (b2 <= a2 && cut[b2] < cut[b2 - 1]) { const int tmp = cut[b2]; cut[b2] = cut[b2 - 1]; cut[b2 - 1] = tmp; }
+    }
+    // cost of a tile of every segment (/ 16), segments with tiles, their sum and their most expensive tile
+    unsigned u[kChainSegs], S = 0, total = 0, u_max = 0;
+#pragma unroll
+    for (int a2 = 0; a2 < kChainSegs; ++a2) {
+      const unsigned T = (unsigned)(cut[a2 + 1] - cut[a2]);
+      unsigned c = w_mlp;
+#pragma unroll
+      for (int q = 0; q < kChainMaxProj; ++q) c += cut[a2] >= t0[q] && cut[a2] < t1[q] ? wgt[q] : 0u;      // (every t0, t1 is a cut)
+      u[a2] = c; k[a2] = 1; nrg[a2] = T;
+      S += T > 0; total += T * c;
+      if (T > 0) u_max = chain_max(u_max, c);
+    }
+    const unsigned G = (unsigned)in.grid;
+    fallback = 8 * S > G && (unsigned)Tt >= 3 * G;
+    if (fallback) return;
+    if ((unsigned)Tt <= G || S > G) { Vs = (unsigned)Tt; B = 16 * u_max; return; }      // every tile a range of its own
+    // many tiles: the smallest bottleneck b (/ 16) whose ranges fit the grid
+    unsigned b = chain_max(u_max, (total + G - 1) / G);
+    Vs = 0;
+#pragma unroll
+    for (int a2 = 0; a2 < kChainSegs; ++a2) {
+      const unsigned T = (unsigned)(cut[a2 + 1] - cut[a2]);
+      if (T > 0) {
+        k[a2] = u[a2] > 0 ? chain_min(b / u[a2], T) : T;   // (a segment without work: one range)
+        nrg[a2] = (T + k[a2] - 1) / k[a2];
+        Vs += nrg[a2];
+      }
+    }
+#pragma unroll 1
+    while (Vs > G) {
+      unsigned nb = ~0u;
+#pragma unroll
+      for (int a2 = 0; a2 < kChainSegs; ++a2)
+        if (k[a2] < (unsigned)(cut[a2 + 1] - cut[a2])) nb = chain_min(nb, (k[a2] + 1) * u[a2]);
+      b = nb;
+#pragma unroll
+      for (int a2 = 0; a2 < kChainSegs; ++a2) {
+        const unsigned T = (unsigned)(cut[a2 + 1] - cut[a2]);
+        if (k[a2] < T && (k[a2] + 1) * u[a2] == b) {
+          Vs -= nrg[a2];
+          k[a2] += 1;
+          nrg[a2] = (T + k[a2] - 1) / k[a2];
+          Vs += nrg[a2];
+        }
+      }
+    }
+    (void)b;
+#pragma unroll
+    for (int a2 = 0; a2 < kChainSegs; ++a2)
+      if (cut[a2 + 1] > cut[a2]) B = chain_max(B, 16 * u[a2] * chain_min(k[a2], (unsigned)(cut[a2 + 1] - cut[a2])));
+  }
+
+
+  // Rows [r0, r1) of range v (both multiples of 16).  False past the last range.  No division.  With more ranges than
+  // workgroups every range is a single tile, range v = tile v (node_chain_kernel relies on it for its later rounds).
+  CHAIN_SPLIT_FN bool range(unsigned v, int& r0, int& r1) const {
+    if (v >= Vs) return false;
+    unsigned j = v, kk = 1;
+    int b0 = 0, b1 = 0;
+    bool found = false;
+#pragma unroll
+    for (int a2 = 0; a2 < kChainSegs; ++a2) {
+      if (!found && j < nrg[a2]) { found = true; kk = k[a2]; b0 = cut[a2]; b1 = cut[a2 + 1]; }
+      if (!found) j -= nrg[a2];
+    }
+    if (!found) return false;
+    r0 = (b0 + (int)(j * kk)) << 4;
+    r1 = chain_min(b1, b0 + (int)((j + 1) * kk)) << 4;
+    return true;
+  }
+};
+
+// What a launch with the option at 1 runs, for the entry points (node_chain_kernel does the same with shorter lifetimes):
+// ChainDeal, or ChainSplit where that falls back.
+struct ChainDealt {
+  ChainDeal dl;
+  ChainSplit sp;
+  unsigned Vs, grid;
+  CHAIN_SPLIT_FN explicit ChainDealt(const ChainSplitIn& in) : dl(in), sp(dl.fallback ? in : ChainSplitIn{}) {
+    Vs = dl.fallback ? sp.Vs : dl.Vs; grid = (unsigned)in.grid;
+  }
+  CHAIN_SPLIT_FN bool range(unsigned v, int& r0, int& r1) const { return dl.fallback ? sp.range(v, r0, r1) : dl.range(v, r0, r1); }
+  // (Mw, B executed load of the slowest range -- 0 in the fallback --, grid, Vs, fallback); all zero when nothing is dealt out
+  CHAIN_SPLIT_FN void report(unsigned* h) const {
+    h[0] = (unsigned)dl.Mw; h[1] = dl.B; h[2] = dl.Mw > 0 ? grid : 0u; h[3] = Vs; h[4] = dl.fallback;
+  }
+};
+
 // The pieces of at most kChainRowsMax rows a workgroup walks for the rows [r0, r1): piece(first row, tiles).
 // (At most one piece unless the rounding overshoots.)
 template <class F>
@@ -220,10 +387,11 @@ CHAIN_SPLIT_FN void chain_pieces(int r0, int r1, F&& piece) {
   }
 }
 
-// The split as the entry points report it: the (workgroup, first row, tiles) triples of the workgroups [0, wg_end) of a
-// launch of `grid`, workgroup by workgroup; those of workgroup `own` (~0u: of all) are written to pieces[capacity][3].
+// A split (ChainSplit or ChainDealt) as the entry points report it: the (workgroup, first row, tiles) triples of the
+// workgroups [0, wg_end) of a launch of `grid`, workgroup by workgroup; those of workgroup `own` (~0u: of all) are written to pieces[capacity][3].
 // Returns the number of pieces of [0, wg_end).
-CHAIN_SPLIT_FN long long chain_split_list(const ChainSplit& sp, unsigned grid, unsigned wg_end, unsigned own, int* pieces,
+template <class Split>
+CHAIN_SPLIT_FN long long chain_split_list(const Split& sp, unsigned grid, unsigned wg_end, unsigned own, int* pieces,
                                           long long capacity) {
   long long n = 0;
   for (unsigned wg = 0; wg < wg_end; ++wg)

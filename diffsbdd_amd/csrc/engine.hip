@@ -234,6 +234,7 @@ int dsbdd_engine_set_option(dsbdd_engine* e, int which, int value) {
     case DSBDD_OPT_TAIL:                                                           // 0 off, 1 on, n > 1: n resident workgroups in the rule
       if (value < 0) return fail(DSBDD_ERR_ARG, "DSBDD_OPT_TAIL takes a value >= 0");
       e->tail = value; break;
+    case DSBDD_OPT_CHAIN_DEAL: e->chain_deal = value ? 1 : 0; break;
     default: return fail(DSBDD_ERR_ARG, "unknown option");
   }
   e->drop_graphs();
@@ -250,6 +251,7 @@ int dsbdd_engine_get_option(const dsbdd_engine* e, int which) {
     case DSBDD_OPT_EMU: return e->emu;
     case DSBDD_OPT_SHELL: return e->shell;
     case DSBDD_OPT_TAIL: return e->tail;
+    case DSBDD_OPT_CHAIN_DEAL: return e->chain_deal;
   }
   return fail(DSBDD_ERR_ARG, "unknown option");
 }

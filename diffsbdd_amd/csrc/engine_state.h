@@ -173,6 +173,7 @@ struct dsbdd_engine : Workspace {
   int shell = 1;                        // DSBDD_OPT_SHELL: shell rows of the cone's ascending stages reuse the ghost rows' messages
   int tail = 1;                         // DSBDD_OPT_TAIL: the last round of the exact H = 256 message launches on quarter items (edge_wave.h);
                                         // 0 off, 1 on (default), n > 1: n in place of the resident workgroups in the rule (test hook); DSBDD_TAIL
+  int chain_deal = 1;                   // DSBDD_OPT_CHAIN_DEAL: node_chain_kernel's rows by the min-max deal (chain_split.h ChainDeal); 0: ChainSplit; DSBDD_CHAIN_DEAL
   int64_t cap_shell = 0;                // slots of one shell list: a level's rows, one padded segment per sample
   // Memory of the shell stages: the shell lists (level_list.h, LevelArgs::sh_*) and the messages of the ghost segment,
   // [ghost_slots][H].  The bound workspace keeps its recorded layout and the message buffer's size is the frame's, not
@@ -328,7 +329,7 @@ static void read_env_switches(dsbdd_engine* e) {
   const std::pair<const char*, int*> off_on_zero[] = {      // on by default; off only on a value that parses to 0
       {"DSBDD_GRAPH", &e->use_graph}, {"DSBDD_EDGE_BPERM", &e->edge_bperm}, {"DSBDD_COORD_SPLIT", &e->coord_split},
       {"DSBDD_NODE_GROUP", &e->node_group}, {"DSBDD_PRUNE", &e->prune}, {"DSBDD_LIG_HEAD", &e->lig_head},
-      {"DSBDD_NODE_CHAIN", &e->chain}};
+      {"DSBDD_NODE_CHAIN", &e->chain}, {"DSBDD_CHAIN_DEAL", &e->chain_deal}};
   for (const auto& sw : off_on_zero) if (env_int(sw.first, &v) && v == 0) *sw.second = 0;
   if (env_int("DSBDD_FOLD_SCAN", &v)) e->fold_scan = v > 0 ? 1 : 0;
   if (env_int("DSBDD_GRANULE16", &v, true)) e->granule16 = (unsigned)v;

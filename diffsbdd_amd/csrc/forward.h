@@ -489,6 +489,7 @@ struct Forward : ForwardArgs {
           fill_pq = ghost && !same_rows;
         }
       }
+      ca.deal = e->chain_deal;
       HIP_TRY(launch_node_chain(s, ca, H, e->n_cu));
     } else {
       HIP_TRY(launch_node_linear(s, n1));
@@ -537,6 +538,7 @@ struct Forward : ForwardArgs {
       ca.row_idx = nx.row_idx; ca.m_count = nx.m_count; ca.M = nx.M; ca.do_mlp = 0; ca.h = e->h;
       ca.n_proj = 1;
       ca.proj[0] = ChainProj{chain_w(blk + 1, 0, 2), e->pqg, 2 * H, 2 * H, nullptr, 0};
+      ca.deal = e->chain_deal;
       HIP_TRY(launch_node_chain(s, ca, H, e->n_cu));
       st.pqg_ready = true;
     } else if (want_next) {

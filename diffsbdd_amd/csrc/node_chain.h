@@ -82,6 +82,7 @@ struct NodeChainArgs {
   const float* W2p; const float* b2;     // packed [H cols][H k]
   int n_proj;
   ChainProj proj[kChainMaxProj];
+  int deal;              // row split: 0 ChainSplit, 1 ChainDeal (chain_split.h; DSBDD_OPT_CHAIN_DEAL) -- same bits either way
 };
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
@@ -370,33 +371,60 @@ __global__ __launch_bounds__(kChainThreads, 2) void node_chain_kernel(NodeChainA
   CHAIN_TS(0);
   const ChainSplitIn in = chain_split_input(p, H, (int)gridDim.x);
   CHAIN_NOTE(11, (unsigned long long)(in.M > 0 ? wall_clock64() : 0));     // row counts loaded
-  const ChainSplit sp(in);                                 // (identical arithmetic in every workgroup: chain_split.h)
+  // (identical arithmetic in every workgroup: chain_split.h)
+  // p.deal: ChainDeal hands out one range per workgroup, so its tables live only inside the block below: the first range
+  // and three numbers are kept (more ranges than workgroups it only deals as single tiles, range v = tile v).  Where it
+  // falls back, and with p.deal = 0, ChainSplit deals the launch; otherwise ChainSplit sees an empty launch.
+  bool split = p.deal == 0;
+  unsigned Vs = 0;
+  int Mw = 0, first_r0 = 0, first_r1 = 0;
   // chain_range indexes the clamped counts by a run-time q: a copy of their own, so that the split's tables, which only
   // unrolled loops index, stay in registers
-  const int cnt[kChainMaxProj] = {sp.cnt[0], sp.cnt[1], sp.cnt[2]};
-  for (unsigned v = blockIdx.x; v < sp.Vs; v += gridDim.x) {
-    int r0, r1;
-    if (!sp.range(v, r0, r1)) break;
+  int cnt[kChainMaxProj] = {0, 0, 0};
+  if (!split) {
+    const ChainDeal dl(in);
+    split = dl.fallback;
+    if (!split) {
+      Vs = dl.Vs; Mw = dl.Mw;
+#pragma unroll
+      for (int q = 0; q < kChainMaxProj; ++q) cnt[q] = dl.cnt[q];
+      if (!dl.range(blockIdx.x, first_r0, first_r1)) Vs = 0;
+    }
+  }
+  const ChainSplit sp(split ? in : ChainSplitIn{});
+  if (split) {
+    Vs = sp.Vs; Mw = sp.Mw;
+#pragma unroll
+    for (int q = 0; q < kChainMaxProj; ++q) cnt[q] = sp.cnt[q];
+  }
+  for (unsigned v = blockIdx.x; v < Vs; v += gridDim.x) {
+    int r0 = first_r0, r1 = first_r1;
+    if (split) {
+      if (!sp.range(v, r0, r1)) break;
+    } else if (v != blockIdx.x) {
+      r0 = (int)v << 4; r1 = r0 + 16;                      // (ChainDeal::range: rounds only of single tiles)
+    }
     CHAIN_NOTE(12, (unsigned long long)(r1 >= r0 ? wall_clock64() : 0));   // range known
     chain_pieces(r0, r1, [&](int rs, int take) {
       switch (take) {
-        case 1: chain_range<H, 1>(p, rs, sp.Mw, smem, cnt); break;
-        case 2: chain_range<H, 2>(p, rs, sp.Mw, smem, cnt); break;
-        case 3: chain_range<H, 3>(p, rs, sp.Mw, smem, cnt); break;
-        case 4: chain_range<H, 4>(p, rs, sp.Mw, smem, cnt); break;
-        case 5: chain_range<H, 5>(p, rs, sp.Mw, smem, cnt); break;
-        default: chain_range<H, 6>(p, rs, sp.Mw, smem, cnt); break;
+        case 1: chain_range<H, 1>(p, rs, Mw, smem, cnt); break;
+        case 2: chain_range<H, 2>(p, rs, Mw, smem, cnt); break;
+        case 3: chain_range<H, 3>(p, rs, Mw, smem, cnt); break;
+        case 4: chain_range<H, 4>(p, rs, Mw, smem, cnt); break;
+        case 5: chain_range<H, 5>(p, rs, Mw, smem, cnt); break;
+        default: chain_range<H, 6>(p, rs, Mw, smem, cnt); break;
       }
     });
   }
 }
 
-// The split as the DEVICE computes it, for the tests (dsbdd_chain_split_probe): one thread per workgroup goes through
-// node_chain_kernel's lines up to chain_range and writes its pieces where the host's list has them, the last one the header.
+// A split (ChainSplit / ChainDealt) as the DEVICE computes it, for the tests (dsbdd_chain_split_probe, dsbdd_chain_deal_probe):
+// one thread per workgroup goes through node_chain_kernel's lines up to chain_range and writes its pieces where the host's list has them, the last one the header.
+template <class Split>
 __global__ void chain_split_probe_kernel(NodeChainArgs p, int H, unsigned* header, int* pieces, long long capacity,
                                          long long* n_pieces) {
   if (threadIdx.x != 0) return;
-  const ChainSplit sp(chain_split_input(p, H, (int)gridDim.x));
+  const Split sp(chain_split_input(p, H, (int)gridDim.x));
   const long long n = chain_split_list(sp, gridDim.x, blockIdx.x + 1, blockIdx.x, pieces, capacity);
   if (blockIdx.x == gridDim.x - 1) { sp.report(header); *n_pieces = n; }
 }

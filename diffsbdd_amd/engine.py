@@ -415,8 +415,8 @@ class HipEngine:
         return list(r[:n.value]), list(g[:n.value]), tl.value
 
     def set_option(self, which, value):
-        """Engine switches (include/diffsbdd_hip.h DSBDD_OPT_*).  Setting a value again is free; a change drops the
-        captured graphs."""
+        """Engine switches (include/diffsbdd_hip.h DSBDD_OPT_*, _lib.OPT_*; e.g. _lib.OPT_CHAIN_DEAL: the node chain's row
+        split, 0 / 1).  Setting a value again is free; a change drops the captured graphs."""
         if not hasattr(self, "_options"):
             self._options = {}
         if self._options.get(which) == int(value):

@@ -259,9 +259,15 @@ int dsbdd_engine_last_plan(const dsbdd_engine* e, int32_t* radius, int32_t* ghos
  * over the column tiles (csrc/edge_wave.h).  0 = whole items only (the launch sequence without the option), 1 = on,
  * n > 1 = on with n in place of the resident workgroup count in the rule that picks the split tiles (a test hook: a launch
  * of a few dozen tiles then holds whole rounds and a split remainder).  Every value gives the same bits: the split keeps
- * every output's fmaf chain and every sum's order.  The workspace layout does not depend on it. */
+ * every output's fmaf chain and every sum's order.  The workspace layout does not depend on it.
+ * DSBDD_OPT_CHAIN_DEAL (0 / 1, default 1; environment DSBDD_CHAIN_DEAL): how node_chain_kernel deals its 16-row tiles to the
+ * workgroups (csrc/chain_split.h).  0 = ranges of equal planned cost, cut at the problems' boundaries only in launches of
+ * >= 3 tiles per workgroup (ChainSplit).  1 = cut at every boundary at every launch size and the ranges chosen so that the
+ * slowest workgroup EXECUTES the least (ChainDeal: the smallest bottleneck whose ranges fit the grid; DESIGN.md §5
+ * "Min-max deal").  Both give the same bits: every output element is one fmaf chain over k that does not depend on the
+ * row split.  Part of a chain's definition like DSBDD_OPT_TAIL: the engine never switches it by size. */
 enum { DSBDD_OPT_PRUNE = 0, DSBDD_OPT_CONE = 1, DSBDD_OPT_GRANULE16 = 2, DSBDD_OPT_EMU = 3, DSBDD_OPT_SPLITK = 4,
-       DSBDD_OPT_SHELL = 5, DSBDD_OPT_TAIL = 6 };
+       DSBDD_OPT_SHELL = 5, DSBDD_OPT_TAIL = 6, DSBDD_OPT_CHAIN_DEAL = 7 };
 int dsbdd_engine_set_option(dsbdd_engine* e, int which, int value);
 /* current value of an option (what the environment / set_option left); DSBDD_ERR_ARG (< 0) for an unknown id */
 int dsbdd_engine_get_option(const dsbdd_engine* e, int which);
@@ -436,6 +442,18 @@ int dsbdd_chain_split_probe(void* stream, int32_t M, const int32_t* m_count, int
                             const int32_t* proj_N, const int32_t* proj_first, const int32_t* const* proj_count,
                             int32_t H, int32_t grid, uint32_t* header, int32_t* pieces, int64_t capacity,
                             int64_t* n_pieces);
+
+/* The twins of the two entry points above for the second policy (ChainDeal, DSBDD_OPT_CHAIN_DEAL = 1): same arguments, same
+ * checks, same piece layout.  header: uint32[5] = (Mw rows with work, B executed load of the slowest range, G ranges the
+ * launch may hold: grid, or segments x grid in the fallback, Vs ranges dealt out, fallback 0 / 1), all zero when nothing is
+ * dealt out. */
+int64_t dsbdd_chain_deal_host(int32_t M, int32_t do_mlp, int32_t n_proj, const int32_t* proj_N,
+                              const int32_t* proj_first, const int32_t* proj_count, int32_t H, int32_t grid,
+                              uint32_t* header, int32_t* pieces, int64_t capacity);
+int dsbdd_chain_deal_probe(void* stream, int32_t M, const int32_t* m_count, int32_t do_mlp, int32_t n_proj,
+                           const int32_t* proj_N, const int32_t* proj_first, const int32_t* const* proj_count,
+                           int32_t H, int32_t grid, uint32_t* header, int32_t* pieces, int64_t capacity,
+                           int64_t* n_pieces);
 
 /* Radius graph (dynamics.py:169-187) -> edge list sorted by (row, col).
  * x [n_lig+n_pocket][3]; scratch: node_batch [N], lig_off/poc_off [batch+1],

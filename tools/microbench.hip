@@ -1,7 +1,7 @@
 // Standalone timing harness for the hot kernels (no torch: a run costs seconds on the GPU box).
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DVARIANT flags] tools/microbench.hip -o tools/bin/mb_<tag>
-//   tools/bin/mb_<tag> [B] [reps]
+//   tools/bin/mb_<tag> [B] [reps] [chain_deal 0 | 1]
 //
 // Builds a synthetic batch with the geometry of the benchmark workload (B samples x (23 ligand + 286 pocket)
 // nodes, 5 A radius graph on uniformly random points at the density of a protein pocket, ligand-ligand complete,
@@ -78,6 +78,7 @@ static float time_us(F&& launch, int reps) {
 int main(int argc, char** argv) {
   const int B = argc > 1 ? atoi(argv[1]) : 64;
   const int reps = argc > 2 ? atoi(argv[2]) : 20;
+  const int chain_deal = argc > 3 ? atoi(argv[3]) : 1;      // node_chain_kernel's row split (NodeChainArgs::deal)
   constexpr int H = 256;
   const int nl = 23, np = 286;
   const int n_lig = B * nl, n_poc = B * np, N = n_lig + n_poc;
@@ -231,51 +232,9 @@ int main(int argc, char** argv) {
     if (!(m == m)) m = 1e30;
     return m / std::max(ref, 1e-30);
   };
-  for (int mi = 0; mi < 3; ++mi) {
-    const int M = mcounts[mi];
-    const int* ridx = mi == 0 ? nullptr : d_rows;
-    const int* mc = mi == 0 ? nullptr : d_mcounts + mi;
-    NodeLinearArgs n1{d_hn, H, H, d_aggc, H, H, W1, H, b1, nullptr, 0, d_t1, H, N, H, 1, ridx, mc};
-    NodeLinearArgs n2{d_t1, H, H, nullptr, 0, 0, W2, H, b2n, d_hn, H, d_hn, H, N, H, 0, ridx, mc};
-    NodeLinearArgs grp[3] = {
-        {d_hn, H, H, nullptr, 0, 0, Wc, 4 * H, nullptr, nullptr, 0, d_pqc, 4 * H, N, 2 * H, 0, d_rows, d_mcounts + 2},
-        {d_hn, H, H, nullptr, 0, 0, Wc + 2 * H, 4 * H, nullptr, nullptr, 0, d_pqc + 2 * H, 4 * H, n_lig, 2 * H, 0, nullptr, nullptr},
-        {d_hn, H, H, nullptr, 0, 0, Wpq, 2 * H, nullptr, nullptr, 0, d_pqg, 2 * H, N, 2 * H, 0, ridx, mc}};
-    NodeChainArgs ca{};
-    ca.row_idx = d_rows; ca.m_count = d_mcounts + mi; ca.M = N; ca.do_mlp = 1; ca.h = d_hc; ca.agg = d_aggc;
-    ca.W1p = W1p; ca.b1 = b1; ca.W2p = W2p; ca.b2 = b2n; ca.n_proj = 3;
-    ca.proj[0] = ChainProj{Wcp, d_pqc2, 4 * H, 2 * H, d_mcounts + 2, 0};                                          // Qc|Qx: active rows
-    ca.proj[1] = ChainProj{Wcp + (size_t)(2 * H / 16) * (H / 16) * 256, d_pqc2 + 2 * H, 4 * H, 2 * H, d_mcounts + 3, 0};   // Pc|Px: ligand rows
-    ca.proj[2] = ChainProj{Wpqp, d_pqg2, 2 * H, 2 * H, nullptr, 0};                                                // next P|Q: all rows
-    // ---- one clean run of either path from the same input: results must agree (fp32 summation order differs) ----
-    CK(hipMemcpy(d_hn, d_h0, (size_t)N * H * 4, hipMemcpyDeviceToDevice)); CK(hipMemcpy(d_hc, d_h0, (size_t)N * H * 4, hipMemcpyDeviceToDevice));
-    CK(hipMemset(d_pqg, 0, (size_t)N * 2 * H * 4)); CK(hipMemset(d_pqc, 0, (size_t)N * 4 * H * 4));
-    CK(hipMemset(d_pqg2, 0, (size_t)N * 2 * H * 4)); CK(hipMemset(d_pqc2, 0, (size_t)N * 4 * H * 4));
-    (void)launch_node_linear(0, n1); (void)launch_node_linear(0, n2); (void)launch_node_group(0, grp, 3);
-    CK(launch_node_chain(0, ca, H, n_cu));
-    CK(hipDeviceSynchronize());
-    printf("| chain vs three launches, max |diff| / max |ref| (M = %d): h %.2e, next P|Q %.2e, coordinate projections %.2e | | | | | |\n", M,
-           maxdiff(d_hn, d_hc, (size_t)N * H), maxdiff(d_pqg, d_pqg2, (size_t)N * 2 * H), maxdiff(d_pqc, d_pqc2, (size_t)N * 4 * H));
-    const float u1 = time_us([&] { (void)launch_node_linear(0, n1); }, reps);
-    const float u2 = time_us([&] { (void)launch_node_linear(0, n2); }, reps);
-    const float u3 = time_us([&] { (void)launch_node_group(0, grp, 3); }, reps);
-    const float uc = time_us([&] { (void)launch_node_chain(0, ca, H, n_cu); }, reps);
-    NodeChainArgs cm = ca; cm.n_proj = 0;
-    const float um = time_us([&] { (void)launch_node_chain(0, cm, H, n_cu); }, reps);
-    NodeChainArgs cp = ca; cp.do_mlp = 0;
-    const float up = time_us([&] { (void)launch_node_chain(0, cp, H, n_cu); }, reps);
-    const double f1 = 2.0 * M * 2.0 * H * H, f2 = 2.0 * M * (double)H * H,
-                 f3 = 2.0 * ((double)M * H * 2 * H + 3639.0 * H * 2 * H + (double)n_lig * H * 2 * H);
-    printf("| node MLP layer 1 (K=512,N=256) | %d | %.1f | %.1f | %.3f | |\n", M, u1, f1 / u1 / 1e6, f1 / u1 / 1e6 / 157.3);
-    printf("| node MLP layer 2 (K=256,N=256,+res) | %d | %.1f | %.1f | %.3f | |\n", M, u2, f2 / u2 / 1e6, f2 / u2 / 1e6 / 157.3);
-    printf("| grouped projections (Qc|Qx act, Pc|Px lig, next P|Q) | %d | %.1f | %.1f | %.3f | |\n", M, u3, f3 / u3 / 1e6, f3 / u3 / 1e6 / 157.3);
-    printf("| = node phase of one block, three launches | %d | %.1f | %.1f | %.3f | |\n", M, u1 + u2 + u3, (f1 + f2 + f3) / (u1 + u2 + u3) / 1e6,
-           (f1 + f2 + f3) / (u1 + u2 + u3) / 1e6 / 157.3);
-    printf("| **node_chain: MLP + 3 projections, one launch** | %d | %.1f | %.1f | %.3f | |\n", M, uc, (f1 + f2 + f3) / uc / 1e6, (f1 + f2 + f3) / uc / 1e6 / 157.3);
-    printf("| node_chain: MLP only | %d | %.1f | %.1f | %.3f | |\n", M, um, (f1 + f2) / um / 1e6, (f1 + f2) / um / 1e6 / 157.3);
-    printf("| node_chain: projections only (h from global) | %d | %.1f | %.1f | %.3f | |\n", M, up, f3 / up / 1e6, f3 / up / 1e6 / 157.3);
 #ifdef DSBDD_CHAIN_TS
-    {   // in-kernel timeline of wave 0 of every workgroup (shader clock), one launch
+  // in-kernel timeline of wave 0 of every workgroup (shader clock), one launch
+  auto timeline = [&](const NodeChainArgs& ca, int M) {
       unsigned long long* d_ts = dev_zero<unsigned long long>((size_t)n_cu * 32);
       CK(hipMemcpyToSymbol(HIP_SYMBOL(g_chain_ts), &d_ts, sizeof(d_ts)));
       CK(launch_node_chain(0, ca, H, n_cu));
@@ -320,7 +279,54 @@ int main(int argc, char** argv) {
       }
       printf("| ... entry -> end | | %.0f cycles = %.1f us by the 100 MHz wall clock -> shader clock %.2f GHz | | | |\n", tot / cnt,
              wall / cnt / 100.0, (tot / cnt) / (wall / cnt * 10.0));
-    }
+  };
+#endif
+  for (int mi = 0; mi < 3; ++mi) {
+    const int M = mcounts[mi];
+    const int* ridx = mi == 0 ? nullptr : d_rows;
+    const int* mc = mi == 0 ? nullptr : d_mcounts + mi;
+    NodeLinearArgs n1{d_hn, H, H, d_aggc, H, H, W1, H, b1, nullptr, 0, d_t1, H, N, H, 1, ridx, mc};
+    NodeLinearArgs n2{d_t1, H, H, nullptr, 0, 0, W2, H, b2n, d_hn, H, d_hn, H, N, H, 0, ridx, mc};
+    NodeLinearArgs grp[3] = {
+        {d_hn, H, H, nullptr, 0, 0, Wc, 4 * H, nullptr, nullptr, 0, d_pqc, 4 * H, N, 2 * H, 0, d_rows, d_mcounts + 2},
+        {d_hn, H, H, nullptr, 0, 0, Wc + 2 * H, 4 * H, nullptr, nullptr, 0, d_pqc + 2 * H, 4 * H, n_lig, 2 * H, 0, nullptr, nullptr},
+        {d_hn, H, H, nullptr, 0, 0, Wpq, 2 * H, nullptr, nullptr, 0, d_pqg, 2 * H, N, 2 * H, 0, ridx, mc}};
+    NodeChainArgs ca{};
+    ca.row_idx = d_rows; ca.m_count = d_mcounts + mi; ca.M = N; ca.do_mlp = 1; ca.h = d_hc; ca.agg = d_aggc;
+    ca.W1p = W1p; ca.b1 = b1; ca.W2p = W2p; ca.b2 = b2n; ca.n_proj = 3;
+    ca.deal = chain_deal;
+    ca.proj[0] = ChainProj{Wcp, d_pqc2, 4 * H, 2 * H, d_mcounts + 2, 0};                                          // Qc|Qx: active rows
+    ca.proj[1] = ChainProj{Wcp + (size_t)(2 * H / 16) * (H / 16) * 256, d_pqc2 + 2 * H, 4 * H, 2 * H, d_mcounts + 3, 0};   // Pc|Px: ligand rows
+    ca.proj[2] = ChainProj{Wpqp, d_pqg2, 2 * H, 2 * H, nullptr, 0};                                                // next P|Q: all rows
+    // ---- one clean run of either path from the same input: results must agree (fp32 summation order differs) ----
+    CK(hipMemcpy(d_hn, d_h0, (size_t)N * H * 4, hipMemcpyDeviceToDevice)); CK(hipMemcpy(d_hc, d_h0, (size_t)N * H * 4, hipMemcpyDeviceToDevice));
+    CK(hipMemset(d_pqg, 0, (size_t)N * 2 * H * 4)); CK(hipMemset(d_pqc, 0, (size_t)N * 4 * H * 4));
+    CK(hipMemset(d_pqg2, 0, (size_t)N * 2 * H * 4)); CK(hipMemset(d_pqc2, 0, (size_t)N * 4 * H * 4));
+    (void)launch_node_linear(0, n1); (void)launch_node_linear(0, n2); (void)launch_node_group(0, grp, 3);
+    CK(launch_node_chain(0, ca, H, n_cu));
+    CK(hipDeviceSynchronize());
+    printf("| chain vs three launches, max |diff| / max |ref| (M = %d): h %.2e, next P|Q %.2e, coordinate projections %.2e | | | | | |\n", M,
+           maxdiff(d_hn, d_hc, (size_t)N * H), maxdiff(d_pqg, d_pqg2, (size_t)N * 2 * H), maxdiff(d_pqc, d_pqc2, (size_t)N * 4 * H));
+    const float u1 = time_us([&] { (void)launch_node_linear(0, n1); }, reps);
+    const float u2 = time_us([&] { (void)launch_node_linear(0, n2); }, reps);
+    const float u3 = time_us([&] { (void)launch_node_group(0, grp, 3); }, reps);
+    const float uc = time_us([&] { (void)launch_node_chain(0, ca, H, n_cu); }, reps);
+    NodeChainArgs cm = ca; cm.n_proj = 0;
+    const float um = time_us([&] { (void)launch_node_chain(0, cm, H, n_cu); }, reps);
+    NodeChainArgs cp = ca; cp.do_mlp = 0;
+    const float up = time_us([&] { (void)launch_node_chain(0, cp, H, n_cu); }, reps);
+    const double f1 = 2.0 * M * 2.0 * H * H, f2 = 2.0 * M * (double)H * H,
+                 f3 = 2.0 * ((double)M * H * 2 * H + 3639.0 * H * 2 * H + (double)n_lig * H * 2 * H);
+    printf("| node MLP layer 1 (K=512,N=256) | %d | %.1f | %.1f | %.3f | |\n", M, u1, f1 / u1 / 1e6, f1 / u1 / 1e6 / 157.3);
+    printf("| node MLP layer 2 (K=256,N=256,+res) | %d | %.1f | %.1f | %.3f | |\n", M, u2, f2 / u2 / 1e6, f2 / u2 / 1e6 / 157.3);
+    printf("| grouped projections (Qc|Qx act, Pc|Px lig, next P|Q) | %d | %.1f | %.1f | %.3f | |\n", M, u3, f3 / u3 / 1e6, f3 / u3 / 1e6 / 157.3);
+    printf("| = node phase of one block, three launches | %d | %.1f | %.1f | %.3f | |\n", M, u1 + u2 + u3, (f1 + f2 + f3) / (u1 + u2 + u3) / 1e6,
+           (f1 + f2 + f3) / (u1 + u2 + u3) / 1e6 / 157.3);
+    printf("| **node_chain: MLP + 3 projections, one launch** | %d | %.1f | %.1f | %.3f | |\n", M, uc, (f1 + f2 + f3) / uc / 1e6, (f1 + f2 + f3) / uc / 1e6 / 157.3);
+    printf("| node_chain: MLP only | %d | %.1f | %.1f | %.3f | |\n", M, um, (f1 + f2) / um / 1e6, (f1 + f2) / um / 1e6 / 157.3);
+    printf("| node_chain: projections only (h from global) | %d | %.1f | %.1f | %.3f | |\n", M, up, f3 / up / 1e6, f3 / up / 1e6 / 157.3);
+#ifdef DSBDD_CHAIN_TS
+    timeline(ca, M);
 #endif
     if (mi == 0) {   // the launch's fixed cost: 16 rows (one row tile on one workgroup, every other workgroup only computes the split)
       NodeChainArgs ct = cm; ct.m_count = d_mcounts + 4;
@@ -328,6 +334,28 @@ int main(int argc, char** argv) {
       NodeChainArgs c3 = ca; c3.m_count = d_mcounts + 4;
       const float ut3 = time_us([&] { (void)launch_node_chain(0, c3, H, n_cu); }, reps);
       printf("| node_chain: 16 rows (fixed cost), MLP only / MLP + 3 projections | 16 | %.1f / %.1f | | | |\n", ut, ut3);
+    }
+  }
+  // the ghost stages of a headline call: 286 ghost rows in front of the level list, the coordinate projections behind them
+  {
+    std::vector<int> gcounts = {3639 + 286, 11545 + 286, 18764 + 286, 18764};
+    int* d_gcounts = dev(gcounts);
+    for (int gi = 0; gi < 4; ++gi) {
+      const int first = gi < 3 ? 286 : 0;
+      NodeChainArgs ca{};
+      ca.row_idx = d_rows; ca.m_count = d_gcounts + gi; ca.M = N; ca.do_mlp = 1; ca.h = d_hc; ca.agg = d_aggc;
+      ca.W1p = W1p; ca.b1 = b1; ca.W2p = W2p; ca.b2 = b2n; ca.n_proj = 3;
+      ca.deal = chain_deal;
+      ca.proj[0] = ChainProj{Wcp, d_pqc2, 4 * H, 2 * H, d_mcounts + 2, first};
+      ca.proj[1] = ChainProj{Wcp + (size_t)(2 * H / 16) * (H / 16) * 256, d_pqc2 + 2 * H, 4 * H, 2 * H, d_mcounts + 3, first};
+      ca.proj[2] = ChainProj{Wpqp, d_pqg2, 2 * H, 2 * H, nullptr, 0};
+      if (gcounts[gi] > N) continue;
+      CK(launch_node_chain(0, ca, H, n_cu));
+      const float ug = time_us([&] { (void)launch_node_chain(0, ca, H, n_cu); }, reps);
+      printf("| node_chain: %d rows, %d ghost rows in front, MLP + 3 projections | %d | %.1f | | | |\n", gcounts[gi], first, gcounts[gi], ug);
+#ifdef DSBDD_CHAIN_TS
+      timeline(ca, gcounts[gi]);
+#endif
     }
   }
 #endif
