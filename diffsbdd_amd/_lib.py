@@ -140,6 +140,9 @@ SIGNATURES = {
     "dsbdd_vina_score_grad": (C.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
     "dsbdd_vina_minimize": (C.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _F, _F, _I32, _P, _P,
                                       _P, _P]),
+    "dsbdd_vina_torsions": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _I32, _P, _P, _P, _P]),
+    "dsbdd_vina_intra": (C.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    "dsbdd_vina_flex": (C.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _I32, _F, _F, _I32] + [_P] * 15),
     "dsbdd_pack_ligands": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _P, _P, _P, _I64, _I64, _I32, _P, _P, _P, _P, _P]),
     # training-step building blocks (struct arguments are passed by pointer: ctypes.byref / arrays)
     "dsbdd_train_scratch_bytes": (C.c_size_t, [_I32, _I64, _I64]),

@@ -1,5 +1,5 @@
 // Thin C-ABI wrappers of the stand-alone kernels (included by engine.hip): DDPM steps (ddpm.h), keyed noise, node GEMM,
-// the node chain's row split (chain_split.h), bond orders (molecule.h), molecule graph statistics and fingerprint distances (mol_metrics.h), pose checks, the Vina-type score, its gradient and the rigid-body minimiser (pose_check.h, vina_score.h, vina_grad.h, vina_minimize.h on pair_sweep.h), ligand packing (ligand_pack.h), the radius graph (radius_graph.h).
+// the node chain's row split (chain_split.h), bond orders (molecule.h), molecule graph statistics and fingerprint distances (mol_metrics.h), pose checks, the Vina-type score, its gradient, the rigid-body minimiser, the torsion tree, the intramolecular term and the flexible minimiser (pose_check.h, vina_score.h, vina_grad.h, vina_minimize.h, vina_torsion.h, vina_intra.h, vina_flex.h on pair_sweep.h), ligand packing (ligand_pack.h), the radius graph (radius_graph.h).
 #pragma once
 
 extern "C" {
@@ -375,6 +375,70 @@ int dsbdd_vina_minimize(void* stream, const float* lig_x, const int32_t* lig_cod
                   atom_out, mol_out, mol_flag}, atom_grad, mol_grad}, lig_x, step, tol, max_evals, x_out, mol_pose, mol_min,
                 mol_stat};
   hipLaunchKernelGGL(vina_minimize_kernel, dim3((unsigned)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_vina_torsions(void* stream, const int8_t* order, const int32_t* atom_type, const int32_t* mol_off, int64_t batch,
+                        int32_t n_types, const int32_t* class_elem, int32_t n_max, int32_t* tor_int, int32_t* tor_end,
+                        int32_t* tor_side, int32_t* pair_mask) {
+  StreamDevice stream_device_(stream);
+  if (!order || !atom_type || !mol_off || !class_elem || !tor_int || !tor_end || !tor_side || !pair_mask)
+    return fail(DSBDD_ERR_ARG, "null argument");
+  if (batch < 0 || batch > 0x7fffffff || n_types < 1) return fail(DSBDD_ERR_ARG, "bad batch or n_types");
+  if (n_max < 1 || n_max > kMolMaxAtoms)
+    return fail(DSBDD_ERR_ARG, "n_max must be in [1, " + std::to_string(kMolMaxAtoms) + "]");
+  if (batch == 0) return DSBDD_OK;
+  VinaTorsionArgs a{reinterpret_cast<const signed char*>(order), atom_type, mol_off, class_elem, (int)batch, n_types, n_max,
+                    tor_int, tor_end, tor_side, pair_mask};
+  hipLaunchKernelGGL(vina_torsion_kernel, dim3((unsigned)batch), dim3(64), 0, static_cast<hipStream_t>(stream), a);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_vina_intra(void* stream, const float* lig_x, const int32_t* lig_code, const int32_t* mol_off, int64_t batch,
+                     const int32_t* pair_mask, float* atom_out, float* mol_out, int32_t* mol_flag, float* atom_grad) {
+  StreamDevice stream_device_(stream);
+  if (!lig_x || !lig_code || !mol_off || !pair_mask || !atom_out || !mol_out || !mol_flag || !atom_grad)
+    return fail(DSBDD_ERR_ARG, "null argument");
+  if (int rc = check_pair_counts(batch, 0)) return rc;
+  if (batch == 0) return DSBDD_OK;
+  // the molecule's own rows are the group of its sweep
+  VinaIntraArgs a{{{{lig_x, mol_off, nullptr, lig_x, mol_off, (int)batch, (int)batch}, lig_code, nullptr, lig_code, atom_out,
+                    mol_out, mol_flag}, atom_grad, nullptr}, pair_mask};
+  hipLaunchKernelGGL(vina_intra_kernel, dim3((unsigned)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+  HIP_TRY(hipGetLastError());
+  return DSBDD_OK;
+}
+
+int dsbdd_vina_flex(void* stream, const float* lig_x, const int32_t* lig_code, const int32_t* mol_off, int64_t batch,
+                    const int32_t* mol_group, const int32_t* mol_int, const float* poc_x, const int32_t* poc_code,
+                    const int32_t* group_off, int64_t n_groups, const int32_t* tor_int, const int32_t* tor_end,
+                    const int32_t* tor_side, const int32_t* pair_mask, int32_t dofs, float step, float tol, int32_t max_evals,
+                    float* atom_out, float* mol_out, int32_t* mol_flag, float* atom_grad, float* mol_grad, float* intra_atom,
+                    float* intra_mol, int32_t* intra_flag, float* intra_grad, float* x_out, float* mol_pose, float* mol_flex,
+                    int32_t* mol_stat, float* theta, float* tau) {
+  StreamDevice stream_device_(stream);
+  if (!lig_x || !lig_code || !mol_off || !mol_group || !mol_int || !poc_x || !poc_code || !group_off || !tor_int || !tor_end ||
+      !tor_side || !pair_mask || !atom_out || !mol_out || !mol_flag || !atom_grad || !mol_grad || !intra_atom || !intra_mol ||
+      !intra_flag || !intra_grad || !x_out || !mol_pose || !mol_flex || !mol_stat || !theta || !tau)
+    return fail(DSBDD_ERR_ARG, "null argument");
+  if (int rc = check_pair_counts(batch, n_groups)) return rc;
+  if (!std::isfinite(step) || !(step > 0.f) || !std::isfinite(tol) || !(tol > 0.f))
+    return fail(DSBDD_ERR_ARG, "step and tol must be finite and positive");
+  if (max_evals < 1 || max_evals > kVinaMaxEvals)
+    return fail(DSBDD_ERR_ARG, "max_evals must be in [1, " + std::to_string(kVinaMaxEvals) + "]");
+  if (dofs < 1 || dofs > (kVinaDofRigid | kVinaDofTorsions)) return fail(DSBDD_ERR_ARG, "dofs must be 1, 2 or 3");
+  if (batch == 0) return DSBDD_OK;                                  // nothing is read or written
+  if (lig_x == x_out) return fail(DSBDD_ERR_ARG, "lig_x and x_out must not alias");
+  // both sweeps read the pose under evaluation from x_out
+  VinaFlexArgs a{{{{{x_out, mol_off, mol_group, poc_x, group_off, (int)batch, (int)n_groups}, lig_code, mol_int, poc_code,
+                    atom_out, mol_out, mol_flag}, atom_grad, mol_grad}, lig_x, step, tol, max_evals, x_out, mol_pose, mol_flex,
+                  mol_stat},
+                 {{{{x_out, mol_off, nullptr, x_out, mol_off, (int)batch, (int)batch}, lig_code, nullptr, lig_code, intra_atom,
+                    intra_mol, intra_flag}, intra_grad, nullptr}, pair_mask},
+                 tor_int, tor_end, tor_side, dofs, theta, tau};
+  hipLaunchKernelGGL(vina_flex_kernel, dim3((unsigned)batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
   HIP_TRY(hipGetLastError());
   return DSBDD_OK;
 }

@@ -43,6 +43,9 @@
 #include "vina_score.h"
 #include "vina_grad.h"
 #include "vina_minimize.h"
+#include "vina_torsion.h"
+#include "vina_intra.h"
+#include "vina_flex.h"
 #include "node_chain.h"
 #include "node_linear.h"
 #include "train.h"

@@ -1,5 +1,5 @@
 // What the ligand-pocket pair kernels share (pose_check_kernel in pose_check.h, vina_score_kernel in vina_score.h,
-// vina_grad_kernel in vina_grad.h), defined once: the batch, its range check, the squared distance, and the sweep of a molecule's atoms over its pocket group.
+// vina_grad_kernel in vina_grad.h, and vina_intra_kernel in vina_intra.h, whose "group" is the molecule itself), defined once: the batch, its range check, the squared distance, and the sweep of a molecule's atoms over its pocket group.
 //
 // pair_sweep: one workgroup per molecule.  The pocket atoms of the molecule's group pass through LDS in tiles of kPairTile
 // (x, y, z and one word of the policy's as one float4 each: lane j reads 16 contiguous bytes, conflict free); wave w takes

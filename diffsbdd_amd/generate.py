@@ -242,7 +242,9 @@ class LigandGenerator:
     def _vina_options(vina):
         """The samplers' `vina` keyword: None / False = off (nothing runs); True = on; a dict may carry 'residues' where the
         sampler is not given any (`diversify_ligands`) and 'minimize': True, or a dict of `step` / `tol` / `max_evals`, also
-        relaxes every sample as a rigid body (vina.vina_minimize) and attaches that record as `m.vina_min`."""
+        relaxes every sample as a rigid body (vina.vina_minimize) and attaches that record as `m.vina_min`; with
+        `torsions`: True in that dict (and `dofs`) the rotatable bonds turn as well, under inter + intra, and the record
+        is the flexible one (`vina.MolVinaFlex`)."""
         if vina is None or vina is False:
             return None
         opts = {} if vina is True else dict(vina)
@@ -252,7 +254,7 @@ class LigandGenerator:
         minimize = opts.pop("minimize", None)
         if minimize is not None and minimize is not False:
             settings = {} if minimize is True else dict(minimize)
-            unknown = set(settings) - {"step", "tol", "max_evals"}
+            unknown = set(settings) - {"step", "tol", "max_evals", "torsions", "dofs"}
             if unknown:
                 raise ValueError(f"vina: unknown minimize setting(s) {sorted(unknown)}")
             opts["minimize"] = settings
@@ -340,11 +342,14 @@ class LigandGenerator:
         arguments.  Returns one dict per molecule, in order: the keys of `vina_gradients` at the returned pose, 'x'
         (float32 [n, 3], its heavy-atom coordinates), 'inter_start', 'score_start', 'status' (index into `vina.STATUS`),
         'evals', 'accepted', 'rmsd'.  See `vina.VINA_MIN_COVERAGE`: rigid ligand, rigid protein, a local search, not smina
-        or qvina output."""
+        or qvina output.
+        With `torsions=True` among the settings (and `dofs`) the relaxation is the flexible one, under inter + intra with
+        the rotatable bonds turning; the dicts gain 'intra', 'intra_start', 'n_torsions', 'torsions_found' and 'theta'.
+        See `vina.VINA_FLEX_COVERAGE`."""
         from . import vina as vina_mod
         residues = self._scope_residues(pdb_file, scope, pocket_ids, ref_ligand)
         pockets = vina_mod.VinaPocket.upload([vina_mod.type_pocket(residues)], self.device)
-        return [dict(r.as_dict(), grad=r.grad, x=r.x)
+        return [dict(r.as_dict(), grad=r.grad, x=r.x, **({"theta": r.theta} if hasattr(r, "theta") else {}))
                 for r in vina_mod.minimize_molecules(molecules, pockets, self.dataset_info, **settings)]
 
     @torch.no_grad()

@@ -42,7 +42,13 @@ doubled back after one that does) until L < 0.001 A or 200 evaluations.  Rigid l
 
   python -m diffsbdd_amd.vina --pdbfile P.pdb --sdf L.sdf [L2.sdf ...] [--scope protein|pocket --ref_ligand ...]
                               [--bonds distance|file] [--dataset crossdock] [--out scores.csv] [--grad_out atoms.csv]
-                              [--minimize relaxed.sdf [--step 0.25] [--tol 0.001] [--max_evals 200]]
+                              [--minimize relaxed.sdf [--torsions] [--step 0.25] [--tol 0.001] [--max_evals 200]]
+
+Torsion tree, intramolecular term and flexible minimiser (`ligand_torsions`, `vina_intra`, `vina_minimize(torsions=True)`;
+csrc/vina_torsion.h, csrc/vina_intra.h, csrc/vina_flex.h; `torsion_tree`, `_vina_intra_host`, `_vina_flex_host` restate
+them): the rotors that N_rot counts, at most 32 kept, each with the smaller side of the molecule as its moving side; intra =
+the five terms over the ligand's own pairs more than 3 bonds apart that a kept rotor separates; the flexible minimiser is
+the rigid one with the torsion angles as further coordinates and E = inter + intra.  VINA_INTRA_COVERAGE, VINA_FLEX_COVERAGE.
 """
 from __future__ import annotations
 
@@ -80,6 +86,11 @@ E_START, E_FINAL, E_STEP, E_SLOPE = range(4)
 S_STATUS, S_EVALS, S_ACCEPTED = range(3)
 STATUS = ("budget", "converged", "no gradient", "nonfinite")
 MIN_STEP, MIN_TOL, MIN_EVALS, MAX_EVALS = 0.25, 1e-3, 200, 4096
+MAX_TORSIONS, TOR_INT, MASK_WORDS = 32, 4, 4   # rotors kept per molecule, columns of tor_int, int32 words of a 128-bit mask
+T_KEPT, T_FOUND = 0, 1
+MOL_FLEX = 8                           # columns of the flexible minimiser's energies (dsbdd_vina_flex): E_START ... E_SLOPE as above, then
+X_INTRA_START, X_INTRA_FINAL, X_E_START, X_E_FINAL = range(4, 8)
+DOF_RIGID, DOF_TORSIONS = 1, 2         # bits of `dofs`
 EPS32 = 2.0 ** -24
 _RADIUS = np.asarray([0.0] + [XS_RADII[c] for c in CLASSES[1:]], np.float64)
 _LIPSCHITZ = (1.716, 0.429, None, 1.0, 1.0 / 0.7)                                # of the five terms in d (repulsion: 2 |d| + 2 dd)
@@ -129,6 +140,35 @@ VINA_MIN_COVERAGE = (
     "nearest minimum downhill, no global search, no multiple starts), steepest descent and not BFGS, no intramolecular "
     "term; NOT the output of smina or qvina and NOT comparable with their minimised or docked scores; typing is done once, "
     "on the input pose.")
+
+VINA_INTRA_COVERAGE = (
+    "Vina-type intramolecular term: PRESENT = the torsion tree of every ligand (one GPU kernel on the bond-order matrices: "
+    "the rotatable bonds that N_rot counts, at most 32 kept in ascending order of their atom indices, each with the smaller "
+    "side of the molecule as its moving side) and the five pair terms of the Vina-type score with their analytic gradient "
+    "summed by one GPU kernel over the ligand's own heavy-atom pairs closer than 8 A that are more than 3 bonds apart (or "
+    "not connected) and separated by a kept rotatable bond, per atom and per molecule, `intra` = the weighted sum, every "
+    "pair once, not divided by the rotor factor; "
+    "NOT = a minimiser: this entry changes no pose and turns no torsion (the flexible minimiser does, the rigid-body "
+    "minimiser does not read this term); NOT the intramolecular energy smina or Vina print (heavy atoms only, amide and conjugated bonds rotate, typing "
+    "and the tree fixed on the bond orders given); a molecule without rotatable bonds, or longer than 128 atoms, has no "
+    "pair and an intramolecular term of exactly 0.")
+
+VINA_FLEX_COVERAGE = (
+    "Vina-type flexible minimiser: PRESENT = a relaxation of every given pose over its translation, its rotation and its "
+    "rotatable bonds (the torsion tree of the intramolecular term: at most 32 rotors, each turning the smaller side of the "
+    "molecule) under E = inter + intra of the Vina-type score, one GPU launch per batch after the typing and the tree (one "
+    "workgroup per molecule, every evaluation and decision on the device); `inter`, `score` and their gradient are reported "
+    "at the returned pose as the rigid minimiser reports them, `intra` beside them, with both at the start, the torsion "
+    "angles, a status and the RMSD moved; bond lengths, angles and rings keep the input's geometry; "
+    "DEFINED AS = steepest descent in a scaled metric (net force, moment about the centroid over the mean squared radius, "
+    "and per rotor the torque about its axis over the mean squared distance of its side from the axis) with the backtracking "
+    "step of the rigid minimiser: no atom moves more than the step (0.25 A, halved on a trial that does not lower E, doubled "
+    "back after one that does) until it falls below 0.001 A or 200 evaluations are spent; `dofs` switches the rigid body "
+    "(bit 0) or the torsions (bit 1) off; "
+    "NOT = BFGS; NOT a docking run: a local search from one start, the nearest minimum downhill, a rigid protein, heavy atoms "
+    "only (no hydrogens, no charges), typing and the torsion tree fixed on the input pose, amide and conjugated bonds "
+    "rotate, rotors beyond the first 32 and every rotor of a molecule longer than 128 atoms stay rigid; NOT the output of "
+    "smina or qvina and NOT comparable with their minimised or docked scores.")
 
 
 def class_of(symbol):
@@ -686,7 +726,7 @@ def _settings(step, tol, max_evals):
 
 
 def vina_minimize(x, atom_type, lig_mask, pockets, info, mol_group=None, batch=None, orders=None, step=MIN_STEP, tol=MIN_TOL,
-                  max_evals=MIN_EVALS):
+                  max_evals=MIN_EVALS, torsions=False, dofs=DOF_RIGID | DOF_TORSIONS):
     """Rigid-body relaxation of every pose of a batch under `inter`, on device tensors: the typing of `vina_score` (once, on
     the input pose), then one launch of `dsbdd_vina_minimize` (csrc/vina_minimize.h; one workgroup per molecule iterates
     the sweep of `vina_gradient`, every decision on the device); no read-back inside.  Arguments as for `vina_score`;
@@ -694,7 +734,14 @@ def vina_minimize(x, atom_type, lig_mask, pockets, info, mol_group=None, batch=N
     `max_evals` the evaluation budget (1 ... 4096).  x is not written.  -> VinaMinimized of device tensors: the fields of
     `vina_gradient` at the returned pose (bit for bit what `vina_gradient` gives on `x`), `x` [N,3], `pose` [B,8], `energies`
     [B,4], `stat` [B,4] and the properties `status` (index into STATUS), `evals`, `accepted`, `inter_start`, `score_start`,
-    `rmsd`.  `_vina_minimize_host` states the iteration; see `VINA_MIN_COVERAGE` for what this is not."""
+    `rmsd`.  `_vina_minimize_host` states the iteration; see `VINA_MIN_COVERAGE` for what this is not.
+    torsions=True: the flexible relaxation instead (`dsbdd_vina_torsions`, then one launch of `dsbdd_vina_flex`,
+    csrc/vina_flex.h): the rotatable bonds turn as well and the objective is inter + intra; `dofs` bit 0 = the rigid body,
+    bit 1 = the torsions.  -> VinaFlexed: the same fields (`inter`, `score`, the gradient stay the intermolecular ones;
+    `energies` [B,8]) and `intra`, `intra_start`, `theta` [B,32], `tau`, `n_torsions`, `torsions_found`, `intra_out`.
+    `_vina_flex_host` states that iteration; see `VINA_FLEX_COVERAGE`.  Without the keyword nothing changes."""
+    if torsions:
+        return _flexed(x, atom_type, lig_mask, pockets, info, mol_group, batch, orders, _settings(step, tol, max_evals), dofs)
     return _scored("vina_minimize", VinaMinimized, x, atom_type, lig_mask, pockets, info, mol_group, batch, orders,
                    _settings(step, tol, max_evals))
 
@@ -795,11 +842,12 @@ def gradient_molecules(molecules, pockets, info="crossdock", mol_group=None, dev
 
 
 def minimize_molecules(molecules, pockets, info="crossdock", mol_group=None, device="cuda", bonds="distance", step=MIN_STEP,
-                       tol=MIN_TOL, max_evals=MIN_EVALS):
+                       tol=MIN_TOL, max_evals=MIN_EVALS, torsions=False, dofs=DOF_RIGID | DOF_TORSIONS):
     """`gradient_molecules` through the launches of `vina_minimize`: the same arguments and the minimiser's settings.
-    -> list of `MolVinaMin`: the records of `gradient_molecules` at the returned pose, with its coordinates `x`."""
+    -> list of `MolVinaMin`: the records of `gradient_molecules` at the returned pose, with its coordinates `x`; with
+    torsions=True list of `MolVinaFlex` (the flexible relaxation)."""
     def entry(*args, **kwargs):
-        return vina_minimize(*args, step=step, tol=tol, max_evals=max_evals, **kwargs)
+        return vina_minimize(*args, step=step, tol=tol, max_evals=max_evals, torsions=torsions, dofs=dofs, **kwargs)
     return _molecule_records(entry, "minimize_molecules", molecules, pockets, info, mol_group, device, bonds)
 
 
@@ -885,10 +933,12 @@ def _molecule_pairs(x, code, q, qcode, dtype):
     return r, r32, d, counted, hyd, hb
 
 
-def _vina_score_host(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_code, group_off, dtype=np.float64, eps=None):
+def _vina_score_host(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_code, group_off, dtype=np.float64, eps=None,
+                     pair_mask=None):
     """`dsbdd_vina_score` in numpy: the same arguments, float32 coordinates, all arithmetic in `dtype` (float64: the
     specification).  -> (VinaScores of arrays in `dtype`, the batch's smallest |r - 8| over typed pairs).  With `eps` also
-    the forward error bound of every output (see `error_bound`): (..., atom_bound [N, 5], mol_bound [B, 7])."""
+    the forward error bound of every output (see `error_bound`): (..., atom_bound [N, 5], mol_bound [B, 7]).  `pair_mask`
+    (int32 [N, 4], `_vina_intra_host` alone): only the pairs (i, j) with bit j of atom i's 128-bit mask set are counted."""
     x = np.asarray(_np(lig_x), np.float32).reshape(-1, 3)
     code = np.asarray(_np(lig_code), np.int32).reshape(-1)
     q = np.asarray(_np(poc_x), np.float32).reshape(-1, 3)
@@ -923,6 +973,9 @@ def _vina_score_host(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_co
             continue
         r, r32, d, counted, hyd, hb = _molecule_pairs(x[lo:hi], code[lo:hi], q[glo:ghi], qcode[glo:ghi], dtype)
         typed = ((code[lo:hi, None] & CLASS_MASK) != 0) & ((qcode[None, glo:ghi] & CLASS_MASK) != 0)
+        if pair_mask is not None:
+            listed = unpack_masks(pair_mask[lo:hi], ghi - glo)
+            counted, typed = counted & listed, typed & listed
         with np.errstate(invalid="ignore"):
             near = np.abs(r32.astype(np.float64) - CUTOFF)[typed & np.isfinite(r32)]
         if near.size:
@@ -984,15 +1037,17 @@ def pair_slopes(d, hydrophobic=True, hbond=True):
     return out
 
 
-def _vina_grad_host(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_code, group_off, dtype=np.float64, eps=None):
+def _vina_grad_host(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_code, group_off, dtype=np.float64, eps=None,
+                    pair_mask=None):
     """`dsbdd_vina_score_grad` in numpy: the arguments of `_vina_score_host`, float32 coordinates, the counted pairs decided
     by the float32 distance (and a pair whose float32 distance is 0 adds nothing to the gradient), everything else in
     `dtype` from differences and a root formed in `dtype` (float64: the specification; its differences of float32
     coordinates are exact).  -> VinaGradients of arrays in `dtype`: the fields of `_vina_score_host`'s result, grad [N, 3],
     mol_grad [B, 8].  With `eps` also the forward error bound of `grad_error_bound`: (result, grad_bound [N, 3],
     mol_grad_bound [B, 8]), and the smallest distance |d - kink| over the pairs a kink of hydrophobic' / hbond' applies to
-    as `result.kink_margin`."""
-    st, _ = _vina_score_host(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_code, group_off, dtype=dtype)
+    as `result.kink_margin`.  `pair_mask` as for `_vina_score_host`."""
+    st, _ = _vina_score_host(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_code, group_off, dtype=dtype,
+                             pair_mask=pair_mask)
     x = np.asarray(_np(lig_x), np.float32).reshape(-1, 3)
     q = np.asarray(_np(poc_x), np.float32).reshape(-1, 3)
     code, qcode = st.lig_code, np.asarray(_np(poc_code), np.int32).reshape(-1)
@@ -1022,6 +1077,8 @@ def _vina_grad_host(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_cod
         if n == 0 or ghi == glo:
             continue
         r, r32, d, counted, hyd, hb = _molecule_pairs(x[lo:hi], code[lo:hi], q[glo:ghi], qcode[glo:ghi], dtype)
+        if pair_mask is not None:
+            counted = counted & unpack_masks(pair_mask[lo:hi], ghi - glo)
         live = counted & (r32 > 0)                                              # coincident atoms have no direction
         xd = x[lo:hi].astype(dtype)
         e = xd[:, None, :] - q[glo:ghi].astype(dtype)[None, :, :]
@@ -1265,9 +1322,589 @@ def _vina_minimize_host(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc
     return out
 
 
+# ---- torsion tree and intramolecular term ------------------------------------------------------------------------------------
+def pack_masks(bits):
+    """bool [..., k <= 128] -> int32 [..., 4]: atom 32 w + b is bit b of word w (the kernels' 128-bit masks)."""
+    bits = np.asarray(bits, bool)
+    full = np.zeros(bits.shape[:-1] + (32 * MASK_WORDS,), bool)
+    full[..., :bits.shape[-1]] = bits
+    return np.ascontiguousarray(np.packbits(full, axis=-1, bitorder="little")).view("<u4").astype(np.uint32).view(np.int32)
+
+
+def unpack_masks(words, n):
+    """int32 [k, 4] -> bool [k, n]: the first n bits of every mask; a bit at or above 128 is not set."""
+    words = np.ascontiguousarray(np.asarray(_np(words), np.int32).reshape(-1, MASK_WORDS))
+    bits = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little").astype(bool)
+    out = np.zeros((len(words), n), bool)
+    out[:, :min(n, bits.shape[1])] = bits[:, :n]
+    return out
+
+
+def torsion_tree(classes, sym, keep=MAX_TORSIONS):
+    """The torsion tree of one molecule: `classes`, `sym` as for `type_graph`; `keep` = how many rotors are kept (0 for a
+    molecule that is to stay rigid).  -> (rotors, found, pairs): `rotors` the kept ones in ascending (a, c) as (fixed end
+    p, moving end m, side bool [n]); `found` the number of all rotors (= `type_graph`'s n_rot); `pairs` bool [n, n], the
+    pairs of the intramolecular term.
+    Rotor: a single bond (a, c), c < a, both ends of heavy degree >= 2, in no ring.  Side: cut the bond; of the two
+    components its ends fall into, the one with fewer atoms, on a tie the one of a (the higher index).  Any two sides are
+    nested or disjoint (two sides of at most half a component each cannot overlap without one containing the other).
+    pairs[i, j]: i != j, both typed, more than 3 bonds apart or not connected, and exactly one of them in the side of some
+    kept rotor."""
+    classes = np.asarray(classes, np.int64).reshape(-1)
+    n = len(classes)
+    sym = np.asarray(sym, np.int64).reshape(n, n)
+    sym = np.where((sym >= 1) & (sym <= 3), sym, 0)
+    classes = np.where((classes >= 0) & (classes <= C_METAL), classes, C_NONE)
+    bonded = sym > 0
+    deg = bonded.sum(1)
+    nbrs = [np.nonzero(bonded[a])[0].tolist() for a in range(n)]
+    bonds = [(a, c) for a in range(n) for c in nbrs[a]
+             if c < a and sym[a, c] == 1 and deg[a] >= 2 and deg[c] >= 2 and not _bond_in_ring(nbrs, a, c)]
+
+    def component(a, c):                                                        # of a, the bond (a, c) left out
+        seen, front = {a}, [a]
+        while front:
+            nxt = [v for u in front for v in nbrs[u] if not (u == a and v == c)]
+            front = list(set(nxt) - seen)
+            seen |= set(front)
+        return seen
+
+    rotors = []
+    for a, c in bonds[:max(int(keep), 0)]:
+        of_a, of_c = component(a, c), component(c, a)
+        side = np.zeros(n, bool)
+        if len(of_a) <= len(of_c):
+            side[list(of_a)] = True
+            rotors.append((c, a, side))
+        else:
+            side[list(of_c)] = True
+            rotors.append((a, c, side))
+    cut = np.zeros((n, n), bool)
+    for _, _, side in rotors:
+        cut |= side[:, None] != side[None, :]
+    step = bonded | np.eye(n, dtype=bool)
+    near = step.copy()
+    for _ in range(2):
+        near = (near.astype(np.int64) @ step.astype(np.int64)) > 0
+    typed = classes != C_NONE
+    return rotors, len(bonds), cut & ~near & typed[:, None] & typed[None, :]
+
+
+@dataclass
+class VinaTorsions:
+    """The outputs of `dsbdd_vina_torsions` (device tensors from `ligand_torsions`, numpy arrays from `_vina_torsions_host`)."""
+    ints: object             # int32 [B, 4]: rotors kept, rotors found, 0, 0
+    ends: object             # int32 [B, 32, 2]: fixed end, moving end; -1 past the kept
+    sides: object            # int32 [B, 32, 4]: the moving side as a 128-bit mask; 0 past the kept
+    pair_mask: object        # int32 [N, 4]: the partners of every atom in the intramolecular term
+    mol_off: object          # int32 [B + 1]
+
+    kept = property(lambda self: self.ints[:, T_KEPT])
+    found = property(lambda self: self.ints[:, T_FOUND])
+
+
+def _vina_torsions_host(order, atom_type, mol_off, class_elem, fill=0):
+    """`dsbdd_vina_torsions` in numpy (integers; exact, the specification): the arguments of `_vina_type_host`.
+    -> VinaTorsions of arrays.  A molecule longer than n_max keeps no rotor (`found` is counted on its first n_max atoms, as
+    `_vina_type_host` counts N_rot) and the masks of all its atoms are 0; rows of `pair_mask` that belong to no valid molecule
+    keep `fill`."""
+    order = np.asarray(_np(order))
+    B, n_max = order.shape[0], order.shape[1]
+    at = np.asarray(_np(atom_type), np.int64).reshape(-1)
+    off = np.asarray(_np(mol_off), np.int64).reshape(-1)
+    table = np.asarray(_np(class_elem), np.int64).reshape(-1)
+    if len(off) != B + 1:
+        raise ValueError(f"{len(off)} offsets for {B} molecules")
+    out = VinaTorsions(np.zeros((B, TOR_INT), np.int32), np.full((B, MAX_TORSIONS, 2), -1, np.int32),
+                       np.zeros((B, MAX_TORSIONS, MASK_WORDS), np.int32), np.full((len(at), MASK_WORDS), fill, np.int32),
+                       off.astype(np.int32))
+    n_total = off[B]
+    for b in range(B):
+        lo, hi = int(off[b]), int(off[b + 1])
+        size = hi - lo if (lo >= 0 and hi >= lo and hi <= n_total) else 0
+        n = min(size, n_max)
+        t = at[lo:lo + n]
+        ok = (t >= 0) & (t < len(table))
+        classes = np.where(ok, table[np.where(ok, t, 0)], C_NONE)
+        low = np.tril(order[b, :n, :n].astype(np.int64), -1)
+        rotors, found, pairs = torsion_tree(classes, low + low.T, 0 if size > n_max else MAX_TORSIONS)
+        out.ints[b, :2] = len(rotors), found
+        for k, (p, m, side) in enumerate(rotors):
+            out.ends[b, k] = p, m
+            out.sides[b, k] = pack_masks(side)
+        out.pair_mask[lo:lo + size] = 0
+        if n:
+            out.pair_mask[lo:lo + n] = pack_masks(pairs)
+    return out
+
+
+def ligand_torsions(x, atom_type, lig_mask, info, orders=None, batch=None):
+    """The torsion tree and the intramolecular pair masks of a batch on the device: one launch of `dsbdd_vina_torsions`
+    (csrc/vina_torsion.h) on the inputs of `type_ligands` (the same arguments; x is read only to perceive `orders` when none
+    are given).  -> VinaTorsions of device tensors.  `_vina_torsions_host` / `torsion_tree` state what it computes."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise _lib.HipLibraryError("ligand_torsions needs device tensors (HIP path; no CPU fallback)")
+    lib = _lib.load()
+    dev = x.device
+    decoder, info = _decoder(info)
+    x = x.detach().to(torch.float32).reshape(-1, 3).contiguous()
+    N = int(x.shape[0])
+    at = torch.as_tensor(atom_type, device=dev).to(torch.int32).reshape(-1).contiguous()
+    lig_mask = torch.as_tensor(lig_mask, device=dev).reshape(-1)
+    if at.shape[0] != N or lig_mask.shape[0] != N:
+        raise ValueError(f"{N} coordinates, {at.shape[0]} types, {lig_mask.shape[0]} mask entries")
+    B = _n_molecules(lig_mask, batch)
+    off = _pairs.mol_offsets(lig_mask, B, dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = VinaTorsions(torch.zeros((B, TOR_INT), **i32), torch.full((B, MAX_TORSIONS, 2), -1, **i32),
+                       torch.zeros((B, MAX_TORSIONS, MASK_WORDS), **i32), torch.zeros((N, MASK_WORDS), **i32), off)
+    if B == 0:
+        return out
+    orders = _perceived_orders(x, at, lig_mask, info, B) if orders is None else \
+        torch.as_tensor(orders, device=dev).to(torch.int8).contiguous()
+    if orders.dim() != 3 or orders.shape[0] != B or orders.shape[1] != orders.shape[2] or \
+            not 1 <= orders.shape[1] <= _lib.MOL_MAX_ATOMS:
+        raise ValueError(f"orders must be [{B}, n_max, n_max] with n_max in [1, {_lib.MOL_MAX_ATOMS}], got {tuple(orders.shape)}")
+    table = torch.as_tensor(class_table(decoder), device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    rc = lib.dsbdd_vina_torsions(stream, orders.data_ptr(), _ptr(at), off.data_ptr(), B, len(decoder), table.data_ptr(),
+                                 int(orders.shape[1]), out.ints.data_ptr(), out.ends.data_ptr(), out.sides.data_ptr(),
+                                 _ptr(out.pair_mask))
+    _lib.check(rc, "dsbdd_vina_torsions")
+    return out
+
+
+@dataclass
+class MolVinaIntra:
+    """The intramolecular record of one molecule (host arrays)."""
+    mol: np.ndarray          # float32 [8]: the five term sums (every pair once), intra, 0, 0
+    atom: np.ndarray         # float32 [n, 5]: the unweighted terms of every atom over its partners
+    grad: np.ndarray         # float32 [n, 3]: d intra / d x_i, kcal/mol/A
+    n_torsions: int = 0      # rotors kept
+    torsions_found: int = 0
+    nonfinite: int = 0
+
+    terms = property(lambda self: self.mol[:ATOM_OUT])
+    intra = property(lambda self: float(self.mol[M_INTER]))
+
+
+@dataclass
+class VinaIntra:
+    """The outputs of `dsbdd_vina_intra` (device tensors from `vina_intra`, numpy arrays from `_vina_intra_host`)."""
+    atom: object             # float [N, 5]
+    mol: object              # float [B, 8]: the five sums with every pair counted once, intra, 0, 0
+    flag: object             # int32 [B]
+    grad: object             # float [N, 3]: d intra / d x_i
+    mol_off: object          # int32 [B + 1]
+    torsions: object = None  # VinaTorsions (`vina_intra` only)
+
+    terms = property(lambda self: self.mol[:, :ATOM_OUT])
+    intra = property(lambda self: self.mol[:, M_INTER])
+    nonfinite = property(lambda self: self.flag)
+
+    def molecules(self):
+        """One `MolVinaIntra` per molecule, in order (one copy of each tensor to the host)."""
+        atom, mol, flag, grad, off = (_np(v) for v in (self.atom, self.mol, self.flag, self.grad, self.mol_off))
+        ints = np.zeros((len(mol), TOR_INT), np.int32) if self.torsions is None else _np(self.torsions.ints)
+        return [MolVinaIntra(mol[b].copy(), atom[off[b]:off[b + 1]].copy(), grad[off[b]:off[b + 1]].copy(), int(ints[b, T_KEPT]),
+                             int(ints[b, T_FOUND]), int(flag[b])) for b in range(len(mol))]
+
+
+def _intra_as_groups(lig_x, lig_code, mol_off):
+    """The arguments of `_vina_score_host` that make every molecule its own pocket group."""
+    off = np.asarray(_np(mol_off), np.int64).reshape(-1)
+    B = len(off) - 1
+    return (lig_x, lig_code, off, np.arange(B), np.zeros((B, MOL_INT), np.int32), lig_x, lig_code, off)
+
+
+def _vina_intra_host(lig_x, lig_code, mol_off, pair_mask, dtype=np.float64, eps=None):
+    """`dsbdd_vina_intra` in numpy: `_vina_grad_host` with every molecule as its own pocket group, over the pairs listed in
+    `pair_mask` (int32 [N, 4]) alone; float32 coordinates, the counted pairs decided by the float32 distance, everything
+    else in `dtype` (float64: the specification).  Per molecule the five sums are HALF the sums over the atoms (every
+    pair is met from both ends), intra = sum_k WEIGHTS[k] T_k, columns 6 and 7 are 0.  -> (VinaIntra of arrays in `dtype`,
+    the smallest |r - 8| over the listed pairs).  With `eps` also the bounds of `intra_error_bound`: (..., atom_bound
+    [N, 5], mol_bound [B, 6], grad_bound [N, 3])."""
+    mask = np.asarray(_np(pair_mask), np.int32).reshape(-1, MASK_WORDS)
+    args = _intra_as_groups(lig_x, lig_code, mol_off)
+    if eps is None:
+        g = _vina_grad_host(*args, dtype=dtype, pair_mask=mask)
+        _, margin = _vina_score_host(*args, dtype=dtype, pair_mask=mask)
+    else:
+        g, grad_bound, _ = _vina_grad_host(*args, dtype=dtype, eps=eps, pair_mask=mask)
+        _, margin, atom_bound, mol_bound = _vina_score_host(*args, dtype=dtype, eps=eps, pair_mask=mask)
+    mol = g.mol.copy()
+    mol[:, :ATOM_OUT] *= dtype(0.5)
+    mol[:, M_INTER] = (mol[:, :ATOM_OUT] * np.asarray(WEIGHTS, dtype)).sum(1)
+    mol[:, M_SCORE:] = np.where(np.isnan(mol[:, M_INTER:M_INTER + 1]), dtype(np.nan), dtype(0))
+    out = VinaIntra(g.atom, mol, g.flag, g.grad, g.mol_off)
+    if eps is None:
+        return out, margin
+    half = 0.5 * mol_bound[:, :M_INTER + 1] + eps * np.abs(mol[:, :M_INTER + 1].astype(np.float64))
+    return out, margin, atom_bound, half, grad_bound
+
+
+def intra_error_bound(lig_x, lig_code, mol_off, pair_mask, eps=EPS32):
+    """Forward error bound of a float32 evaluation of the intramolecular term (and so of the kernel, which rounds less: float64
+    from the float32 r on) against `_vina_intra_host` in float64.  The pairs are ligand-ligand, the arithmetic per pair is
+    that of `dsbdd_vina_score_grad` with the partner's float32 coordinates and code in the pocket atom's place, so the
+    derivations of `error_bound` (terms) and `grad_error_bound` (gradient) hold pair for pair: per atom they are taken
+    over as they stand, the sums running over the atom's listed partners.  Per molecule the value is half the sum over all
+    ordered pairs: half the bound of that sum (the halving is exact), plus eps |value| for the one rounding of the stored
+    float32 that the halved value gets on its own; intra: sum_k |w_k| bound_k, halved the same way, plus eps |intra|.
+    -> (atom_bound [N, 5], mol_bound [B, 6], grad_bound [N, 3]); NaN where the molecule is not finite."""
+    return _vina_intra_host(lig_x, lig_code, mol_off, pair_mask, eps=float(eps))[2:]
+
+
+def vina_intra(x, atom_type, lig_mask, info, batch=None, orders=None):
+    """The intramolecular term of a batch and its gradient with respect to x, on device tensors: bond orders (unless
+    given), `dsbdd_vina_type`, `dsbdd_vina_torsions`, `dsbdd_vina_intra`; no read-back inside.  Arguments as for
+    `type_ligands`.  -> VinaIntra of device tensors, with the tree as `.torsions`.  A molecule without rotors (or longer
+    than 128 atoms) has no pair and gives exact zeros.  See `VINA_INTRA_COVERAGE`."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise _lib.HipLibraryError("vina_intra needs device tensors (HIP path; no CPU fallback)")
+    lib = _lib.load()
+    dev = x.device
+    x = x.detach().to(torch.float32).reshape(-1, 3).contiguous()
+    N = int(x.shape[0])
+    lig_mask = torch.as_tensor(lig_mask, device=dev).reshape(-1)
+    B = _n_molecules(lig_mask, batch)
+    if orders is None and B:
+        orders = perceive_orders(x, atom_type, lig_mask, info, batch=B)
+    code, _, off = type_ligands(x, atom_type, lig_mask, info, orders=orders, batch=B)
+    tree = ligand_torsions(x, atom_type, lig_mask, info, orders=orders, batch=B)
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = VinaIntra(torch.zeros((N, ATOM_OUT), **f32), torch.zeros((B, MOL_OUT), **f32),
+                    torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros((N, ATOM_GRAD), **f32), off, tree)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    rc = lib.dsbdd_vina_intra(stream, _ptr(x), _ptr(code), off.data_ptr(), B, _ptr(tree.pair_mask), _ptr(out.atom),
+                              _ptr(out.mol), _ptr(out.flag), _ptr(out.grad))
+    _lib.check(rc, "dsbdd_vina_intra")
+    return out
+
+
+def intra_molecules(molecules, info="crossdock", device="cuda", bonds="distance"):
+    """Intramolecular records of written molecules (`as_ligands` forms) through the launches of `vina_intra`; `info`,
+    `device` and `bonds` as for `score_molecules`.  -> list of `MolVinaIntra`."""
+    def entry(x, at, mask, pockets, info, mol_group, batch=None, orders=None):
+        return vina_intra(x, at, mask, info, batch=batch, orders=orders)
+    return _molecule_records(entry, "intra_molecules", molecules, None, info, None, device, bonds)
+
+
+# ---- the flexible minimiser ---------------------------------------------------------------------------------------------------
+@dataclass
+class MolVinaFlex(MolVinaMin):
+    """`MolVinaMin` at the pose the flexible minimiser returned (host arrays): `inter`, `score` and the gradient stay the
+    intermolecular ones, the intramolecular term is reported beside them.  `energies` float [8]: inter at the start, at the
+    end, the last accepted step, u at the end, intra at the start, at the end, E = inter + intra at the start, at the end."""
+    intra_rec: MolVinaIntra = None    # the intramolecular record at the returned pose
+    theta: np.ndarray = None          # float32 [32]: the torsion angles (rad) in the slots of the tree; 0 where no rotor stands
+    tau: np.ndarray = None            # float32 [32]: d E / d theta_k at the returned pose
+
+    intra = property(lambda self: self.intra_rec.intra)
+    intra_start = property(lambda self: float(self.energies[X_INTRA_START]))
+    n_torsions = property(lambda self: self.intra_rec.n_torsions)
+    torsions_found = property(lambda self: self.intra_rec.torsions_found)
+
+    def as_dict(self):
+        out = super().as_dict()
+        out.update(intra=self.intra, intra_start=self.intra_start, n_torsions=self.n_torsions, torsions_found=self.torsions_found)
+        return out
+
+
+@dataclass
+class VinaFlexed(VinaMinimized):
+    """`VinaMinimized` at the poses the flexible minimiser returned (device tensors from `vina_minimize(torsions=True)`,
+    numpy arrays from `_vina_flex_host`); `energies` is [B, 8] (see `MolVinaFlex`)."""
+    intra_out: object = None  # VinaIntra at the returned poses, with the tree as `.torsions`
+    theta: object = None      # float [B, 32]
+    tau: object = None        # float [B, 32]
+
+    intra = property(lambda self: self.intra_out.intra)
+    intra_start = property(lambda self: self.energies[:, X_INTRA_START])
+    n_torsions = property(lambda self: self.intra_out.torsions.kept)
+    torsions_found = property(lambda self: self.intra_out.torsions.found)
+
+    def molecules(self):
+        """One `MolVinaFlex` per molecule, in order (one copy of each tensor to the host)."""
+        theta, tau = _np(self.theta), _np(self.tau)
+        return [MolVinaFlex(m.mol, m.ints, m.atom, m.code, m.nonfinite, m.grad, m.mol_grad, m.x, m.pose, m.energies, m.stat,
+                            m.rmsd, r, theta[b].copy(), tau[b].copy())
+                for b, (m, r) in enumerate(zip(VinaMinimized.molecules(self), self.intra_out.molecules()))]
+
+
+def valid_torsions(tree, b, n, dofs=DOF_RIGID | DOF_TORSIONS):
+    """The rotors of molecule b (n atoms) of a `VinaTorsions` of arrays that `dsbdd_vina_flex` turns, as it checks them: none
+    without the torsion bit of `dofs` or with n > 128; the kept count clamped to [0, 32]; a rotor whose ends are not two
+    different atoms of the molecule dropped; side bits at or above n cleared.  -> list of (p, m, side bool [n], slot)."""
+    if not (dofs & DOF_TORSIONS) or n > _lib.MOL_MAX_ATOMS:
+        return []
+    kept = min(max(int(_np(tree.ints)[b, T_KEPT]), 0), MAX_TORSIONS)
+    ends, sides = _np(tree.ends)[b], _np(tree.sides)[b]
+    out = []
+    for k in range(kept):
+        p, m = int(ends[k, 0]), int(ends[k, 1])
+        if 0 <= p < n and 0 <= m < n and p != m:
+            out.append((p, m, unpack_masks(sides[k:k + 1], n)[0], k))
+    return out
+
+
+def _torsion_frame(x0, torsions, theta):
+    """y float64 [n, 3]: the input with every side turned, in list order, by the formula the kernel uses."""
+    y = np.asarray(x0, np.float32).reshape(-1, 3).astype(np.float64)
+    for rotor, angle in zip(torsions, theta):
+        p, m, side = rotor[:3]
+        angle = float(angle)
+        o = y[m].copy()
+        ax = o - y[p]
+        length = float(np.sqrt((ax[0] * ax[0] + ax[1] * ax[1]) + ax[2] * ax[2]))
+        if angle == 0.0 or not length > 0.0:
+            continue
+        ax = ax / length
+        cs, sn = np.cos(angle), np.sin(angle)
+        v = y[side] - o
+        along = ((ax[0] * v[:, 0] + ax[1] * v[:, 1]) + ax[2] * v[:, 2]) * (1.0 - cs)
+        cr = np.stack([ax[(k + 1) % 3] * v[:, (k + 2) % 3] - ax[(k + 2) % 3] * v[:, (k + 1) % 3] for k in range(3)], 1)
+        y[side] = o + ((v * cs + cr * sn) + ax[None, :] * along[:, None])
+    return y
+
+
+def torsion_coordinates(x0, torsions, theta, shift=(0.0, 0.0, 0.0), q=(1.0, 0.0, 0.0, 0.0)):
+    """float32(t + R(q) y) of the float32 input coordinates x0 [n, 3]: y = x0 in float64, then for every rotor of `torsions`
+    ((p, m, side bool [n], ...) tuples) in list order the atoms of its side turn by its `theta` about the line from y[p]
+    through y[m] as it stands (a rotor with theta = 0 or coinciding ends is skipped); rounded once.  The sides being nested
+    or disjoint, the result does not depend on the list order beyond the float64 roundings."""
+    y = _torsion_frame(x0, torsions, theta)
+    R, t = pose_frame(q), np.asarray(shift, np.float64)
+    return np.stack([t[k] + ((R[k, 0] * y[:, 0] + R[k, 1] * y[:, 1]) + R[k, 2] * y[:, 2]) for k in range(3)], 1).astype(np.float32)
+
+
+def flex_geometry(x, torsions, grad):
+    """The scales and torques of an accepted pose: x float32 [n, 3] its coordinates, `grad` [n, 3] = g^inter + g^intra.
+    -> (c [3], rho2, rho_max, tau [K], reach [K], rho2k [K]) in float64: c the mean of x, rho^2 = max(mean |x - c|^2, 1),
+    rho_max = max |x - c|; per rotor a = the unit vector from x[p] to x[m], tau = a . sum_{i in S} (x_i - x[m]) x grad_i,
+    reach = the largest distance of an atom of S from the axis, rho2k = max(mean over S of that distance squared, 1); a
+    rotor whose ends coincide has tau = reach = 0."""
+    x = np.asarray(x, np.float32).reshape(-1, 3).astype(np.float64)
+    g = np.asarray(grad, np.float64).reshape(-1, 3)
+    n, K = len(x), len(torsions)
+    c = x.sum(0) / n if n else np.zeros(3)
+    s2 = ((x - c) ** 2).sum(1)
+    rho2 = max(float(s2.sum() / n), 1.0) if n else 1.0
+    rho_max = float(np.sqrt(s2.max())) if n else 0.0
+    tau, reach, rho2k = np.zeros(K), np.zeros(K), np.ones(K)
+    for k, rotor in enumerate(torsions):
+        p, m, side = rotor[:3]
+        ax = x[m] - x[p]
+        length = _norm3(ax)
+        if not length > 0.0 or not side.any():
+            continue
+        ax = ax / length
+        v = x[side] - x[m]
+        tau[k] = float((np.cross(v, g[side]) @ ax).sum())
+        d2 = (np.cross(v, ax) ** 2).sum(1)
+        reach[k], rho2k[k] = float(np.sqrt(d2.max())), max(float(d2.sum() / len(d2)), 1.0)
+    return c, rho2, rho_max, tau, reach, rho2k
+
+
+def flex_slope(F, M, rho2, rho_max, tau, reach, rho2k, dofs=DOF_RIGID | DOF_TORSIONS):
+    """u = |F| + rho_max |M| / rho^2 + sum_k reach_k |tau_k| / rho2k_k, a switched-off block left out."""
+    u = _norm3(F) + rho_max * _norm3(M) / rho2 if dofs & DOF_RIGID else 0.0
+    for k in range(len(tau)):
+        u += reach[k] * abs(tau[k]) / rho2k[k]
+    return u
+
+
+def flex_step(shift, q, theta, F, M, tau, c, rho2, rho2k, alpha, dofs=DOF_RIGID | DOF_TORSIONS):
+    """The trial of one step from the accepted pose (t, q, theta) whose coordinates have the mean c: with the rigid bit of
+    `dofs` the rotation dq by -alpha M / rho^2 about c and the translation -alpha F, q' = normalise(dq q), t' = c + R(dq)(t - c)
+    - alpha F (else t, q as they are); theta' = theta - alpha tau / rho2k (`tau` holds only the rotors that turn).  float64.
+    -> (t', q', theta')."""
+    shift, q = np.asarray(shift, np.float64), np.asarray(q, np.float64)
+    theta = np.asarray(theta, np.float64) - (alpha * np.asarray(tau, np.float64)) / np.asarray(rho2k, np.float64)
+    if not dofs & DOF_RIGID:
+        return shift.copy(), q.copy(), theta
+    th = -(alpha * np.asarray(M, np.float64)) / rho2
+    angle = float(np.sqrt((th[0] * th[0] + th[1] * th[1]) + th[2] * th[2]))
+    dq = np.asarray([1.0, 0.0, 0.0, 0.0])
+    if angle > 0.0:
+        dq = np.concatenate([[np.cos(0.5 * angle)], (np.sin(0.5 * angle) / angle) * th])
+    _, q1 = pose_step(np.zeros(3), q, np.zeros(3), M, rho2, alpha)
+    R, s, c = pose_frame(dq), shift - np.asarray(c, np.float64), np.asarray(c, np.float64)
+    t1 = np.asarray([(c[k] + ((R[k, 0] * s[0] + R[k, 1] * s[1]) + R[k, 2] * s[2])) - alpha * float(F[k]) for k in range(3)])
+    return t1, q1, theta
+
+
+def _flex_one(evaluate, x0, torsions, step, tol, max_evals, dofs):
+    """The iteration on one molecule.  `evaluate(x float32 [n, 3])` -> (inter float32, intra float32, F [3], M [3], g [n, 3],
+    record): the two energies as stored, the net gradient and its moment about the centroid rounded to float32, the sum of
+    the two float32 gradients.  -> (x, pose [8], energies [8], stat [4], theta [K], tau [K], record of the returned pose)."""
+    x0 = np.asarray(x0, np.float32).reshape(-1, 3)
+    K = len(torsions)
+    shift, q, theta = np.zeros(3), np.asarray([1.0, 0.0, 0.0, 0.0]), np.zeros(K)
+    x = torsion_coordinates(x0, torsions, theta, shift, q)
+    inter, intra, F, M, g, kept = evaluate(x)
+    E = float(inter) + float(intra)
+    evals, accepted, E_start, L, last_L, rejected = 1, 0, E, step, 0.0, False
+    inter_start, intra_start = inter, intra
+    while True:
+        c, rho2, rho_max, tau, reach, rho2k = flex_geometry(x, torsions, g)
+        u = flex_slope(F, M, rho2, rho_max, tau, reach, rho2k, dofs)
+        if not u > 0.0:
+            status = 2
+            break
+        moved = False
+        while True:
+            if L < tol:
+                status = 1
+                break
+            if evals >= max_evals:
+                status = 0
+                break
+            trial = flex_step(shift, q, theta, F, M, tau, c, rho2, rho2k, L / u, dofs)
+            xt = torsion_coordinates(x0, torsions, trial[2], trial[0], trial[1])
+            it, at, Ft, Mt, gt, rec = evaluate(xt)
+            evals += 1
+            if float(it) + float(at) < E:
+                (shift, q, theta), x, E, F, M, g, kept = trial, xt, float(it) + float(at), Ft, Mt, gt, rec
+                last_L, L, accepted, rejected, moved = L, min(2.0 * L, step), accepted + 1, False, True
+                break
+            L, rejected = 0.5 * L, True
+        if not moved:
+            break
+    if rejected:
+        kept = evaluate(x)[5]
+        evals += 1
+    pose = np.concatenate([shift, q, [rho2]])
+    inter_final, intra_final = float(np.float32(kept[0].mol[0, M_INTER])), float(np.float32(kept[1].mol[0, M_INTER]))
+    energies = np.asarray([inter_start, inter_final, last_L, u, intra_start, intra_final, E_start, E], np.float64)
+    return x, pose, energies, np.asarray([status, evals, accepted, 0], np.int32), theta, tau, kept
+
+
+def _vina_flex_host(lig_x, lig_code, mol_off, mol_group, mol_int, poc_x, poc_code, group_off, tree, dofs=DOF_RIGID | DOF_TORSIONS,
+                    step=MIN_STEP, tol=MIN_TOL, max_evals=MIN_EVALS, trace=None):
+    """`dsbdd_vina_flex` in numpy, the specification of its iteration: the arguments of `_vina_minimize_host`, `tree` a
+    `VinaTorsions` of arrays (what `_vina_torsions_host` returns), `dofs` bit 0 = the rigid body, bit 1 = the torsions.  Per
+    molecule, with the rotors `valid_torsions` keeps and the pose (t, q, theta) from (0, identity, 0), all float64:
+    an evaluation is `_vina_grad_host` and `_vina_intra_host` in float64 on the float32-rounded coordinates
+    `torsion_coordinates(x0, rotors, theta, t, q)`; inter, intra, F = net, M = moment and the two gradients are rounded to
+    float32 before any use, and E = inter + intra is their float64 sum:
+      1. evaluate the input pose; E_start = E, L = step
+      2. at the accepted pose `flex_geometry`, u = `flex_slope`; unless u > 0 stop, status 2
+      3. L < tol: stop, status 1; max_evals evaluations made: stop, status 0; else the trial `flex_step` with alpha = L / u
+         (no atom moves more than L); evaluate; E' < E (strict): take it, L = min(2 L, step), go to 2; else L = L / 2, repeat 3
+      4. after a stop on a rejected trial the accepted pose is evaluated once more (counted; the only evaluation beyond
+         max_evals)
+    A molecule with a coordinate that is not finite: status 3, x the input, NaN in its other floats, both flags.
+    -> VinaFlexed of arrays: the fields of `_vina_minimize_host`, energies [B, 8], `intra_out` (a VinaIntra in float64 with
+    the tree), theta and tau [B, 32] in the slots of the tree.  `trace`: a list that receives (molecule, E) per evaluation."""
+    step, tol, max_evals = _settings(step, tol, max_evals)
+    if dofs not in (1, 2, 3):
+        raise ValueError("dofs must be 1, 2 or 3")
+    x_in = np.asarray(_np(lig_x), np.float32).reshape(-1, 3)
+    code = np.asarray(_np(lig_code), np.int32).reshape(-1)
+    q_all = np.asarray(_np(poc_x), np.float32).reshape(-1, 3)
+    qcode = np.asarray(_np(poc_code), np.int32).reshape(-1)
+    off = np.asarray(_np(mol_off), np.int64).reshape(-1)
+    goff = np.asarray(_np(group_off), np.int64).reshape(-1)
+    ints = np.asarray(_np(mol_int), np.int32).reshape(-1, MOL_INT)
+    groups = np.asarray(_np(mol_group), np.int64).reshape(-1)
+    pair_mask = np.asarray(_np(tree.pair_mask), np.int32).reshape(-1, MASK_WORDS)
+    B, G, N = len(off) - 1, len(goff) - 1, len(x_in)
+    if len(code) != N or len(qcode) != len(q_all) or len(groups) != B or len(ints) != B or len(pair_mask) != N:
+        raise ValueError("one code and one pair mask per atom, one group and one mol_int row per molecule")
+    intra = VinaIntra(np.zeros((N, ATOM_OUT)), np.zeros((B, MOL_OUT)), np.zeros(B, np.int32), np.zeros((N, ATOM_GRAD)),
+                      off.astype(np.int32), tree)
+    out = VinaFlexed(np.zeros((N, ATOM_OUT)), np.zeros((B, MOL_OUT)), ints, np.zeros(B, np.int32), code, off.astype(np.int32),
+                     np.zeros((N, ATOM_GRAD)), np.zeros((B, MOL_GRAD)), float("inf"), x_in.copy(), np.zeros((B, MOL_POSE)),
+                     np.zeros((B, MOL_FLEX)), np.zeros((B, MOL_STAT), np.int32), x_in, intra, np.zeros((B, MAX_TORSIONS)),
+                     np.zeros((B, MAX_TORSIONS)))
+    for b in range(B):
+        lo, hi = int(off[b]), int(off[b + 1])
+        if not (lo >= 0 and hi >= lo and hi <= off[B]):
+            lo = hi = 0
+        g = int(groups[b])
+        glo, ghi = (int(goff[g]), int(goff[g + 1])) if 0 <= g < G else (0, 0)
+        if not (glo >= 0 and ghi >= glo and ghi <= goff[G]):
+            glo = ghi = 0
+        x0, c, one = x_in[lo:hi], code[lo:hi], np.asarray([0, hi - lo], np.int64)
+        qg, qc, pm = q_all[glo:ghi], qcode[glo:ghi], pair_mask[lo:hi]
+        rotors = valid_torsions(tree, b, hi - lo, dofs)
+
+        def evaluate(x):
+            near = np.ones(len(qg), bool)
+            if len(x) and len(qg) and np.isfinite(x).all():
+                low, high = x.astype(np.float64).min(0) - (CUTOFF + 0.5), x.astype(np.float64).max(0) + (CUTOFF + 0.5)
+                near = ((qg >= low) & (qg <= high)).all(1)
+            st = _vina_grad_host(x, c, one, [0], ints[b:b + 1], qg[near], qc[near], [0, int(near.sum())])
+            si, _ = _vina_intra_host(x, c, one, pm)
+            inter, intra_e = np.float32(st.mol[0, M_INTER]), np.float32(si.mol[0, M_INTER])
+            if trace is not None:
+                trace.append((b, float(inter) + float(intra_e)))
+            r32 = lambda v: np.asarray(v).astype(np.float32).astype(np.float64)
+            return inter, intra_e, r32(st.mol_grad[0, G_NET]), r32(st.mol_grad[0, G_MOMENT]), r32(st.grad) + r32(si.grad), (st, si)
+
+        if not np.isfinite(x0).all():
+            st, si = evaluate(x0)[5]
+            pose, energies, stat = np.full(MOL_POSE, np.nan), np.full(MOL_FLEX, np.nan), np.asarray([3, 0, 0, 0], np.int32)
+            out.theta[b], out.tau[b] = np.nan, np.nan
+        else:
+            x, pose, energies, stat, theta, tau, (st, si) = _flex_one(evaluate, x0, rotors, step, tol, max_evals, dofs)
+            out.x[lo:hi] = x
+            for k, rotor in enumerate(rotors):
+                out.theta[b, rotor[3]], out.tau[b, rotor[3]] = theta[k], tau[k]
+        out.atom[lo:hi], out.grad[lo:hi] = st.atom, st.grad
+        out.mol[b], out.flag[b], out.mol_grad[b] = st.mol[0], st.flag[0], st.mol_grad[0]
+        intra.atom[lo:hi], intra.grad[lo:hi], intra.mol[b], intra.flag[b] = si.atom, si.grad, si.mol[0], si.flag[0]
+        out.pose[b], out.energies[b], out.stat[b] = pose, energies, stat
+    return out
+
+
+def _flexed(x, atom_type, lig_mask, pockets, info, mol_group, batch, orders, settings, dofs):
+    """The launches behind `vina_minimize(torsions=True)`: bond orders (unless given), `dsbdd_vina_type`,
+    `dsbdd_vina_torsions`, then `dsbdd_vina_flex`."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise _lib.HipLibraryError("vina_minimize needs device tensors (HIP path; no CPU fallback)")
+    if dofs not in (1, 2, 3):
+        raise ValueError("dofs must be 1 (rigid body), 2 (torsions) or 3 (both)")
+    lib = _lib.load()
+    dev = x.device
+    if not isinstance(pockets, VinaPocket):
+        pockets = VinaPocket.upload(pockets, dev)
+    x = x.detach().to(torch.float32).reshape(-1, 3).contiguous()
+    N = int(x.shape[0])
+    lig_mask = torch.as_tensor(lig_mask, device=dev).reshape(-1)
+    B = _n_molecules(lig_mask, batch)
+    G = pockets.n_groups
+    groups = _pairs.device_groups(mol_group, B, G, dev)
+    if orders is None and B:
+        orders = perceive_orders(x, atom_type, lig_mask, info, batch=B)
+    code, mol_int, off = type_ligands(x, atom_type, lig_mask, info, orders=orders, batch=B)
+    tree = ligand_torsions(x, atom_type, lig_mask, info, orders=orders, batch=B)
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+    intra = VinaIntra(torch.zeros((N, ATOM_OUT), **f32), torch.zeros((B, MOL_OUT), **f32), torch.zeros(B, **i32),
+                      torch.zeros((N, ATOM_GRAD), **f32), off, tree)
+    out = VinaFlexed(torch.zeros((N, ATOM_OUT), **f32), torch.zeros((B, MOL_OUT), **f32), mol_int, torch.zeros(B, **i32), code, off,
+                     torch.zeros((N, ATOM_GRAD), **f32), torch.zeros((B, MOL_GRAD), **f32), float("inf"), x.clone(),
+                     torch.zeros((B, MOL_POSE), **f32), torch.zeros((B, MOL_FLEX), **f32), torch.zeros((B, MOL_STAT), **i32), x,
+                     intra, torch.zeros((B, MAX_TORSIONS), **f32), torch.zeros((B, MAX_TORSIONS), **f32))
+    step, tol, max_evals = settings
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    # without atoms both pointers are stand-ins (`_ptr`); held here together, so that they are two addresses
+    x_arg, x_out_arg = (x, out.x) if N else (torch.zeros(4, **f32), torch.zeros(4, **f32))
+    rc = lib.dsbdd_vina_flex(stream, x_arg.data_ptr(), _ptr(code), off.data_ptr(), B, _ptr(groups), _ptr(mol_int), _ptr(pockets.x),
+                             _ptr(pockets.code), pockets.group_off.data_ptr(), G, _ptr(tree.ints), _ptr(tree.ends),
+                             _ptr(tree.sides), _ptr(tree.pair_mask), int(dofs), float(step), float(tol), int(max_evals),
+                             _ptr(out.atom), _ptr(out.mol), _ptr(out.flag), _ptr(out.grad), _ptr(out.mol_grad), _ptr(intra.atom),
+                             _ptr(intra.mol), _ptr(intra.flag), _ptr(intra.grad), x_out_arg.data_ptr(), _ptr(out.pose),
+                             _ptr(out.energies), _ptr(out.stat), _ptr(out.theta), _ptr(out.tau))
+    _lib.check(rc, "dsbdd_vina_flex")
+    return out
+
+
 # ---- command line ----------------------------------------------------------------------------------------------------------
 CSV_COLUMNS = ("n_atoms", "untyped", "n_rot", "nonfinite") + TERMS + ("inter", "score")
 MIN_CSV_COLUMNS = CSV_COLUMNS + ("inter_start", "score_start", "status", "evals", "rmsd")      # with --minimize
+FLEX_CSV_COLUMNS = MIN_CSV_COLUMNS + ("intra", "intra_start", "n_torsions")                    # with --minimize --torsions
 
 
 def write_csv(path, rows, columns=CSV_COLUMNS):
@@ -1317,6 +1954,9 @@ def parse_args(argv=None):
                    help="relax every pose as a rigid body under `inter` on the device first (rigid ligand, rigid protein, a "
                         "local search; not smina or qvina output): the relaxed molecules go to this file, the rows of --out "
                         "(and of --grad_out) describe them and gain the columns inter_start, score_start, status, evals, rmsd")
+    p.add_argument("--torsions", action="store_true",
+                   help="--minimize: turn the rotatable bonds as well, under inter + intra (a local search, not smina or qvina "
+                        "output); the rows gain the columns intra, intra_start, n_torsions")
     p.add_argument("--step", type=float, default=MIN_STEP, help="--minimize: the first and largest step, A")
     p.add_argument("--tol", type=float, default=MIN_TOL, help="--minimize: stop when the step falls below this, A")
     p.add_argument("--max_evals", type=int, default=MIN_EVALS, help=f"--minimize: evaluation budget per molecule (1 ... {MAX_EVALS})")
@@ -1333,16 +1973,18 @@ def main(argv=None):
     if a.grad_out is not None:
         print(VINA_GRAD_COVERAGE, file=sys.stderr)
         records_of = gradient_molecules
+    if a.torsions and a.minimize is None:
+        raise SystemExit("--torsions needs --minimize OUT.sdf")
     if a.minimize is not None:
-        print(VINA_MIN_COVERAGE, file=sys.stderr)
+        print(VINA_FLEX_COVERAGE if a.torsions else VINA_MIN_COVERAGE, file=sys.stderr)
         step, tol, max_evals = _settings(a.step, a.tol, a.max_evals)
 
         def records_of(path, *args, **kwargs):
-            return minimize_molecules(path, *args, step=step, tol=tol, max_evals=max_evals, **kwargs)
+            return minimize_molecules(path, *args, step=step, tol=tol, max_evals=max_evals, torsions=a.torsions, **kwargs)
     rows = []
     for path in a.sdf:
         rows += [(path, k, rec) for k, rec in enumerate(records_of(path, pockets, a.dataset, bonds=a.bonds))]
-    write_csv(a.out, rows, CSV_COLUMNS if a.minimize is None else MIN_CSV_COLUMNS)
+    write_csv(a.out, rows, CSV_COLUMNS if a.minimize is None else FLEX_CSV_COLUMNS if a.torsions else MIN_CSV_COLUMNS)
     if a.grad_out is not None:
         write_grad_csv(a.grad_out, rows)
     if a.minimize is not None:

@@ -959,6 +959,81 @@ int dsbdd_vina_minimize(void* stream, const float* lig_x, const int32_t* lig_cod
                         float* atom_grad, float* mol_grad, float step, float tol, int32_t max_evals, float* x_out,
                         float* mol_pose, float* mol_min, int32_t* mol_stat);
 
+/* Torsion tree and intramolecular term of such a batch (csrc/vina_torsion.h, csrc/vina_intra.h): these two launches list
+ * the rotatable bonds with their moving sides and evaluate the ligand-ligand term and its gradient at the pose given;
+ * nothing is moved.  dsbdd_vina_flex (below) relaxes a pose over them.
+ *
+ * dsbdd_vina_torsions: one wave per molecule, integers only; order / atom_type / mol_off / n_types / class_elem / n_max
+ * exactly as for dsbdd_vina_type.  A rotor is what N_rot counts: a bond (a, c), c < a, of order 1, both ends of heavy
+ * degree >= 2, in no ring.  Rotors are enumerated in ascending (a, c); the first 32 are kept.
+ * tor_int [batch][4] = rotors kept, rotors found (= mol_int[2] of dsbdd_vina_type on the same input), 0, 0; a molecule
+ * longer than n_max keeps none (found is still counted on its first n_max atoms).
+ * Moving side S_k of kept rotor k: of the two components its ends fall into when the bond is cut, the one with fewer atoms,
+ * on a tie the one of the higher-index end.  tor_end [batch][32][2] = fixed end p_k, moving end m_k (m_k in S_k; atom
+ * indices inside the molecule), -1 past the kept; tor_side [batch][32][4] = S_k as a 128-bit mask in four int32 words (atom
+ * 32 w + b is bit b of word w), 0 past the kept.  Any two S_k are nested or disjoint: two sides of at most half a
+ * component each cannot overlap without one containing the other.
+ * pair_mask [N][4]: for atom i of its molecule the 128-bit mask of the atoms j of the same molecule with i != j, both typed
+ * (class_elem of their type), more than 3 bonds apart or not connected, and exactly one of i, j in S_k for some kept k.
+ * Symmetric; all zero for a molecule without kept rotors and for the atoms past n_max.  A molecule whose offsets fail the
+ * range check is read as empty: zeros in tor_int, no row of pair_mask written.
+ *
+ * dsbdd_vina_intra: one workgroup per molecule, the sweep of dsbdd_vina_score_grad with the molecule's own atoms in place
+ * of the pocket group, over the pairs set in pair_mask (what dsbdd_vina_torsions wrote; a bit at or above the molecule's
+ * size is ignored).  The same float32 distance and strict cutoff r < 8, the same five terms, weights, radii and flags from
+ * lig_code on both sides, the same one-sided derivatives; a pair with r == 0 adds to the terms and zero to the gradient.
+ * atom_out [N][5]: the unweighted sums of the five terms over the atom's partners.  atom_grad [N][3]: g_i = sum_j (sum_k w_k
+ * T_k'(d_ij)) u_ij = d intra / d x_i in kcal/mol/A.  mol_out [batch][8]: the five sums with every pair counted once (half
+ * the sum over the atoms), intra = sum_k w_k T_k (no division by rotors), 0, 0.  mol_flag [batch]: 1 when a coordinate is
+ * NaN or +-inf; every float the molecule owns in atom_out, mol_out and atom_grad is then NaN.  A molecule without kept rotors
+ * gives exact zeros.  Sums in float64 in a fixed order, stored as float32; no atomics, bitwise reproducible, independent of
+ * the rest of the batch; offsets range-checked as everywhere.  batch = 0 launches nothing; null pointers, negative counts
+ * and an n_max outside [1, DSBDD_MOL_MAX_ATOMS] are DSBDD_ERR_ARG. */
+int dsbdd_vina_torsions(void* stream, const int8_t* order, const int32_t* atom_type, const int32_t* mol_off, int64_t batch,
+                        int32_t n_types, const int32_t* class_elem, int32_t n_max, int32_t* tor_int, int32_t* tor_end,
+                        int32_t* tor_side, int32_t* pair_mask);
+int dsbdd_vina_intra(void* stream, const float* lig_x, const int32_t* lig_code, const int32_t* mol_off, int64_t batch,
+                     const int32_t* pair_mask, float* atom_out, float* mol_out, int32_t* mol_flag, float* atom_grad);
+
+/* Flexible minimisation of every pose of such a batch under E = inter + intra, one launch (csrc/vina_flex.h) after
+ * dsbdd_vina_type and dsbdd_vina_torsions: dsbdd_vina_minimize with the kept rotors as further degrees of freedom and the
+ * term of dsbdd_vina_intra in the objective.  NOT smina or qvina output: steepest descent with backtracking and not BFGS, a
+ * local search from one start, a rigid protein, heavy atoms only, typing and the torsion tree fixed on the input pose, amide
+ * and conjugated bonds rotate, at most 32 rotors.  Every input, convention and check of dsbdd_vina_minimize; tor_int, tor_end,
+ * tor_side and pair_mask what dsbdd_vina_torsions wrote.  They are range-checked on the device: the kept count is clamped
+ * to [0, 32], a rotor whose ends are not two different atoms of the molecule is DROPPED (the molecule relaxes with the
+ * others), side and pair bits at or above the molecule's size are ignored, a molecule longer than 128 atoms has no rotor.
+ * dofs: bit 0 = the rigid body, bit 1 = the torsions (1, 2 or 3); a switched-off block is never stepped.
+ * Coordinates, always from the input x0 in float64, rounded once: y = x0; for k in list order (a rotor with theta_k == 0 or
+ * coinciding ends is skipped) the atoms of S_k turn by theta_k about the line from y[p_k] through y[m_k] as it stands
+ * (Rodrigues); x_i = float32(t + R(q) y_i).  Start: theta = 0, t = 0, q = identity, so x = x0 bit for bit.  Because the S_k
+ * are nested or disjoint the geometry does not depend on the list order in real arithmetic, and bond lengths, angles and
+ * all distances inside a rigid piece are the input's up to one float32 rounding.
+ * An evaluation writes x to x_out, runs the sweep of dsbdd_vina_score_grad and that of dsbdd_vina_intra on it, and reads
+ * back E = (double)inter + (double)intra of the stored float32 values (compared with strict <), F and M (mol_grad[0..5]).
+ * At every accepted pose, with c the mean of its float32 coordinates: rho^2 = max(mean |x_i - c|^2, 1), rho_max = max |x_i - c|;
+ * per rotor a_k the unit vector from x[p_k] to x[m_k], tau_k = a_k . sum_{i in S_k} (x_i - x[m_k]) x (g_i^inter + g_i^intra)
+ * (the stored float32 gradients, float64 sums), r_k = the largest distance of an atom of S_k from axis k,
+ * rho_k^2 = max(mean over S_k of that distance squared, 1).  u = |F| + rho_max |M| / rho^2 + sum_k r_k |tau_k| / rho_k^2
+ * (switched-off blocks left out), alpha = L / u, and the trial is q' = normalise(dq q), t' = c + R(dq)(t - c) - alpha F (dq
+ * the rotation by -alpha M / rho^2: a rotation about c then a translation), theta_k' = theta_k - alpha tau_k / rho_k^2.  No atom
+ * moves more than L in a trial.  Steps 1-4, tol, max_evals and the statuses are those of dsbdd_vina_minimize with this E, u.
+ * Outputs, for the returned x_out: atom_out, mol_out, mol_flag, atom_grad, mol_grad bit for bit what dsbdd_vina_score_grad
+ * writes on x_out; intra_atom, intra_mol, intra_flag, intra_grad bit for bit what dsbdd_vina_intra writes on x_out;
+ * mol_pose [B][8] = t (3), q (4), rho^2 at the returned pose; mol_flex [B][8] = inter at the start, inter at the end, the last
+ * accepted L (0 if none), u at the returned pose, intra at the start, intra at the end, E at the start, E at the end;
+ * mol_stat as dsbdd_vina_minimize; theta, tau [B][32] in the slots of tor_end (0 where no valid kept rotor stands).  A
+ * molecule with a NaN or +-inf coordinate: status 3, x_out the input's bits, NaN in every other float it owns, both flags 1.
+ * No atomics, bitwise reproducible, independent of the rest of the batch.  batch = 0 launches nothing; the argument errors of
+ * dsbdd_vina_minimize, and dofs outside [1, 3], are DSBDD_ERR_ARG. */
+int dsbdd_vina_flex(void* stream, const float* lig_x, const int32_t* lig_code, const int32_t* mol_off, int64_t batch,
+                    const int32_t* mol_group, const int32_t* mol_int, const float* poc_x, const int32_t* poc_code,
+                    const int32_t* group_off, int64_t n_groups, const int32_t* tor_int, const int32_t* tor_end,
+                    const int32_t* tor_side, const int32_t* pair_mask, int32_t dofs, float step, float tol, int32_t max_evals,
+                    float* atom_out, float* mol_out, int32_t* mol_flag, float* atom_grad, float* mol_grad, float* intra_atom,
+                    float* intra_mol, int32_t* intra_flag, float* intra_grad, float* x_out, float* mol_pose, float* mol_flex,
+                    int32_t* mol_stat, float* theta, float* tau);
+
 /* ---- ligands as input: the packed batch of the design front ends -------------*/
 /* One launch that writes the ligand batch of substructure inpainting and of
  * diversification (inpaint.py:114-141, optimize.py:39-62 of the reference build
